@@ -2,7 +2,15 @@
 """bench.py -- megapixels/s restored on synthetic 512x512x1 micrograph batches (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload D|K|X|T|G|A|S|all] [--batch B]
-                    [--scaling weak|strong] [--dry-run]
+                    [--scaling weak|strong] [--dry-run] [--full] [--dump-outputs DIR]
+
+A plain run sets up the primary workload, warms it up, times exactly --steps steps and prints the JSON line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, config, and the roofline where it follows from the step time and algorithmic
+counts alone): nothing else runs on the device or the host.  --full adds everything else described below: the CPU baselines and parity against the oracle, the
+riders, per-kernel-family attribution, the isolated-GEMM / native-executor / small-batch / pinned-host legs and the on-box
+peaks.  --dump-outputs DIR writes what the primary workload's last timed step returned as DIR/<name>.npy (float32, rank 0,
+at most 64 MB in all: a fixed strided sample of a larger output); the inputs are seeded, so two builds compare output for
+output.
 
 A "step" is one pass of the hot path over one batch that is already resident in HBM.  Workloads:
   D  BASELINE configs[2], THE PRIMARY LINE: the modified-Xception encoder-decoder of machine_learning/denoiser.py on
@@ -16,8 +24,8 @@ A "step" is one pass of the hot path over one batch that is already resident in 
   A  BASELINE configs[4]: one adversarial training iteration of the in-filling GAN.
   S  SURVEY.md 8f rank 4: the small separable autoencoder (misc_py/apply_autoencoders.py) on 160-px crops.
 Default ("all"): the JSON line's metric/value/roofline/cpu_baseline are workload D's, measured with --steps/--warmup
-(default 20 / 5); with one rank K, X, T, G, S, A ride along under "workload_<letter>" with short fixed step counts, and a rider that
-throws is reported in the line AND makes the exit code non-zero.  With more than one rank only the primary workload runs (the
+(default 20 / 5); with --full and one rank K, X, T, G, S, A ride along under "workload_<letter>" with short fixed step counts, and a
+rider that throws is reported in the line AND makes the exit code non-zero.  With more than one rank only the primary workload runs (the
 training step's scaling: `--workload T --gpus N`); any exception there re-raises at once, so that the launcher tears every rank
 down instead of leaving the others in a collective.
 
@@ -92,7 +100,15 @@ def parse_args(argv=None):
                          "two = the two-half-batch form the headline step runs (a kernel's average then means 'beside the other half's kernels')")
     ap.add_argument("--precision", choices=["bf16x3", "bf16"], default="bf16x3",
                     help="matrix-core mode: bf16x3 = split-bf16 parity mode (default), bf16 = fast mode (never reported as parity)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: CPU baselines and oracle parity, the riders of --workload all, per-kernel-family "
+                         "attribution, isolated-GEMM / native-executor / small-batch / pinned-host legs, on-box peaks (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the primary workload's last timed step returned as DIR/<name>.npy (float32, rank 0, <= 64 MB in all)")
+    a = ap.parse_args(argv)
+    if (a.steps is not None and a.steps < 1) or (a.warmup is not None and a.warmup < 0):
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def _free_port():
@@ -230,6 +246,30 @@ def psnr_rel(y_gpu, y_ref):
     return (float("inf") if mse == 0 else round(10.0 * math.log10(1.0 / mse), 2)), float(f"{rel:.3e}")
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def keep_outputs(a, timer, rank, primary, **arrays):
+    """--dump-outputs: host float32 copies of what the primary workload's last timed step returned, taken right after the timed
+    steps (before any other leg runs on the device); written by write_outputs once the line is complete."""
+    if a.dump_outputs and primary and rank == 0:
+        timer.outputs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+
+
+def write_outputs(d, outputs):
+    """DIR/<name>.npy for every kept output; above DUMP_BUDGET_BYTES in all, every array is cut to the same fixed strided sample
+    of its flattened elements (the same elements in every run with the same arguments)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    total = sum(v.nbytes for v in outputs.values())
+    for name, v in outputs.items():
+        if total > DUMP_BUDGET_BYTES:
+            v = np.ascontiguousarray(v.reshape(-1)[::-(-total // DUMP_BUDGET_BYTES)])
+        np.save(os.path.join(d, name + ".npy"), v)
+        print(f"[bench] wrote {os.path.join(d, name + '.npy')}: {v.dtype} {list(v.shape)}", file=sys.stderr, flush=True)
+
+
 class Timer:
     """Barrier + synchronize on both sides, exactly `steps` steps, max over ranks (the bench contract); one HIP-event pair per
     step on the launch stream gives the median device-side step time beside it."""
@@ -237,6 +277,7 @@ class Timer:
     def __init__(self, torch, dist, dev):
         self.torch, self.dist, self.dev = torch, dist, dev
         self.gpu = dev is not None and dev.type == "cuda"
+        self.outputs = None   # keep_outputs
 
     def sync(self):
         if self.gpu:
@@ -719,6 +760,17 @@ def bench_K(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
             emdenoise.kernel_denoise(x, pd, 3, 2, params.symmetric, out=y)
 
     ms = timer.run(step, steps, warmup)
+    keep_outputs(a, timer, rank, primary, K_out=y if B else None)
+    alg_bytes = 8.0 * B * H * W  # SURVEY.md 8(d): 8 B per pixel (read 4 + write 4)
+    if not a.full:
+        achieved = alg_bytes / (ms * 1e-3) / 1e9
+        return {"value": total * H * W / 1e6 / (ms / 1e3), "unit": "MPx/s", "ms_per_step": ms, "median_hipevent_ms": timer.median_event_ms,
+                "steps": steps, "warmup": warmup, "dtype": "f32",
+                "config": {"workload": f"K: kernel denoiser depth 2 width 3 (noise-removal-kernels.py), [{B},{H},{W},1] fp32 per GPU",
+                           "global_batch": total, "image": f"{H}x{W}x1", "sharding": shard_note(a, world, B, total)},
+                "roofline": {"bound": "hbm", "kernel": "k3_roll<8,2>", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBPS, 4), "algorithmic_bytes_per_launch": alg_bytes,
+                             "how": "algorithmic bytes / step time (one launch per step); --full: HIP events around a hipGraph burst"}}
     # the dominant (only) kernel, timed live with HIP events on the launch stream: torch's current stream IS
     # the stream handed to the C ABI.  One event pair around a back-to-back burst cancels the per-event cost.
     n_burst = 50
@@ -734,7 +786,6 @@ def bench_K(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
     e1.record()
     torch.cuda.synchronize()
     launch_us = e0.elapsed_time(e1) * 1e3 / n_burst
-    alg_bytes = 8.0 * B * H * W  # SURVEY.md 8(d): 8 B per pixel (read 4 + write 4)
     achieved = alg_bytes / (launch_us * 1e-6) / 1e9
     tr, src = pmc_traffic()
     traffic = None
@@ -801,12 +852,40 @@ def bench_D(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
         eng.two_streams = eng.pipeline = False
     ms = timer.run(step, steps, warmup)
     med = timer.median_event_ms
+    keep_outputs(a, timer, rank, primary, D_out=box[0])
     if a.profile_clean:
         return {"value": total * H * W / 1e6 / (ms / 1e3), "unit": "MPx/s", "ms_per_step": ms, "median_hipevent_ms": med, "steps": steps, "warmup": warmup,
                 "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)",
                 "config": {"workload": f"D: modified-Xception encoder-decoder (machine_learning/denoiser.py), [{B},{H},{W},1] fp32 per GPU", "profile_clean": True},
                 "roofline": {"bound": "hbm", "achieved": round(d_graph_algorithmic_bytes(B, H) / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                              "frac": round(d_graph_algorithmic_bytes(B, H) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None}}
+    passes = 3 if a.precision == "bf16x3" else 1
+    alg_bytes = d_graph_algorithmic_bytes(B, H)
+    achieved = alg_bytes / (ms * 1e-3) / 1e9
+    tr, src = pmc_traffic()
+    traffic = None
+    if tr and (B, H, W) == (32, 512, 512):   # HBM bytes of every launch of one step (PMC run of `steps_sampled` forwards)
+        dk = {k: v for k, v in tr.items() if k.startswith("D:")}
+        if dk:
+            n = float(next(iter(dk.values())).get("steps_sampled", 4))
+            traffic = round(sum(v["hbm_bytes_per_launch_corrected"] * v["launches_sampled"] / n for v in dk.values()))
+    out = {
+        "value": total * H * W / 1e6 / (ms / 1e3), "unit": "MPx/s", "ms_per_step": ms, "median_hipevent_ms": med, "steps": steps, "warmup": warmup,
+        "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)" if passes == 3 else "bf16",
+        "config": {"workload": f"D: modified-Xception encoder-decoder (machine_learning/denoiser.py), [{B},{H},{W},1] fp32 per GPU",
+                   "global_batch": total, "image": f"{H}x{W}x1", "precision": a.precision, "sharding": shard_note(a, world, B, total)},
+        "roofline": {"bound": "hbm", "kernel": "whole step (every launch of one forward pass; the graph is HBM-bound end to end, SURVEY.md 8d)",
+                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                     "algorithmic_bytes_per_step": alg_bytes,
+                     "algorithmic_note": "fp32 activation bytes of a fully fused graph: in + out (+ residual) per layer, no depthwise intermediates "
+                                         "(bench.d_graph_algorithmic_bytes; 80.0 GB at B=32, 512^2: SURVEY 8d's 118 GB unfused - 45 GB depthwise intermediates + 6.5 GB residual reads)",
+                     "traffic": traffic, "traffic_source": src,
+                     "hbm_busy_frac": round(traffic / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
+                     "hbm_busy_note": "PMC bytes per step / step time / 8 TB/s (traffic above the algorithmic bytes = re-reads and unfused intermediates)",
+                     "how": "step time = wall clock over the timed steps (barrier + synchronize on both sides); median of per-step HIP events beside it"},
+    }
+    if not a.full:
+        return out
     # per-kernel-family device time of ONE more step on the single-stream launch sequence (with the two half batches staggered on
     # two streams -- DenoiserEngine.forward -- a launch's event pair would also span the other half's kernels)
     two, pipe = eng.two_streams, eng.pipeline
@@ -835,37 +914,15 @@ def bench_D(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
     dwp_bytes = sum(fam.bytes_.get(k, 0.0) for k in DWP)
     scale = (B / 32.0) * (H * W) / (512.0 * 512.0)
     alg_flops = 2.0 * D_GMAC_MATRIX_B32_512 * 1e9 * scale
-    passes = 3 if a.precision == "bf16x3" else 1
-    alg_bytes = d_graph_algorithmic_bytes(B, H)
-    achieved = alg_bytes / (ms * 1e-3) / 1e9
-    tr, src = pmc_traffic()
-    traffic = None
-    if tr and (B, H, W) == (32, 512, 512):   # HBM bytes of every launch of one step (PMC run of `steps_sampled` forwards)
-        dk = {k: v for k, v in tr.items() if k.startswith("D:")}
-        if dk:
-            n = float(next(iter(dk.values())).get("steps_sampled", 4))
-            traffic = round(sum(v["hbm_bytes_per_launch_corrected"] * v["launches_sampled"] / n for v in dk.values()))
-    out = {
-        "value": total * H * W / 1e6 / (ms / 1e3), "unit": "MPx/s", "ms_per_step": ms, "median_hipevent_ms": med, "steps": steps, "warmup": warmup,
-        "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)" if passes == 3 else "bf16",
-        "config": {"workload": f"D: modified-Xception encoder-decoder (machine_learning/denoiser.py), [{B},{H},{W},1] fp32 per GPU",
-                   "global_batch": total, "image": f"{H}x{W}x1", "precision": a.precision, "sharding": shard_note(a, world, B, total)},
-        "roofline": {"bound": "hbm", "kernel": "whole step (every launch of one forward pass; the graph is HBM-bound end to end, SURVEY.md 8d)",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                     "algorithmic_bytes_per_step": alg_bytes,
-                     "algorithmic_note": "fp32 activation bytes of a fully fused graph: in + out (+ residual) per layer, no depthwise intermediates "
-                                         "(bench.d_graph_algorithmic_bytes; 80.0 GB at B=32, 512^2: SURVEY 8d's 118 GB unfused - 45 GB depthwise intermediates + 6.5 GB residual reads)",
-                     "depthwise_frac": round(dw_bytes / (max(dw_ms, 1e-9) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                     "depthwise_path_frac": round(dwp_bytes / (max(dwp_ms, 1e-9) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                     "pointwise_frac": round(pw728_flops / (max(pw728_ms, 1e-9) * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-                     "targets_note": "north_star's two targets, where the driver keeps them: depthwise_frac = standalone depthwise launches, "
-                                     "depthwise_path_frac = every launch with a depthwise stage (standalone + fused separable convs), both algorithmic "
-                                     "bytes / device time / 8 TB/s (target 0.70); pointwise_frac = issued bf16 flops of the 728-channel pointwise "
-                                     "GEMMs / device time / 2.5 PFLOP/s (target 0.40); details under depthwise / depthwise_path / pointwise",
-                     "traffic": traffic, "traffic_source": src,
-                     "hbm_busy_frac": round(traffic / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if traffic else None,
-                     "hbm_busy_note": "PMC bytes per step / step time / 8 TB/s (traffic above the algorithmic bytes = re-reads and unfused intermediates)",
-                     "how": "step time = wall clock over the timed steps (barrier + synchronize on both sides); median of per-step HIP events beside it"},
+    out["roofline"].update({
+        "depthwise_frac": round(dw_bytes / (max(dw_ms, 1e-9) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+        "depthwise_path_frac": round(dwp_bytes / (max(dwp_ms, 1e-9) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+        "pointwise_frac": round(pw728_flops / (max(pw728_ms, 1e-9) * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+        "targets_note": "north_star's two targets, where the driver keeps them: depthwise_frac = standalone depthwise launches, "
+                        "depthwise_path_frac = every launch with a depthwise stage (standalone + fused separable convs), both algorithmic "
+                        "bytes / device time / 8 TB/s (target 0.70); pointwise_frac = issued bf16 flops of the 728-channel pointwise "
+                        "GEMMs / device time / 2.5 PFLOP/s (target 0.40); details under depthwise / depthwise_path / pointwise"})
+    out.update({
         "matrix_cores": {"bound": "mfma", "kernel": "gemm_conv + gemm_split* + sep_fused / sep_dual + deconv (every matrix-core launch of one step)",
                          "algorithmic_flops_per_step": alg_flops, "mfma_passes": passes, "kernel_ms_per_step": round(gemm_ms, 3),
                          "achieved_tflops": round(alg_flops / (max(gemm_ms, 1e-9) * 1e-3) / 1e12, 1),
@@ -894,7 +951,7 @@ def bench_D(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
                                                              "matrix pipe is busy with; pointwise_frac counts the unpadded 3 x 2MKN only",
                                        "note": "the launches with K or N = 728 (the matrix-core bound ones); the other launches of the family are HBM-bound"}},
         "kernel_family_ms": fam.table(),
-    }
+    })
     # the headline pointwise GEMM on its own (32768 x 728 x 728 at B = 32: 40 of D's layers), interleaved rounds in this
     # process: the default kernel, and the same pipeline on 16x16x32 MFMAs (opt-in: it sums a K step in another order)
     if (B, H, W) == (32, 512, 512) and rank == 0 and a.precision == "bf16x3":
@@ -1022,20 +1079,25 @@ def bench_X(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
             box[0] = eng.forward(x)
 
     ms = timer.run(step, steps, warmup)
+    keep_outputs(a, timer, rank, primary, X_out=box[0])
     if a.profile_clean:   # for rocprofv3: the timed steps and nothing else (graph X is single stream by construction)
         return {"value": round(total * H * W / 1e6 / (ms / 1e3), 1), "unit": "MPx/s", "ms_per_step": round(ms, 3), "steps": steps, "warmup": warmup,
                 "dtype": "bf16x3", "config": {"workload": f"X: [{B},{H},{W},1] fp32 per GPU", "profile_clean": True}, "roofline": None}
-    with FamilyTimer(torch, ops) as fam:
-        step()
     scale = (B / 32.0) * (H * W) / (512.0 * 512.0)
-    dec = ("conv3x3", "conv3x3_split32", "deconv3x3s2", "deconv3x3s2_split32", "deconv3x3s2_fused")
-    dec_ms = sum(fam.ms.get(k, 0.0) for k in dec)
-    dec_fl = sum(fam.flops.get(k, 0.0) for k in dec)
     out = {"value": round(total * H * W / 1e6 / (ms / 1e3), 1), "unit": "MPx/s", "ms_per_step": round(ms, 3), "median_hipevent_ms": timer.median_event_ms,
            "steps": steps, "warmup": warmup, "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)",
            "config": {"workload": f"X: Xception autoencoder (misc_py/modified_Xception.py), [{B},{H},{W},1] fp32 per GPU",
                       "precision": a.precision, "algorithmic_tflop_per_step": round(9.01 * scale, 3), "sharding": shard_note(a, world, B, total)},
            "tflops_algorithmic": round(9.01 * scale / (ms / 1e3), 1),
+           "roofline": None}   # the decoder family's figure takes an attribution step of its own: --full
+    if not a.full:
+        return out
+    with FamilyTimer(torch, ops) as fam:
+        step()
+    dec = ("conv3x3", "conv3x3_split32", "deconv3x3s2", "deconv3x3s2_split32", "deconv3x3s2_fused")
+    dec_ms = sum(fam.ms.get(k, 0.0) for k in dec)
+    dec_fl = sum(fam.flops.get(k, 0.0) for k in dec)
+    out.update({
            "roofline": {"bound": "mfma", "kernel": "decoder family: dense 3x3 convs + transposed convs (gemm_split_conv / gemm_conv), 60 % of X's flops",
                         "achieved": round(dec_fl / (max(dec_ms, 1e-9) * 1e-3) / 1e12, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                         "frac": round(dec_fl / (max(dec_ms, 1e-9) * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
@@ -1044,7 +1106,7 @@ def bench_X(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
                         "issued_frac": round(3.0 * dec_fl / (max(dec_ms, 1e-9) * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
                         "algorithmic_flops_per_step": dec_fl, "kernel_ms_per_step": round(dec_ms, 3),
                         "how": "HIP events around every launch of the family in one extra step; flops from the launch arguments"},
-           "kernel_family_ms": fam.table()}
+           "kernel_family_ms": fam.table()})
     if B and rank == 0 and H == W and H % 64 == 0 and a.precision == "bf16x3":
         # the same graph through the library's native executor (csrc/graph_exec_x.hip, emd_graph_create variant 2)
         try:
@@ -1096,9 +1158,21 @@ def bench_G(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
             box[0] = eng.forward(x)
 
     ms = timer.run(step, steps, warmup)
+    keep_outputs(a, timer, rank, primary, G_out=box[0])
     if a.profile_clean:   # for rocprofv3 (kernel statistics, PMC step totals): the timed steps and nothing else
         return {"value": round(total * S * S / 1e6 / (ms / 1e3), 1), "unit": "MPx/s in-filled", "ms_per_step": round(ms, 3), "steps": steps, "warmup": warmup,
                 "dtype": "bf16x3", "config": {"workload": f"G: [{B},{S},{S},1] fp32 per GPU", "profile_clean": True}, "roofline": None}
+    tflop = GN.algorithmic_flops(S) * B / 1e12
+    out = {"value": round(total * S * S / 1e6 / (ms / 1e3), 1), "unit": "MPx/s in-filled", "ms_per_step": round(ms, 3),
+           "median_hipevent_ms": timer.median_event_ms, "steps": steps, "warmup": warmup,
+           "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)",
+           "config": {"workload": f"G: in-filling generator forward (misc_py/gan-infilling-100.py), [{B},{S},{S},1] fp32 per GPU, "
+                                  f"1/64 of the pixels given ({a.mask} mask)", "precision": a.precision,
+                      "algorithmic_tflop_per_step": round(tflop, 3), "sharding": shard_note(a, world, B, total)},
+           "tflops_algorithmic": round(tflop / (ms / 1e3), 1),
+           "roofline": None}   # the matrix-core family's figure takes an attribution step of its own: --full
+    if not a.full:
+        return out
     two = getattr(eng, "two_streams", None)
     if two is not None:
         eng.two_streams = False
@@ -1108,15 +1182,8 @@ def bench_G(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
     finally:
         if two is not None:
             eng.two_streams = two
-    tflop = GN.algorithmic_flops(S) * B / 1e12
     mm, mf = fam.matrix_ms(), fam.matrix_flops()
-    out = {"value": round(total * S * S / 1e6 / (ms / 1e3), 1), "unit": "MPx/s in-filled", "ms_per_step": round(ms, 3),
-           "median_hipevent_ms": timer.median_event_ms, "steps": steps, "warmup": warmup,
-           "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)",
-           "config": {"workload": f"G: in-filling generator forward (misc_py/gan-infilling-100.py), [{B},{S},{S},1] fp32 per GPU, "
-                                  f"1/64 of the pixels given ({a.mask} mask)", "precision": a.precision,
-                      "algorithmic_tflop_per_step": round(tflop, 3), "sharding": shard_note(a, world, B, total)},
-           "tflops_algorithmic": round(tflop / (ms / 1e3), 1),
+    out.update({
            "roofline": {"bound": "mfma", "kernel": "matrix-core family (sep_fused + gemm_split + gemm_conv launches of one step)",
                         "achieved": round(mf / (max(mm, 1e-9) * 1e-3) / 1e12, 1), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                         "frac": round(mf / (max(mm, 1e-9) * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
@@ -1124,7 +1191,7 @@ def bench_G(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
                         "hbm_busy_frac": round(step_traffic("G")[0] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if (step_traffic("G")[0] and (B, S) == (32, 512)) else None,
                         "algorithmic_flops_per_step": mf, "kernel_ms_per_step": round(mm, 3),
                         "note": "<= 128 channels at 256-512 px: the graph is HBM-bound, the matrix-core fraction is low by construction"},
-           "kernel_family_ms": fam.table()}
+           "kernel_family_ms": fam.table()})
     if B:
         attach_cpu(out, cpu, "G", lambda rec: box[0][:1].cpu().numpy())
     return out
@@ -1154,6 +1221,7 @@ def bench_S(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
             box[0] = fwd(x)
 
     ms = timer.run(step, steps, warmup)
+    keep_outputs(a, timer, rank, primary, S_out=box[0])
     out = {"value": round(total * S * S / 1e6 / (ms / 1e3), 1), "unit": "MPx/s", "ms_per_step": round(ms, 3), "median_hipevent_ms": timer.median_event_ms,
            "steps": steps, "warmup": warmup, "dtype": "bf16x3 (split-bf16 MFMA inputs, fp32 accumulate and activations)",
            "config": {"workload": f"S: separable autoencoder (misc_py/apply_autoencoders.py), [{B},{S},{S},1] fp32 per GPU, "
@@ -1189,6 +1257,7 @@ def bench_A(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
 
     ms = timer.run(step, steps, warmup)
     rg, rd = box[0]
+    keep_outputs(a, timer, rank, primary, A_d_fake=rg, A_d_out=rd)
     out = {"value": round(T * S * S / 1e6 * world / (ms / 1e3), 2), "unit": "MPx/s trained (GAN)", "ms_per_step": round(ms, 3),
            "median_hipevent_ms": timer.median_event_ms,
            "steps": steps, "warmup": warmup, "dtype": "bf16x3 GEMMs (split-bf16 MFMA inputs, fp32 accumulate), fp32 elsewhere",
@@ -1224,6 +1293,7 @@ def bench_T(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
         box[0] = tr.train_step(x, t, tower_batch=tb, streams=a.train_streams, graph=not a.no_graph, batched=a.tower_mode == "batched")
 
     ms = timer.run(step, steps, warmup)
+    keep_outputs(a, timer, rank, primary, T_out=box[0])
     if a.profile_clean:   # for rocprofv3: run with --no-graph so that the trace names every kernel of the step
         return {"value": round(B * S * S / 1e6 * world / (ms / 1e3), 2), "unit": "MPx/s trained", "ms_per_step": round(ms, 3), "steps": steps, "warmup": warmup,
                 "dtype": "bf16x3", "config": {"workload": f"T: [{B},{S},{S},1] pairs per GPU, towers of {tb}, {a.tower_mode}", "profile_clean": True,
@@ -1241,7 +1311,7 @@ def bench_T(a, torch, emdenoise, dev, timer, rank, world, cpu, primary):
            "loss_first_tower": float(box[0][0, 1].item())}
     import torch.distributed as dist
 
-    if dist.is_available() and dist.is_initialized():
+    if a.full and dist.is_available() and dist.is_initialized():
         # the step's only exchange, timed on its own (SURVEY.md 8d cfg 4): all-reduce of the flat gradient + broadcast of
         # the moving statistics (with one rank the process group exists but there is nothing to exchange: RCCL init only)
         from emdenoise.trainer import sync_gradients
@@ -1342,14 +1412,14 @@ def _worker(a, real_stdout):
         # more than one rank: the primary workload only.  The training step is the one workload with a collective, and a failure in
         # a rider would take the inference scaling figure down with it (a rider's exception tears every rank down): its scaling
         # is measured on its own with `--workload T --gpus N`
-        riders = [] if (a.no_riders or multi) else (["K"] if a.workload == "both" else ["K", "X", "T", "G", "S", "A"])
+        riders = [] if (a.no_riders or multi or not a.full) else (["K"] if a.workload == "both" else ["K", "X", "T", "G", "S", "A"])
     else:
         primary, riders = a.workload, []
     # the CPU baselines FIRST, in a child that never sees a GPU, while this process has not yet loaded torch or the HIP runtime
     cpu = None
     if a.profile_clean:
         riders = []
-    if rank == 0 and not multi and not a.no_cpu_baseline and not a.profile_clean:
+    if rank == 0 and not multi and a.full and not a.no_cpu_baseline and not a.profile_clean:
         assert "torch" not in sys.modules, "the CPU-baseline child must be started before this process loads torch / HIP"
         cpu = run_cpu_child(a, a.argv, [primary] + [w for w in riders if w != "A"])
 
@@ -1411,7 +1481,7 @@ def _worker(a, real_stdout):
               "depthwise_path", "small_batch", "kernel_family_ms", "from_pinned_host", "native_executor", "tflops_algorithmic", "loss_first_tower", "allreduce", "d_fake_first", "d_out_first"):
         if k in prim:
             out[k] = prim[k]
-    if rank == 0 and primary == "D" and not multi and not a.profile_clean:
+    if rank == 0 and primary == "D" and not multi and a.full and not a.profile_clean:
         note("on-box peaks ...")
         pk = out["measured_peaks"] = measured_peaks(torch, dev)
         # the same fractions against what THIS device delivers (nominal and measured peaks, both stated)
@@ -1433,6 +1503,8 @@ def _worker(a, real_stdout):
         out["workload_" + w] = r
     if failed:
         out["failed_riders"] = failed
+    if timer.outputs is not None:
+        write_outputs(a.dump_outputs, timer.outputs)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

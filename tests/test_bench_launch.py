@@ -54,6 +54,37 @@ def test_gpus_must_match_world_size():
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)
 
 
+def test_dump_outputs_within_budget_and_fixed(tmp_path):
+    """--dump-outputs: arrays under the budget are written whole; above it every array is cut to the same strided sample."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = np.arange(12, dtype=np.float32).reshape(3, 4)
+    bench.write_outputs(str(tmp_path / "a"), {"y": small})
+    assert np.array_equal(np.load(tmp_path / "a" / "y.npy"), small)
+    big = np.arange(bench.DUMP_BUDGET_BYTES // 4 + 1000, dtype=np.float32)
+    bench.write_outputs(str(tmp_path / "b"), {"y": big, "z": small})
+    files = sorted((tmp_path / "b").iterdir())
+    assert [f.name for f in files] == ["y.npy", "z.npy"]
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_BUDGET_BYTES
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), big[::2])
+    assert np.array_equal(np.load(tmp_path / "b" / "z.npy"), small.reshape(-1)[::2])
+
+
+def test_full_and_dump_options():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def test_algorithmic_bytes_of_graph_d():
     sys.path.insert(0, ROOT)
     import bench
