@@ -23,6 +23,12 @@ class PackJob(C.Structure):
                 ("cout_major", C.c_int), ("cpad", C.c_int), ("pad_", C.c_int)]
 
 
+class KFusedJob(C.Structure):
+    """include/emdenoise.h emd_k_fused_job_t"""
+    _fields_ = [("theta", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("step", C.c_void_p),
+                ("params_out", C.c_void_p), ("losses", C.c_void_p), ("width", C.c_int), ("depth", C.c_int)]
+
+
 SIGNATURES = {
     "emd_version": (C.c_int, []),
     "emd_last_error": (C.c_char_p, []),
@@ -30,6 +36,19 @@ SIGNATURES = {
     "emd_kernel_params_count": (C.c_size_t, [C.c_int, C.c_int]),
     "emd_kernel_denoise_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _c_float_p, C.c_uint, C.c_void_p]),
+    "emd_k_train_scalar_count": (C.c_size_t, [C.c_int, C.c_int]),
+    "emd_k_train_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # x B H W width depth loss_mode theta m v step lr0 total_steps beta1 beta2 eps flags grad loss params workspace ws_bytes stream
+    "emd_k_train_step_f32": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_float_p, _c_float_p,
+                                       _c_float_p, C.c_void_p, C.c_double, C.c_long, C.c_float, C.c_float, C.c_float, C.c_uint,
+                                       _c_float_p, _c_float_p, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # stack N H W crops B crop seed first_index draws stream
+    "emd_k_sample_crops_f32": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_ulonglong,
+                                         C.c_ulonglong, C.c_void_p, C.c_void_p]),
+    # jobs njobs stack N H W batches nbatches B crop seed nsteps loss_mode lr0 total_steps beta1 beta2 eps stream
+    "emd_k_train_fused_f32": (C.c_int, [C.c_void_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int, _c_float_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.c_double, C.c_long, C.c_float, C.c_float,
+                                        C.c_float, C.c_void_p]),
     "emd_packed_weight_elems": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "emd_pack_weights_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # x ldx whi wlo scale1 shift1 scale2 shift2 res ldres y ldy B H W Cin Cout stride act precision stream

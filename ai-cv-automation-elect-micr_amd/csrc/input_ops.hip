@@ -15,28 +15,15 @@
 #include <cmath>
 
 #include "emd_common.hpp"
+#include "philox.hpp"
 
 namespace {
 
-constexpr unsigned kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-// stream tags (counter word 3): independent sequences under one seed
-constexpr unsigned kTagRaw = 0u, kTagScale = 1u, kTagChoice = 2u, kTagPoisson = 3u;
-
-struct U4 {
-    unsigned x, y, z, w;
-};
-
-__host__ __device__ inline U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)kPhiloxM0 * c.x, p1 = (unsigned long long)kPhiloxM1 * c.z;
-        const U4 n = {(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        c = n;
-        k0 += kPhiloxW0;
-        k1 += kPhiloxW1;
-    }
-    return c;
-}
+// stream tags (counter word 3): independent sequences under one seed (philox.hpp lists every tag of the library)
+constexpr unsigned kTagRaw = emd::kPhiloxTagRaw, kTagScale = emd::kPhiloxTagScale, kTagChoice = emd::kPhiloxTagChoice,
+                   kTagPoisson = emd::kPhiloxTagPoisson;
+using emd::U4;
+using emd::philox4x32_10;
 
 // uniform double in (0, 1): the top 52 bits of two words, (m + 1/2) / 2^52 -- exactly representable, never 0 and never 1
 __device__ inline double u01(unsigned hi, unsigned lo) {

@@ -195,12 +195,21 @@ class Micrograph_Autoencoder(object):
 def load_kernel_params(ckpt_loc, depth: int, width: int) -> KernelParams:
     """Load filter scalars saved as ``<ckpt_loc>/kernel_params_depth-{d}_size-{w}.npz`` with the
     TF variable names as keys (``depth-{d}_size-{w}/w0/var_x-{x}_y-{y}/v`` ...,
-    ``depth-{d}_size-{w}/fully_connected[_k]/weights``).  Reading TensorFlow checkpoint bundles
-    directly is a later step."""
+    ``depth-{d}_size-{w}/fully_connected[_k]/weights``).  When there is no such file, the same names
+    are read from the TensorFlow checkpoint ``tf_checkpoint.latest_checkpoint(ckpt_loc)`` -- what the
+    reference restores (apply_kernels+MLPs.py:604) and what KernelDenoiserTrainer.save_checkpoint writes."""
     import os
 
     path = os.path.join(ckpt_loc, f"kernel_params_depth-{depth}_size-{width}.npz")
-    z = np.load(path, allow_pickle=False)
+    if os.path.exists(path):
+        z = np.load(path, allow_pickle=False)
+    else:
+        from . import tf_checkpoint
+
+        prefix = tf_checkpoint.latest_checkpoint(ckpt_loc)
+        if prefix is None:
+            raise FileNotFoundError(f"{ckpt_loc}: neither {os.path.basename(path)} nor a TF checkpoint")
+        z = tf_checkpoint.read_checkpoint(prefix)
     scope = f"depth-{depth}_size-{width}"
     pairs = sym_pairs(width)
 

@@ -74,6 +74,69 @@ int emd_kernel_denoise_f32(const float* x, float* y, int B, int H, int W, int wi
                            const float* params, unsigned flags, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Graph K training (csrc/k_train.hip).
+ * replaces: misc_py/noise-removal-kernels.py:409-446 (the unrolled per-pixel filter graph, its MSE loss, TF's gradient and
+ *           one AdamOptimizer per filter), :665-678 (lr = lr0 (1 - t / (T + 1))), :450-538 (the host input path).
+ *
+ * The trainable state of one (depth, width) filter is `theta`, emd_k_train_scalar_count(width, depth) float32 make_layer
+ * scalars (nsym = (o+1)(o+2)/2 per map, o = width/2, in make_layer's creation order x = 0..o, y = 0..x):
+ *     w [depth][nsym]   the weight maps w0 .. w(depth-1)
+ *     b [depth-1][nsym] the bias maps b1 .. b(depth-1)
+ *     s [depth-1]       the fully_connected scalars s1 .. s(depth-1)
+ * A scalar's gradient is the sum over the D4-symmetric taps that share it.
+ *
+ * emd_k_train_step_f32: one training (or evaluation) step on a device batch x [B,H,W] (any B, H, W; width/2 < min(H,W)).
+ *   loss_mode EMD_K_LOSS_REFERENCE: mean((F(x)^T - x)^2), what the reference minimises (its output is assembled
+ *             transposed, :421-424; H == W);  EMD_K_LOSS_IMAGE: mean((F(x) - x)^2).
+ *   flags     EMD_K_TRAIN_UPDATE: apply TF's Adam to theta with adam_m / adam_v and the device step counter *step (completed
+ *             steps; incremented), lr_t = lr sqrt(1-beta2^t)/(1-beta1^t), lr = float32(lr0 (1 - t/(total_steps+1))), t = *step + 1.
+ *             EMD_K_TRAIN_LOSS_ONLY: forward pass and loss only (no backward, no update).  Neither: loss and gradient.
+ *   grad_out  [nscal] dL/dtheta (NULL: not stored); loss_out [1] the loss with the parameters BEFORE the update (NULL: not
+ *             stored); params_out: the packed block of emd_kernel_denoise_f32 (emd_kernel_params_count) expanded from the
+ *             updated theta (NULL: not written).  All device pointers; adam_m / adam_v / step may be NULL without UPDATE.
+ *   workspace device scratch of emd_k_train_workspace_bytes(B, H, W, width, depth) bytes.
+ * Deterministic: no atomics; the same inputs give the same bits. */
+#define EMD_K_LOSS_REFERENCE 0
+#define EMD_K_LOSS_IMAGE 1
+#define EMD_K_TRAIN_UPDATE 1u
+#define EMD_K_TRAIN_LOSS_ONLY 2u
+size_t emd_k_train_scalar_count(int width, int depth);
+size_t emd_k_train_workspace_bytes(int B, int H, int W, int width, int depth);
+int emd_k_train_step_f32(const float* x, int B, int H, int W, int width, int depth, int loss_mode, float* theta, float* adam_m,
+                         float* adam_v, int* step, double lr0, long total_steps, float beta1, float beta2, float eps,
+                         unsigned flags, float* grad_out, float* loss_out, float* params_out, void* workspace,
+                         size_t workspace_bytes, emd_stream_t stream);
+/* The K trainer's input path on the device: B crops of crop x crop from the device stack [N,H,W] (H, W > crop).  Crop b draws
+ * Philox4x32-10(counter = (first_index + b, 0, tag 4), key = seed) -> image n, offsets x = randint(0, H-crop),
+ * y = randint(0, W-crop) (:457-462), D4 element (flip_rotate, :498-515), then NaN/Inf -> 0, scale0to1 (constant -> 0.5),
+ * / mean (preprocess, :517-529) and all-zero if any value is non-finite (record_parser, :531-538).  draws_out (int32 [B][4] =
+ * n, x, y, element; may be NULL) records the draws.  The trainer passes first_index = step * B. */
+int emd_k_sample_crops_f32(const float* stack, int N, int H, int W, float* crops, int B, int crop, unsigned long long seed,
+                           unsigned long long first_index, int* draws_out, emd_stream_t stream);
+/* The fused small-batch form (the reference's 32 x 10 x 10): one workgroup per filter runs `nsteps` (1..EMD_K_FUSED_MAX_STEPS)
+ * complete steps in one launch per depth present -- sample (as emd_k_sample_crops_f32, crop index (t-1) * B + b for the 1-based
+ * step t read from the filter's counter) or take fixed batch (it % nbatches) of `batches` [nbatches][B][crop][crop] when that is
+ * not NULL, then forward + backward, the reduction in LDS and Adam -- and writes the loss of every step to losses[it] (the
+ * parameters before update it).  Needs B * crop^2 <= EMD_K_FUSED_MAX_PIXELS (the batch lives in LDS) and square crops.
+ * Deterministic; it sums in another order than emd_k_train_step_f32 (and the sampled crops' means may differ in the last bit),
+ * so the two forms agree to rounding, not bit for bit.  params_out may be NULL; every other job pointer is required. */
+#define EMD_K_FUSED_MAX_STEPS 1000
+#define EMD_K_FUSED_MAX_PIXELS 8192
+typedef struct {
+    float* theta;      /* [emd_k_train_scalar_count] */
+    float* adam_m;
+    float* adam_v;
+    int* step;         /* completed steps; advanced by nsteps */
+    float* params_out; /* packed emd_kernel_denoise_f32 block after the last step, or NULL */
+    float* losses;     /* [nsteps] */
+    int width;
+    int depth;
+} emd_k_fused_job_t;
+int emd_k_train_fused_f32(const emd_k_fused_job_t* jobs, int njobs, const float* stack, int N, int H, int W, const float* batches,
+                          int nbatches, int B, int crop, unsigned long long seed, int nsteps, int loss_mode, double lr0,
+                          long total_steps, float beta1, float beta2, float eps, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Graph D: the depthwise-separable encoder-decoder (machine_learning/denoiser.py:58-398).
  *
  * Fused epilogue shared by the matrix-core entry points (per output channel n):
