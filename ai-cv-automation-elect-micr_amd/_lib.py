@@ -49,6 +49,16 @@ SIGNATURES = {
     "emd_k_train_fused_f32": (C.c_int, [C.c_void_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int, _c_float_p, C.c_int, C.c_int,
                                         C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.c_double, C.c_long, C.c_float, C.c_float,
                                         C.c_float, C.c_void_p]),
+    # stack N H W crops x4 B crop seed first_index first_index_dev draws stream
+    "emd_s_sample_crops_f32": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, _c_float_p, _c_float_p, C.c_int, C.c_int, C.c_ulonglong,
+                                         C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "emd_s_head_bwd_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # out x a lda w9 B H W C da ldo dw9 dbias loss workspace ws_bytes stream
+    "emd_s_head_bwd_f32": (C.c_int, [_c_float_p, _c_float_p, _c_float_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _c_float_p, C.c_int, _c_float_p, _c_float_p, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_s_mse_loss_workspace_bytes": (C.c_size_t, []),
+    "emd_s_mse_loss_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_long, _c_float_p, _c_float_p, C.c_void_p, C.c_void_p]),
+    "emd_relu_mask_bwd_f32": (C.c_int, [_c_float_p, _c_float_p, _c_float_p, C.c_long, C.c_void_p]),
     "emd_packed_weight_elems": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "emd_pack_weights_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # x ldx whi wlo scale1 shift1 scale2 shift2 res ldres y ldy B H W Cin Cout stride act precision stream

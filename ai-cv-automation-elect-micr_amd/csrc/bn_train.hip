@@ -21,6 +21,7 @@ __device__ __forceinline__ float grad_mask(float dy, float z, int mask) {
     if (mask == 1) return (z > 0.f && z < 6.f) ? dy : 0.f;   // tf.nn.relu6 (Relu6Grad: 0 < z < 6)
     if (mask == 2) return (z > 0.f && z <= 1.f) ? dy : 0.f;  // relu6 then tf.clip_by_value(., 0, 1) (passes on [0,1])
     if (mask == 3) return z > 0.f ? dy : 0.2f * dy;           // tf.nn.leaky_relu, alpha 0.2 (graph G)
+    if (mask == 4) return z > 0.f ? dy : 0.f;                 // tf.nn.relu (ReluGrad: z > 0; graph S)
     return dy;
 }
 
@@ -619,7 +620,7 @@ static int bwd_reduce_impl(const float* dy, int ldd, const float* x, int ldx, co
     EMD_REQUIRE(!c1.g1 || (c1.w9 && x && C % 4 == 0 && ldx % 4 == 0 && emd::aligned16(x) && emd::aligned16(c1.w9) && c1.H >= 1 && c1.W >= 1 &&
                            npix % ((long)c1.H * c1.W) == 0), EMD_E_INVALID, "emd_bn_bwd_reduce_prep_cout1_f32: bad argument");
     EMD_REQUIRE(!prep || (x && !accumulate_s1), EMD_E_INVALID, "emd_bn_bwd_reduce_prep_f32: the per-channel step needs x (both sums)");
-    EMD_REQUIRE(B >= 1 && B <= 65535 && npix >= 1 && C >= 1 && mask >= 0 && mask <= 3, EMD_E_INVALID, "emd_bn_bwd_reduce_f32: bad argument");
+    EMD_REQUIRE(B >= 1 && B <= 65535 && npix >= 1 && C >= 1 && mask >= 0 && mask <= 4, EMD_E_INVALID, "emd_bn_bwd_reduce_f32: bad argument");
     EMD_REQUIRE(!x || (mean && rstd && s2), EMD_E_INVALID, "emd_bn_bwd_reduce_f32: x needs mean, rstd and s2");
     EMD_REQUIRE(!mask || (x && mscale && mshift), EMD_E_INVALID, "emd_bn_bwd_reduce_f32: a mask needs x, mscale, mshift");
     EMD_REQUIRE(B == 1 || !accumulate_s1, EMD_E_INVALID, "emd_bn_bwd_reduce_images_f32: accumulate_s1 is a batch-form option");
@@ -699,7 +700,7 @@ static int bwd_apply_impl(const float* dy, int ldd, const float* x, int ldx, con
     EMD_REQUIRE((dy || c1.g1) && x && K && m1 && mean && m2 && dx, EMD_E_INVALID, "emd_bn_bwd_apply_f32: null pointer");
     EMD_REQUIRE(!c1.g1 || (c1.w9 && C % 4 == 0 && emd::aligned16(c1.w9) && c1.H >= 1 && c1.W >= 1 && npix % ((long)c1.H * c1.W) == 0),
                 EMD_E_INVALID, "emd_bn_bwd_apply_cout1_f32: bad argument");
-    EMD_REQUIRE(B >= 1 && B <= 65535 && npix >= 1 && C >= 1 && mask >= 0 && mask <= 3 && (!mask || (mscale && mshift)), EMD_E_INVALID,
+    EMD_REQUIRE(B >= 1 && B <= 65535 && npix >= 1 && C >= 1 && mask >= 0 && mask <= 4 && (!mask || (mscale && mshift)), EMD_E_INVALID,
                 "emd_bn_bwd_apply_f32: bad argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (C % 4 == 0 && (c1.g1 || (ldd % 4 == 0 && emd::aligned16(dy))) && ldx % 4 == 0 && ldo % 4 == 0 && emd::aligned16(x) &&
@@ -845,7 +846,7 @@ extern "C" int emd_bn_train_bwd_small_f32(const float* dy, int ldd, const float*
                                           float* dbeta2, float* dx, int ldo, emd_stream_t stream) {
     EMD_REQUIRE(dy && x && mean && rstd1 && gamma2 && dgamma2 && dbeta2 && dx, EMD_E_INVALID, "emd_bn_train_bwd_small_f32: null pointer");
     EMD_REQUIRE(!gamma1 || (rstd2 && dgamma1), EMD_E_INVALID, "emd_bn_train_bwd_small_f32: BN1 needs rstd2 and dgamma1");
-    EMD_REQUIRE(B >= 1 && B <= 65535 && mask >= 0 && mask <= 3 && (!mask || (mscale && mshift)), EMD_E_INVALID, "emd_bn_train_bwd_small_f32: bad argument");
+    EMD_REQUIRE(B >= 1 && B <= 65535 && mask >= 0 && mask <= 4 && (!mask || (mscale && mshift)), EMD_E_INVALID, "emd_bn_train_bwd_small_f32: bad argument");
     EMD_REQUIRE(emd_bn_train_small_supported(npix, C), EMD_E_UNSUPPORTED, "emd_bn_train_bwd_small_f32: needs npix <= 4096 and C % 4 == 0");
     EMD_REQUIRE(ldd % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && ldd >= C && ldx >= C && ldo >= C && emd::aligned16(dy) && emd::aligned16(x) &&
                     emd::aligned16(dx), EMD_E_ALIGN, "emd_bn_train_bwd_small_f32: alignment");

@@ -25,6 +25,7 @@ __device__ __forceinline__ float grad_mask(float dy, float z, int mask) {   // b
     if (mask == 1) return (z > 0.f && z < 6.f) ? dy : 0.f;
     if (mask == 2) return (z > 0.f && z <= 1.f) ? dy : 0.f;
     if (mask == 3) return z > 0.f ? dy : 0.2f * dy;
+    if (mask == 4) return z > 0.f ? dy : 0.f;
     return dy;
 }
 
@@ -405,7 +406,7 @@ extern "C" int emd_dw3x3_bn_bwd_reduce_f32(const float* dd, int ldd, const float
     EMD_REQUIRE((stride == 1 || stride == 2) && rate >= 1 && (rate == 1 || stride == 1), EMD_E_INVALID, "emd_dw3x3_bn_bwd_reduce_f32: stride 1 or 2; rate > 1 needs stride 1");
     EMD_REQUIRE(!dw_consumer || mask == 1, EMD_E_INVALID, "emd_dw3x3_bn_bwd_reduce_f32: the consumer's weight gradient needs the relu6 mask (x = relu6(r*mscale + mshift))");
     EMD_REQUIRE(w_flipped && mean && rstd && s1 && s2 && workspace, EMD_E_INVALID, "emd_dw3x3_bn_bwd_reduce_f32: null pointer");
-    EMD_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && mask >= 0 && mask <= 3 && (!mask || (mscale && mshift)), EMD_E_INVALID,
+    EMD_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && mask >= 0 && mask <= 4 && (!mask || (mscale && mshift)), EMD_E_INVALID,
                 "emd_dw3x3_bn_bwd_reduce_f32: bad argument");
     EMD_REQUIRE(args_ok(dd, ldd, C) && args_ok(r, ldr, C) && emd::aligned16(w_flipped) && emd::aligned16(mean) && emd::aligned16(rstd) &&
                     (!mask || (emd::aligned16(mscale) && emd::aligned16(mshift))) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
@@ -431,7 +432,7 @@ extern "C" int emd_dw3x3_bn_bwd_apply_f32(const float* dd, int ldd, const float*
                                           emd_stream_t stream) {
     EMD_REQUIRE((stride == 1 || stride == 2) && rate >= 1 && (rate == 1 || stride == 1), EMD_E_INVALID, "emd_dw3x3_bn_bwd_apply_f32: stride 1 or 2; rate > 1 needs stride 1");
     EMD_REQUIRE(w_flipped && K && m1 && mean && m2 && dr, EMD_E_INVALID, "emd_dw3x3_bn_bwd_apply_f32: null pointer");
-    EMD_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && mask >= 0 && mask <= 3 && (!mask || (mscale && mshift)), EMD_E_INVALID,
+    EMD_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && mask >= 0 && mask <= 4 && (!mask || (mscale && mshift)), EMD_E_INVALID,
                 "emd_dw3x3_bn_bwd_apply_f32: bad argument");
     EMD_REQUIRE(args_ok(dd, ldd, C) && args_ok(r, ldr, C) && args_ok(dr, ldo, C) && emd::aligned16(w_flipped) && emd::aligned16(K) &&
                     emd::aligned16(m1) && emd::aligned16(mean) && emd::aligned16(m2) && (!mask || (emd::aligned16(mscale) && emd::aligned16(mshift))),

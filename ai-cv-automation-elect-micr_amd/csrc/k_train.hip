@@ -295,15 +295,21 @@ __device__ __forceinline__ unsigned draw_below(unsigned r, unsigned n) {   // fl
     return (unsigned)(((unsigned long long)r * n) >> 32);
 }
 
+// S = true: graph S's input path (misc_py/autoencoder.py:190-274): its own Philox tag, a non-finite crop becomes ONES (:271-272),
+// x4 (may be NULL) receives a copy of every crop in channel 0 of a [B][crop][crop][4] tensor (its other channels are not touched), and
+// first_index_dev (may be NULL) holds the first crop index on the device (a replayed graph).
+template <bool S>
 __global__ __launch_bounds__(kThreads) void k_sample_kernel(const float* __restrict__ stack, int N, int H, int W,
                                                             float* __restrict__ crops, int crop, unsigned long long seed,
-                                                            unsigned long long first_index, int* __restrict__ draws) {
+                                                            unsigned long long first_index, int* __restrict__ draws,
+                                                            float* __restrict__ x4, const unsigned long long* __restrict__ first_index_dev) {
     __shared__ float shf[kWaves];
     __shared__ double shd[kWaves];
     __shared__ int bad;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const unsigned long long idx = first_index + (unsigned long long)b;
-    const emd::U4 r = emd::philox4x32_10(emd::U4{(unsigned)idx, (unsigned)(idx >> 32), 0u, emd::kPhiloxTagKCrop},
+    const unsigned long long idx = (S && first_index_dev ? *first_index_dev : first_index) + (unsigned long long)b;
+    constexpr unsigned tag = S ? emd::kPhiloxTagSCrop : emd::kPhiloxTagKCrop;
+    const emd::U4 r = emd::philox4x32_10(emd::U4{(unsigned)idx, (unsigned)(idx >> 32), 0u, tag},
                                          (unsigned)seed, (unsigned)(seed >> 32));
     const int n = (int)draw_below(r.x, (unsigned)N);
     const int x0 = (int)draw_below(r.y, (unsigned)(H - crop));   // np.random.randint(0, H - crop): upper bound exclusive
@@ -359,8 +365,10 @@ __global__ __launch_bounds__(kThreads) void k_sample_kernel(const float* __restr
     }
     if (nonfinite) bad = 1;   // benign race: every writer stores 1
     __syncthreads();
-    if (bad)   // record_parser (:534-535): a crop with any non-finite value becomes zeros
-        for (int k = tid; k < np_; k += kThreads) out[k] = 0.f;
+    if (bad)   // record_parser (:534-535): a crop with any non-finite value becomes zeros (graph S: ones)
+        for (int k = tid; k < np_; k += kThreads) out[k] = S ? 1.f : 0.f;
+    if (S && x4)   // each thread copies only what it wrote itself
+        for (int k = tid; k < np_; k += kThreads) x4[((size_t)b * np_ + k) * 4] = out[k];
 }
 
 
@@ -694,8 +702,22 @@ extern "C" int emd_k_sample_crops_f32(const float* stack, int N, int H, int W, f
     EMD_REQUIRE(crop < H && crop < W, EMD_E_INVALID,
                 "emd_k_sample_crops_f32: crop must be smaller than the image (randint(0, H - crop) needs H > crop)");
     EMD_REQUIRE(B <= 0x7fffffff / 4, EMD_E_UNSUPPORTED, "emd_k_sample_crops_f32: batch too large");
-    hipLaunchKernelGGL(k_sample_kernel, dim3(B), dim3(kThreads), 0, static_cast<hipStream_t>(stream), stack, N, H, W, crops, crop, seed,
-                       first_index, draws_out);
+    hipLaunchKernelGGL(k_sample_kernel<false>, dim3(B), dim3(kThreads), 0, static_cast<hipStream_t>(stream), stack, N, H, W, crops, crop, seed,
+                       first_index, draws_out, nullptr, nullptr);
+    return emd::check_launch("k_sample_kernel");
+}
+
+extern "C" int emd_s_sample_crops_f32(const float* stack, int N, int H, int W, float* crops, float* x4, int B, int crop,
+                                      unsigned long long seed, unsigned long long first_index,
+                                      const unsigned long long* first_index_dev, int* draws_out, emd_stream_t stream) {
+    EMD_REQUIRE(stack && crops, EMD_E_INVALID, "emd_s_sample_crops_f32: null pointer");
+    EMD_REQUIRE(N >= 1 && H >= 1 && W >= 1 && B >= 1 && crop >= 1, EMD_E_INVALID, "emd_s_sample_crops_f32: bad shape");
+    EMD_REQUIRE(crop < H && crop < W, EMD_E_INVALID,
+                "emd_s_sample_crops_f32: crop must be smaller than the image (randint(0, H - crop) needs H > crop)");
+    EMD_REQUIRE(B <= 0x7fffffff / 4, EMD_E_UNSUPPORTED, "emd_s_sample_crops_f32: batch too large");
+    EMD_REQUIRE((long)B * crop * crop * 4 < (1L << 40), EMD_E_UNSUPPORTED, "emd_s_sample_crops_f32: batch too large");
+    hipLaunchKernelGGL(k_sample_kernel<true>, dim3(B), dim3(kThreads), 0, static_cast<hipStream_t>(stream), stack, N, H, W, crops, crop, seed,
+                       first_index, draws_out, x4, first_index_dev);
     return emd::check_launch("k_sample_kernel");
 }
 

@@ -9,7 +9,7 @@ namespace emd {
 
 constexpr unsigned kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 // stream tags (counter word 3)
-constexpr unsigned kPhiloxTagRaw = 0u, kPhiloxTagScale = 1u, kPhiloxTagChoice = 2u, kPhiloxTagPoisson = 3u, kPhiloxTagKCrop = 4u;
+constexpr unsigned kPhiloxTagRaw = 0u, kPhiloxTagScale = 1u, kPhiloxTagChoice = 2u, kPhiloxTagPoisson = 3u, kPhiloxTagKCrop = 4u, kPhiloxTagSCrop = 5u;
 
 struct U4 {
     unsigned x, y, z, w;

@@ -89,6 +89,30 @@ def k_record_parser(img, rng, crop: int = 10):
     return k_crop(img, x, y, choice, crop)
 
 
+
+def s_crop(img, x: int, y: int, choice: int, crop: int = 160):
+    """Graph S's crop (misc_py/autoencoder.py:190-274): the crop of load_image at (x, y), flip_rotate(choice), preprocess -- the
+    steps of k_crop -- but a crop with any non-finite value afterwards becomes ONES (:271-272), where K's becomes zeros."""
+    img = np.asarray(img, dtype=np.float32)
+    img = img.reshape(img.shape[0], img.shape[1])
+    out = k_preprocess(k_flip_rotate(img[x:x + crop, y:y + crop], choice))
+    if np.sum(np.isfinite(out)) != crop * crop:
+        out = np.ones((crop, crop), np.float32)
+    return out
+
+
+def s_record_parser(img, rng, crop: int = 160):
+    """Graph S's host input path for one [H,W(,1)] image: draws x = randint(0, H - crop), y = randint(0, W - crop) and the D4
+    element from ``rng`` (numpy Generator), in that order (autoencoder.py:190-233), then s_crop."""
+    img = np.asarray(img, dtype=np.float32)
+    H, W = img.shape[0], img.shape[1]
+    if H <= crop or W <= crop:
+        raise ValueError(f"crop {crop} needs an image larger than it, got {H}x{W}")
+    x = int(rng.integers(0, H - crop))
+    y = int(rng.integers(0, W - crop))
+    choice = int(rng.integers(0, 8))
+    return s_crop(img, x, y, choice, crop)
+
 # ---- schedule and parameter vectors -------------------------------------------------------------------------------------
 def lr_schedule(t: int, lr0: float = 0.005, total_steps: int = 20000) -> float:
     """:665-669: lr = lr0 (1 - t / (total_steps + 1)) for the 1-based step t."""

@@ -10,7 +10,7 @@ import ctypes as C
 from . import _lib
 from .ops import PREC_BF16X3, Act, _act, _p
 
-MASK_NONE, MASK_RELU6, MASK_RELU6_CLIP, MASK_LEAKY = 0, 1, 2, 3
+MASK_NONE, MASK_RELU6, MASK_RELU6_CLIP, MASK_LEAKY, MASK_RELU = 0, 1, 2, 3, 4
 BN_EPS = 1e-3
 BN_DECAY = 0.999  # tf.contrib.layers.batch_norm default
 

@@ -137,6 +137,35 @@ int emd_k_train_fused_f32(const emd_k_fused_job_t* jobs, int njobs, const float*
                           long total_steps, float beta1, float beta2, float eps, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Graph S training (misc_py/autoencoder.py:177-274 trains the separable autoencoder of apply_autoencoders.py:91-187).
+ * The reverse pass of the encoder and decoder is the graph-D' entry points (batch-form norms with mask 4, relu); these
+ * are the parts that are S's own.
+ * emd_s_sample_crops_f32: emd_k_sample_crops_f32's input path with graph S's differences: Philox tag 5 (its own stream),
+ *   a crop with any non-finite value after preprocess becomes ONES (autoencoder.py:271-272), and x4 (may be NULL)
+ *   receives a copy of every crop in channel 0 of the [B][crop][crop][4] tensor the first separable block reads (its
+ *   channels 1..3 are not touched: the caller keeps them zero).  crops [B][crop][crop] is the loss target.
+ *   first_index_dev (device uint64, may be NULL) replaces first_index when given: a captured graph's crop index.
+ * emd_s_head_bwd_f32: the loss and the reverse pass of the last two layers, a = relu(conv2d_transpose + bias) [B,H,W,C]
+ *   (pitch lda) and out = conv2d(a, w9 [9][C], 3x3 SAME, no bias) [B,H,W], for L = sum (out - x)^2 / (B*H*W) with target
+ *   x [B,H,W]: dout = 2 (out - x) / (B*H*W) is formed in registers and never written; dw9 [9][C] += dL/dw9;
+ *   da (pitch ldo; may be a itself) = [a > 0] * (3x3 transpose of dout) = dL/d(pre-activation); dbias [C] += sum of da
+ *   (may be NULL); loss_out[0] = L.  C a power of two, 4..256.  workspace: emd_s_head_bwd_workspace_bytes(B, H, W, C)
+ *   bytes (per-tile partial sums, reduced in a fixed order: deterministic).
+ * emd_s_mse_loss_f32: loss_out[0] = sum (out - x)^2 / n; dout (may be NULL) = 2 (out - x) / n.  workspace:
+ *   emd_s_mse_loss_workspace_bytes() bytes.  With emd_conv3x3_cout1_wgrad_f32, emd_conv3x3_cout1_bwd_data_f32,
+ *   emd_relu_mask_bwd_f32 and emd_bn_bwd_reduce_f32 (x NULL, accumulate_s1) it is the composed form of emd_s_head_bwd_f32.
+ * emd_relu_mask_bwd_f32: dr = [a > 0] * g over n floats (n a multiple of 4; dr may be g). */
+int emd_s_sample_crops_f32(const float* stack, int N, int H, int W, float* crops, float* x4, int B, int crop, unsigned long long seed,
+                           unsigned long long first_index, const unsigned long long* first_index_dev, int* draws_out,
+                           emd_stream_t stream);
+size_t emd_s_head_bwd_workspace_bytes(int B, int H, int W, int C);
+int emd_s_head_bwd_f32(const float* out, const float* x, const float* a, int lda, const float* w9, int B, int H, int W, int C, float* da,
+                       int ldo, float* dw9, float* dbias, float* loss_out, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_s_mse_loss_workspace_bytes(void);
+int emd_s_mse_loss_f32(const float* out, const float* x, long n, float* loss_out, float* dout, void* workspace, emd_stream_t stream);
+int emd_relu_mask_bwd_f32(const float* a, const float* g, float* dr, long n, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Graph D: the depthwise-separable encoder-decoder (machine_learning/denoiser.py:58-398).
  *
  * Fused epilogue shared by the matrix-core entry points (per output channel n):
@@ -505,7 +534,8 @@ int emd_conv1x1_s2_bwd_data_f32(const float* dy, int ldd, const uint16_t* whi, c
  *   rstd2 for the double norm: gamma1/beta1 non-NULL), and, if mm2 != NULL, the moving-average updates
  *   (mm1/mv1: BN1's, double norm only; bias: the conv bias that precedes a single BN, may be NULL).
  * emd_bn_bwd_reduce_f32: s1[c] = sum g, s2[c] = sum g*(x-mean)*rstd, g = dy*mask(x*mscale+mshift);
- *   mask 0 none, 1 relu6 (0<z<6), 2 relu6 then clip [0,1] (0<z<=1), 3 leaky_relu 0.2 (graph G).  x == NULL: s1 only.
+ *   mask 0 none, 1 relu6 (0<z<6), 2 relu6 then clip [0,1] (0<z<=1), 3 leaky_relu 0.2 (graph G), 4 relu (z>0, graph S).
+ *   x == NULL: s1 only.
  *   accumulate_s1 != 0: s1 += (bias gradients).  workspace: emd_chan_reduce_workspace_bytes(npix, C) bytes.
  * emd_bn_bwd_prep_f32: (s1, t=s2) -> K, m1, m2 for the apply step; dgamma1, dgamma2, dbeta2 += .
  * emd_bn_bwd_apply_f32: dx = K*(g - m1 - (x-mean)*m2); dx may be dy.  C = 1 is allowed (the final layer). */
