@@ -359,6 +359,17 @@ SIGNATURES = {
     # img scale lq truth counts_out B npix seed first_image workspace stream
     "emd_gen_lq_f32": (C.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, C.c_void_p, C.c_int, C.c_long, C.c_ulonglong,
                                  C.c_ulonglong, C.c_void_p, C.c_void_p]),
+    # ---- whole-micrograph tiling (csrc/tile_ops.hip)
+    "emd_tile_prep_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # x y N H W mode param stats workspace workspace_bytes stream
+    "emd_tile_prep_f32": (C.c_int, [_c_float_p, _c_float_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # src N H W pad cs ys ny xs nx t0 count out crop_stats stream
+    "emd_tile_gather_f32": (C.c_int, [_c_float_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 +
+                            [_c_float_p, _c_float_p, C.c_void_p]),
+    # preds crop_stats N H W pad cs m ys ny xs nx row_range col_range clip out stream
+    "emd_tile_blend_f32": (C.c_int, [_c_float_p, _c_float_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                                               C.c_void_p, C.c_int, _c_float_p, C.c_void_p]),
+    "emd_tile_affine_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

@@ -316,3 +316,11 @@ class Micrograph_Autoencoder(object):
             cnt[y + m:y + cs - m, x + m:x + cs - m] += 1
         core = (slice(overlap, H - overlap), slice(overlap, W - overlap))
         return (acc[core] / cnt[core]).astype(np.float32)
+
+    def denoise_images(self, imgs, preprocess=True, overlap=25, used_overlap=1, max_batch=64):
+        """``denoise`` on the device for one [H,W] image or an [N,H,W] stack (float32 numpy or torch; a CUDA tensor stays on the
+        device): preprocessing, reflect-indexed crops with their rescale, and the blend in csrc/tile_ops.hip, the crops of all
+        images pooled into engine batches of max_batch.  Per image the result is ``denoise``'s with the same arguments."""
+        from . import tiling
+
+        return tiling.denoise_images_s(self.engine, self.device, imgs, preprocess, overlap, used_overlap, max_batch, self.cropsize)

@@ -723,6 +723,14 @@ class Denoiser(object):
         denoised /= contributions
         return denoised.clip(0.0, 1.0) if postprocess else denoised
 
+    def denoise_images(self, imgs, preprocess=True, postprocess=True, overlap=80, max_batch=32):
+        """``denoise`` on the device for one [H,W] image or an [N,H,W] stack (float32 numpy or torch; a CUDA tensor stays on the
+        device): preprocessing, tiling and blending in csrc/tile_ops.hip, the tiles of all images pooled into engine batches of
+        max_batch.  Per image the result is ``denoise``'s with the same arguments, as float32, in the caller's container."""
+        from . import tiling
+
+        return tiling.denoise_images_d(self.engine, self.device, imgs, preprocess, postprocess, overlap, max_batch, cropsize)
+
 
 def architecture(inputs, ground_truth=None, phase=False, params=None, engine=None, trainer=None):
     """Signature of the reference's graph builder (machine_learning/denoiser.py:58-61, misc_py/denoiser-multi-gpu.py:200-203):

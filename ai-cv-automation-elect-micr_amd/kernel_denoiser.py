@@ -191,6 +191,14 @@ class Micrograph_Autoencoder(object):
             den = den * scale + offset if scale else den * offset
         return den
 
+    def denoise_images(self, imgs, preprocess=True, postprocess=True):
+        """``denoise`` on the device for one [H,W] image or an [N,H,W] stack (float32 numpy or torch; a CUDA tensor stays on the
+        device): the padded-image statistics, the rescale and its inverse in csrc/tile_ops.hip around one filter launch over the
+        stack.  Per image the result is ``denoise``'s with the same arguments, as float32, in the caller's container."""
+        from . import tiling
+
+        return tiling.denoise_images_k(self, imgs, preprocess, postprocess)
+
 
 def load_kernel_params(ckpt_loc, depth: int, width: int) -> KernelParams:
     """Load filter scalars saved as ``<ckpt_loc>/kernel_params_depth-{d}_size-{w}.npz`` with the

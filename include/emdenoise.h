@@ -885,6 +885,50 @@ void emd_graph_destroy(emd_graph_t* graph);
 int emd_graph_set_two_streams(emd_graph_t* graph, int on);
 
 /* ------------------------------------------------------------------------------------------------
+ * Whole-micrograph tiling (csrc/tile_ops.hip): the image preparation, crop stacking, per-crop rescale and
+ * overlap-add blending around the networks, so that a whole micrograph is denoised on the device.
+ * replaces: the host numpy of Denoiser.denoise / .preprocess (machine_learning/denoiser.py:632-682), of the graph-S
+ *           Micrograph_Autoencoder.denoise / .preprocess (misc_py/apply_autoencoders.py:346-534) and of the graph-K
+ *           Micrograph_Autoencoder.denoise (misc_py/apply_kernels+MLPs.py:611-703).
+ *
+ * Images are [N,H,W] float32.  A tile plan is the caller's (emdenoise.tiling computes it), in DEVICE int32 arrays:
+ *   ys[ny], xs[nx]      tile start rows / columns in the coordinates of the image reflect-padded by `pad`;
+ *                       tile t = (n, i, j) = n*ny*nx + i*nx + j starts at (ys[i], xs[j]) of image n
+ *   row_range[2*H]      for each row y of the (un-padded) image, the tiles [first, last) of ys whose kept rows
+ *                       [ys[i] + m, ys[i] + cs - m) contain y + pad; col_range[2*W] the same for columns
+ * Rows and columns outside the image are read with numpy's mode="reflect" indexing (any distance), so no padded copy
+ * exists and no plan content can make a kernel read outside the image.  Nothing uses atomics; every result is deterministic. */
+#define EMD_TILE_PREP_S 0 /* autoencoder preprocess (:346-358): NaN/Inf -> 0, scale0to1, divide by the image mean */
+#define EMD_TILE_PREP_K 1 /* graph K (:638-660): NaN/Inf -> 0, statistics of the image reflect-padded by param, (x - off) / scale */
+#define EMD_TILE_PREP_D 2 /* Denoiser.preprocess (:632-643): cv2-style half-pixel bilinear resize to param x param (edge
+                           * clamp), scale0to1, NaN/Inf -> 0.5, scale0to1, with numpy's NaN semantics (a NaN anywhere after
+                           * the resize makes the whole image 0.5) */
+/* Bytes of scratch emd_tile_prep_f32 needs (same arguments). */
+size_t emd_tile_prep_workspace_bytes(int N, int H, int W, int mode, int param);
+/* Per-image preparation, x [N,H,W] -> y: [N,H,W] for S and K (y may alias x), [N,param,param] for D (y != x).  Means
+ * accumulate in double and round to float32 once.  K: param = pad (0 <= pad < min(H,W)); stats (double [N][3], required)
+ * receives (off, scale, flat) per image for emd_tile_affine_f32: off = min, scale = float32(mean of the padded image) - off
+ * in double (0 for a flat image, which becomes 1.0).  stats is ignored by S and D. */
+int emd_tile_prep_f32(const float* x, float* y, int N, int H, int W, int mode, int param, double* stats, void* workspace,
+                      size_t workspace_bytes, emd_stream_t stream);
+/* Crop stack: out[c] (c < count, [count][cs][cs]) = tile t0 + c of the plan, src[n, ys[i] - pad + a, xs[j] - pad + b].
+ * crop_stats == NULL: a verbatim copy (numpy slicing of the padded image; graph D).  Otherwise (graph S, :304-308) each
+ * crop is rescaled: off = min, scale = float32(mean) - off, out = (x - off) / scale, or 1.0 for a flat crop (scale == 0);
+ * crop_stats[c] = (off, scale) (float [count][2]).  Needs cs <= H + 2*pad and cs <= W + 2*pad, t0 + count <= N*ny*nx. */
+int emd_tile_gather_f32(const float* src, int N, int H, int W, int pad, int cs, const int* ys, int ny, const int* xs, int nx,
+                        int t0, int count, float* out, float* crop_stats, emd_stream_t stream);
+/* Overlap-add of all N*ny*nx tile predictions preds [N*ny*nx][cs][cs] into out [N,H,W] (the un-padded core): each output
+ * pixel sums, in ascending tile order and in double, the tiles whose kept window (margin m, 0 <= m < cs/2) covers it,
+ * divides by their count, optionally clips to [0,1] (clip = 1) and rounds once.  crop_stats != NULL (graph S) first maps each
+ * prediction back with the crop's (off, scale) from emd_tile_gather_f32: pred * scale + off in float32. */
+int emd_tile_blend_f32(const float* preds, const float* crop_stats, int N, int H, int W, int pad, int cs, int m, const int* ys,
+                       int ny, const int* xs, int nx, const int* row_range, const int* col_range, int clip, float* out,
+                       emd_stream_t stream);
+/* Graph K's inverse rescale (:700-701): y = x * scale + off, or x * off for a flat image (scale == 0), per image, with the
+ * (off, scale, flat) of emd_tile_prep_f32(EMD_TILE_PREP_K), in double, rounded once; y may alias x. */
+int emd_tile_affine_f32(const float* x, float* y, int N, long npix, const double* stats, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
