@@ -9,7 +9,8 @@ from .kernel_denoiser import KernelParams, Micrograph_Autoencoder, kernel_denois
 from . import autoencoder, autoencoder_trainer, denoiser, gan, graphed, input_pipeline, k_trainer, kernel_denoiser, ops, streams, tf_checkpoint, tiling, train_ops, trainer, xception  # noqa: F401
 from .denoiser import Denoiser, DenoiserEngine, architecture, synthetic_weights  # noqa: F401
 from .trainer import DenoiserTrainer, get_model_fn  # noqa: F401
-from .k_trainer import KernelDenoiserTrainer, k_record_parser, s_record_parser  # noqa: F401
+from .k_trainer import KernelDenoiserTrainer, PAIR_PRESET, distill, k_record_parser, make_pairs, s_record_parser  # noqa: F401
 from .autoencoder_trainer import AutoencoderTrainer  # noqa: F401
 
-__all__ = ["KernelParams", "Micrograph_Autoencoder", "kernel_denoise", "KernelDenoiserTrainer", "AutoencoderTrainer"]
+__all__ = ["KernelParams", "Micrograph_Autoencoder", "kernel_denoise", "KernelDenoiserTrainer", "AutoencoderTrainer", "make_pairs", "distill",
+           "PAIR_PRESET"]

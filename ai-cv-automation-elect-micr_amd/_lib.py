@@ -49,6 +49,15 @@ SIGNATURES = {
     "emd_k_train_fused_f32": (C.c_int, [C.c_void_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int, _c_float_p, C.c_int, C.c_int,
                                         C.c_int, C.c_ulonglong, C.c_int, C.c_int, C.c_double, C.c_long, C.c_float, C.c_float,
                                         C.c_float, C.c_void_p]),
+    # x truth B H W width depth pad_mode theta m v step lr0 total_steps beta1 beta2 eps flags grad loss params workspace ws_bytes stream
+    "emd_k_train_pair_step_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_float_p,
+                                            _c_float_p, _c_float_p, C.c_void_p, C.c_double, C.c_long, C.c_float, C.c_float, C.c_float,
+                                            C.c_uint, _c_float_p, _c_float_p, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # a b N H W patch lo hi seed first_index x t draws stream
+    "emd_k_make_pairs_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
+                                       C.c_ulonglong, _c_float_p, _c_float_p, C.c_void_p, C.c_void_p]),
+    # pred crop_stats N npix out stream
+    "emd_s_crop_unscale_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, _c_float_p, C.c_void_p]),
     # stack N H W crops x4 B crop seed first_index first_index_dev draws stream
     "emd_s_sample_crops_f32": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, _c_float_p, _c_float_p, C.c_int, C.c_int, C.c_ulonglong,
                                          C.c_ulonglong, C.c_void_p, C.c_void_p, C.c_void_p]),

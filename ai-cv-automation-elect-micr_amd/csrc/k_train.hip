@@ -22,41 +22,10 @@
 #include <cmath>
 
 #include "emd_common.hpp"
+#include "k_common.hpp"
 #include "philox.hpp"
 
 namespace {
-
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr int kThreads = 256, kWaves = kThreads / 64, kPx = 4, kChunk = kThreads * kPx;
-constexpr int kMaxNsym = (EMD_K_MAX_WIDTH / 2 + 1) * (EMD_K_MAX_WIDTH / 2 + 2) / 2;
-constexpr int kMaxScal = (2 * EMD_K_MAX_DEPTH - 1) * kMaxNsym + EMD_K_MAX_DEPTH - 1;
-constexpr int kMaxGrid = 1024;          // workgroups of k_grad_kernel (partial slabs)
-constexpr int kUpdThreads = 1024;
-
-int nsym_of(int width) { return (width / 2 + 1) * (width / 2 + 2) / 2; }
-int nscal_of(int width, int depth) { return (2 * depth - 1) * nsym_of(width) + depth - 1; }
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-
-__device__ __forceinline__ float sigm(float z) {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-kLog2e * z));
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// class of tap (i, j) of a width-w map: the creation index of (max(|i-o|,|j-o|), min(..)) in make_layer's order
-__device__ __forceinline__ int tap_class(int i, int j, int o) {
-    const int a = abs(i - o), b = abs(j - o);
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    return hi * (hi + 1) / 2 + lo;
-}
 
 template <int D>
 __global__ __launch_bounds__(kThreads) void k_grad_kernel(const float* __restrict__ x, int B, int H, int W, int width,
@@ -190,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void k_grad_kernel(const float* __restric
         partial[(long)blockIdx.x * (nscal + 1) + i] = (acc[0][i] + acc[1][i]) + (acc[2][i] + acc[3][i]);
 }
 
-// One workgroup of kUpdThreads.  R threads per scalar share the partial slabs (strided), then a fixed-order tree in LDS.
+// One workgroup of kUpdThreads: k_update_body (k_common.hpp) without the paired trainer's sqrt rule.
 __global__ __launch_bounds__(kUpdThreads) void k_update_kernel(const float* __restrict__ partial, int nwg, int R, int width,
                                                                int depth, long npix, float* __restrict__ theta,
                                                                float* __restrict__ adam_m, float* __restrict__ adam_v,
@@ -198,103 +167,11 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_kernel(const float* __re
                                                                float beta1, float beta2, float eps, int update,
                                                                float* __restrict__ grad_out, float* __restrict__ loss_out,
                                                                float* __restrict__ params_out) {
-    __shared__ double red[kUpdThreads];
-    __shared__ double sums[kMaxScal + 1];
-    __shared__ float th[kMaxScal];
-    const int tid = threadIdx.x;
-    const int o = width >> 1, nsym = (o + 1) * (o + 2) / 2, ww = width * width;
-    const int nscal = (2 * depth - 1) * nsym + depth - 1, n1 = nscal + 1;
-    const int t = update ? step[0] + 1 : 0;   // 1-based step of this update
-    const int per = kUpdThreads / R, part = tid % R;
-    for (int base = 0; base < n1; base += per) {
-        const int i = base + tid / R;
-        double s = 0.0;
-        if (i < n1)
-            for (int w = part; w < nwg; w += R) s += (double)partial[(long)w * n1 + i];
-        red[tid] = s;
-        __syncthreads();
-        for (int h = R >> 1; h; h >>= 1) {
-            if (part < h) red[tid] += red[tid + h];
-            __syncthreads();
-        }
-        if (part == 0 && i < n1) sums[i] = red[tid];
-        __syncthreads();
-    }
-    // TF AdamOptimizer: lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), lr the float32 placeholder value (:665-669)
-    float lr_t = 0.f;
-    if (update) {
-        const float lr = (float)(lr0 * (1.0 - (double)t / (double)(total_steps + 1)));
-        lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)t)) / (1.0 - pow((double)beta1, (double)t)));
-    }
-    for (int i = tid; i < n1; i += kUpdThreads) {
-        if (i == nscal) {
-            if (loss_out) loss_out[0] = (float)(sums[i] / (double)npix);
-            continue;
-        }
-        const float g = (float)(sums[i] * 2.0 / (double)npix);
-        if (grad_out) grad_out[i] = g;
-        float p = theta[i];
-        if (update) {   // adam_kernel's arithmetic (gan_train.hip)
-            const float mi = beta1 * adam_m[i] + (1.f - beta1) * g;
-            const float vi = beta2 * adam_v[i] + (1.f - beta2) * g * g;
-            adam_m[i] = mi;
-            adam_v[i] = vi;
-            p -= lr_t * mi / (sqrtf(vi) + eps);
-            theta[i] = p;
-        }
-        th[i] = p;
-    }
-    __syncthreads();
-    if (params_out) {   // [wmaps D][w*w] | [bmaps D][w*w] (bmaps[0] = 0) | s [D] (s[0] = 1)
-        const int offB = depth * nsym - nsym, offS = (2 * depth - 1) * nsym - 1;
-        const int n = 2 * depth * ww + depth;
-        for (int k = tid; k < n; k += kUpdThreads) {
-            float val;
-            if (k < 2 * depth * ww) {
-                const int l = (k / ww) % depth, tap = k % ww;
-                const int c = tap_class(tap / width, tap % width, o);
-                if (k < depth * ww) val = th[l * nsym + c];
-                else val = l ? th[offB + l * nsym + c] : 0.f;
-            } else {
-                const int l = k - 2 * depth * ww;
-                val = l ? th[offS + l] : 1.f;
-            }
-            params_out[k] = val;
-        }
-    }
-    if (update && tid == 0) step[0] = t;
+    k_update_body<false>(partial, nwg, R, width, depth, npix, theta, adam_m, adam_v, step, lr0, total_steps, beta1, beta2, eps, update,
+                         0, grad_out, loss_out, params_out);
 }
 
 // ---- the input path (:450-538) for one crop per workgroup
-__device__ __forceinline__ float block_reduce_min(float v, float* sh) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fminf(fminf(sh[0], sh[1]), fminf(sh[2], sh[3]));
-}
-__device__ __forceinline__ float block_reduce_max(float v, float* sh) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ double block_reduce_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__device__ __forceinline__ unsigned draw_below(unsigned r, unsigned n) {   // floor(n * r / 2^32): 0 .. n-1
-    return (unsigned)(((unsigned long long)r * n) >> 32);
-}
-
 // S = true: graph S's input path (misc_py/autoencoder.py:190-274): its own Philox tag, a non-finite crop becomes ONES (:271-272),
 // x4 (may be NULL) receives a copy of every crop in channel 0 of a [B][crop][crop][4] tensor (its other channels are not touched), and
 // first_index_dev (may be NULL) holds the first crop index on the device (a replayed graph).

@@ -9,6 +9,11 @@ Here each step is, per filter, one forward + backward launch and one reduce + Ad
 (emd_k_train_step_f32); the crops come from a device-resident image stack through emd_k_sample_crops_f32.  The only host reads
 are the per-step losses, once per chunk of steps.  ``k_record_parser`` restates the host input path in numpy (the check of the
 device sampler).
+
+Paired training (misc_py/noise_removal_kernels_duplicate.py, fed by misc_py/autoencoder_train-val-test.py): ``train_step_pair`` /
+``train_pairs`` train the same filters to turn one patch into another (emd_k_train_pair_step_f32), ``make_pairs`` cuts the patch
+pairs from two aligned stacks (emd_k_make_pairs_f32) and ``distill`` makes them from a trained autoencoder and its input crops.
+``PAIR_PRESET`` holds the reference's settings for that trainer.
 """
 from __future__ import annotations
 
@@ -25,12 +30,22 @@ EMD_K_LOSS_REFERENCE = 0
 EMD_K_LOSS_IMAGE = 1
 EMD_K_TRAIN_UPDATE = 1
 EMD_K_TRAIN_LOSS_ONLY = 2
+EMD_K_TRAIN_SQRT_ABOVE_1 = 4
+EMD_K_PAD_REFLECT = 0
+EMD_K_PAD_VALID = 1
+PADS = {"reflect": EMD_K_PAD_REFLECT, "valid": EMD_K_PAD_VALID}
 FUSED_MAX_STEPS = 1000      # EMD_K_FUSED_MAX_STEPS: steps per fused launch
 FUSED_MAX_PIXELS = 8192     # EMD_K_FUSED_MAX_PIXELS: batch_size * crop^2 held in LDS by the fused launch
 LOSSES = {"reference": EMD_K_LOSS_REFERENCE, "image": EMD_K_LOSS_IMAGE}
 MAX_WIDTH, MAX_DEPTH = 15, 5
 VAL_SKIP_N = 10          # noise-removal-kernels.py:89
 VAL_SEED_XOR = 0x76616C  # the validation crops' Philox key: the seed with this mixed in ("val")
+# The paired trainer's settings (noise_removal_kernels_duplicate.py): lr = 0.01 (1 - t / 10001) over 10 000 steps (:720-724), Adam
+# at beta1 = 0.5 (:449), depth-1 filters of width 3, 5 and 7 (:87-88).  KernelDenoiserTrainer(**PAIR_PRESET) is that trainer; its
+# patches are PAIR_PATCH = 20 pixels (:74), one pair per step (:54).
+PAIR_PRESET = {"configs": ((1, 3), (1, 5), (1, 7)), "lr0": 0.01, "total_steps": 10000, "beta1": 0.5}
+PAIR_PATCH = 20
+PAIR_TEACHER_CROP = 160  # autoencoder_train-val-test.py:36
 
 
 # ---- the host input path (noise-removal-kernels.py:450-538) -----------------------------------------------------------
@@ -249,6 +264,101 @@ def sample_crops(stack_dev, B: int, crop: int, seed: int, first_index: int, out=
     return out
 
 
+def check_pair_window(S: int, patch: int, lo: int, hi):
+    """The offset window [lo, hi) of make_pairs on images of side S; hi = None is the reference's S - 2 * patch
+    (randint(20, 160 - 20 - 20), autoencoder_train-val-test.py:51-52).  Returns hi."""
+    if hi is None:
+        hi = S - 2 * patch
+    if patch < 1 or lo < 0:
+        raise ValueError(f"bad patch / lo ({patch}, {lo})")
+    if hi <= lo:
+        raise ValueError(f"the offset window [{lo}, {hi}) is empty")
+    if hi - 1 + patch > S:
+        raise ValueError(f"a {patch}-px patch at offset {hi - 1} does not fit a {S}-px image")
+    return int(hi)
+
+
+def make_pairs(a, b, patch: int = PAIR_PATCH, lo: int = 20, hi=None, seed: int = 0, first_index: int = 0, return_draws: bool = False,
+               device=None, stream=None):
+    """emd_k_make_pairs_f32: autoencoder_train-val-test.py:35-55 for two aligned stacks a, b [N,H,W] (host or device): each image
+    rescaled by (img - min) / (mean - min), one patch x patch window per pair at offsets (i, j) uniform in [lo, hi) (Philox, keyed
+    by ``seed``, pair n at counter first_index + n), both patches 0.5 where either holds a non-finite value.
+    Returns (x, t) CUDA float32 [N,patch,patch], and the draws (int32 [N,2]) with ``return_draws``."""
+    import torch
+
+    if device is None:
+        device = a.device if isinstance(a, torch.Tensor) and a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    a, b = _as_batch(a, device), _as_batch(b, device)
+    if a.shape != b.shape:
+        raise ValueError(f"the two stacks differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+    N, H, W = a.shape
+    hi = check_pair_window(min(H, W), patch, lo, hi)
+    x = torch.empty((N, patch, patch), dtype=torch.float32, device=device)
+    t = torch.empty_like(x)
+    draws = torch.empty((N, 2), dtype=torch.int32, device=device) if return_draws else None
+    rc = _lib.load().emd_k_make_pairs_f32(_lib.ptr(a), _lib.ptr(b), N, H, W, patch, lo, hi, C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                          C.c_ulonglong(int(first_index)), _lib.ptr(x), _lib.ptr(t),
+                                          _lib.ptr(draws) if draws is not None else None, _lib.stream_ptr(stream))
+    _lib.check(rc, "emd_k_make_pairs_f32")
+    return (x, t, draws) if return_draws else (x, t)
+
+
+def teacher_crops(teacher, stack, max_batch: int = 64):
+    """The first half of ``distill``: (crops, outputs), both CUDA float32 [N,160,160].  crops = stack[:, :160, :160]; outputs[n] is
+    ``teacher.denoise_crop(crops[n])`` at its default arguments, computed on the device in batches of ``max_batch``: the crop's
+    rescale by (min, mean - min) (emd_tile_gather_f32), preprocess on the result (emd_tile_prep_f32, EMD_TILE_PREP_S, per crop),
+    the engine, and the inverse map with denoise_crop's flat-crop branch (emd_s_crop_unscale_f32)."""
+    import torch
+
+    from . import tiling
+
+    if max_batch < 1:
+        raise ValueError("max_batch must be >= 1")
+    cs = teacher.cropsize
+    src = _as_batch(stack, teacher.device)
+    N, H, W = src.shape
+    if H < cs or W < cs:
+        raise ValueError(f"distill needs images of at least {cs}x{cs}, got {H}x{W}")
+    crops = src[:, :cs, :cs].contiguous()   # img[:160, :160] (autoencoder_train-val-test.py:36)
+    plan = tiling.TilePlan(cs, cs, cs, 0, 0, [0], [0])   # one tile per image: the crop itself
+    keep, dev_plan = plan.device_arrays(src.device)
+    net_in = torch.empty((N, cs, cs), dtype=torch.float32, device=src.device)
+    cstats = torch.empty((N, 2), dtype=torch.float32, device=src.device)
+    for g0 in range(0, N, tiling._MAX_TILES_PER_LAUNCH):
+        n = min(tiling._MAX_TILES_PER_LAUNCH, N - g0)
+        tiling.gather(crops, plan, dev_plan, g0, n, net_in[g0:g0 + n], cstats[g0:g0 + n])
+    net_in, _ = tiling.prepare(net_in, tiling.PREP_S)
+    preds = torch.empty((N, cs, cs), dtype=torch.float32, device=src.device)
+    for t0 in range(0, N, max_batch):
+        n = min(max_batch, N - t0)
+        preds[t0:t0 + n] = teacher.engine.forward(net_in[t0:t0 + n, :, :, None])[..., 0]
+    rc = _lib.load().emd_s_crop_unscale_f32(_lib.ptr(preds), _lib.ptr(cstats), N, cs * cs, _lib.ptr(preds), _lib.stream_ptr())
+    _lib.check(rc, "emd_s_crop_unscale_f32")
+    del keep
+    return crops, preds
+
+
+def distill(teacher, stack, patch: int = PAIR_PATCH, lo: int = 20, hi=None, seed: int = 0, first_index: int = 0,
+            max_batch: int = 64, return_draws: bool = False):
+    """autoencoder_train-val-test.py as one device pass: the training pairs of the paired K trainer from a trained autoencoder.
+    ``teacher`` is an autoencoder.Micrograph_Autoencoder, ``stack`` [N,H,W(,1)] with H, W >= 160 (host or device).  Every image's
+    160 x 160 corner goes through the teacher (teacher_crops), then make_pairs cuts one patch pair per image.  Returns make_pairs'
+    result: (x, t) with x the input's patch and t the teacher's.  Nothing returns to the host in between.  Unlike the script, the
+    whole stack is processed (it stops after 6076 pairs) and errors are raised (it swallows them)."""
+    cs = teacher.cropsize
+    check_pair_window(cs, patch, lo, hi)
+    crops, preds = teacher_crops(teacher, stack, max_batch)
+    return make_pairs(crops, preds, patch, lo, hi, seed, first_index, return_draws, device=teacher.device)
+
+
+def pair_order(n_pairs: int, start: int, steps: int, batch_size: int = 1):
+    """The pair indices train_pairs feeds: step k (0-based, counted from ``start`` completed steps) takes pairs
+    ((start + k) * batch_size + b) % n_pairs, b = 0..batch_size-1 -- the stacks in stored order, wrapping round
+    (Dataset.zip(...).repeat().batch(), noise_removal_kernels_duplicate.py:561-590)."""
+    k = (start + np.arange(steps, dtype=np.int64))[:, None] * batch_size + np.arange(batch_size, dtype=np.int64)[None]
+    return k % n_pairs
+
+
 class _Filter:
     """Device state of one (depth, width) filter: theta, Adam's m and v, the step counter and the packed inference block."""
 
@@ -373,6 +483,142 @@ class KernelDenoiserTrainer:
         g = torch.empty(f.n, dtype=torch.float32, device=self.device)
         self._launch(f, x, 0, self._elem_ptr(self._loss_buf, 0), grad_out=g)
         return float(self._loss_buf[0].item()), g.cpu().numpy()
+
+    # ---- paired training (noise_removal_kernels_duplicate.py)
+    def _launch_pair(self, f: _Filter, x, truth, pad_mode, flags, loss_out, grad_out=None):
+        B, H, W = x.shape
+        ws = self._workspace(f, B, H, W)
+        upd = flags & EMD_K_TRAIN_UPDATE
+        rc = self.lib.emd_k_train_pair_step_f32(
+            _lib.ptr(x), _lib.ptr(truth), B, H, W, f.width, f.depth, pad_mode, _lib.ptr(f.theta), _lib.ptr(f.m), _lib.ptr(f.v),
+            _lib.ptr(f.step), C.c_double(self.lr0), self.total_steps, self.beta1, self.beta2, self.eps, flags,
+            _lib.ptr(grad_out) if grad_out is not None else None, loss_out, _lib.ptr(f.packed) if upd else None,
+            _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr())
+        _lib.check(rc, "emd_k_train_pair_step_f32")
+
+    def _check_pair_shape(self, shape, pad, filters=None):
+        """(pad mode) for [B,H,W] pair batches; every filter trained on them must fit."""
+        if pad not in PADS:
+            raise ValueError(f"pad must be one of {sorted(PADS)}")
+        H, W = int(shape[1]), int(shape[2])
+        for f in (self.filters if filters is None else filters):
+            if pad == "valid" and f.width > min(H, W):
+                raise ValueError(f'pad="valid" needs width <= min(H, W): width {f.width}, batch {H}x{W}')
+            if pad == "reflect" and f.width // 2 >= min(H, W):
+                raise ValueError(f'pad="reflect" needs width/2 < min(H, W): width {f.width}, batch {H}x{W}')
+        return PADS[pad]
+
+    def _as_pair(self, x, truth, pad, filters=None):
+        x, truth = _as_batch(x, self.device), _as_batch(truth, self.device)
+        if x.shape != truth.shape:
+            raise ValueError(f"x and truth differ in shape: {tuple(x.shape)} and {tuple(truth.shape)}")
+        return x, truth, self._check_pair_shape(x.shape, pad, filters)
+
+    def train_step_pair(self, x, truth, pad: str = "valid", sqrt_above_1: bool = True):
+        """One Adam step of every filter towards ``truth`` from ``x`` (both host or device [B,H,W(,1)]).  pad "valid": each filter
+        is evaluated on its own (H-w+1) x (W-w+1) interior and compared with the same interior of ``truth``
+        (noise_removal_kernels_duplicate.py:406-432); "reflect": the unpaired trainer's border, H x W outputs.
+        sqrt_above_1: the loss is sqrt(MSE) while the MSE exceeds 1 (:433).  Returns the per-filter losses, computed with the
+        parameters before the update."""
+        x, truth, pm = self._as_pair(x, truth, pad)
+        self._check_steps(1)
+        flags = EMD_K_TRAIN_UPDATE | (EMD_K_TRAIN_SQRT_ABOVE_1 if sqrt_above_1 else 0)
+        for i, f in enumerate(self.filters):
+            self._launch_pair(f, x, truth, pm, flags, self._elem_ptr(self._loss_buf, i))
+        self.step += 1
+        return self._loss_buf.cpu().numpy().copy()
+
+    def evaluate_pair(self, x, truth, pad: str = "valid", sqrt_above_1: bool = True):
+        """Per-filter paired losses on (x, truth) with the current parameters."""
+        x, truth, pm = self._as_pair(x, truth, pad)
+        flags = EMD_K_TRAIN_LOSS_ONLY | (EMD_K_TRAIN_SQRT_ABOVE_1 if sqrt_above_1 else 0)
+        for i, f in enumerate(self.filters):
+            self._launch_pair(f, x, truth, pm, flags, self._elem_ptr(self._loss_buf, i))
+        return self._loss_buf.cpu().numpy().copy()
+
+    def loss_and_grad_pair(self, x, truth, config=None, pad: str = "valid", sqrt_above_1: bool = True):
+        """(loss, dL/dtheta) of one filter on the pair batch without updating it (theta's layout: emd_k_train_step_f32)."""
+        import torch
+
+        f = self._filter(config)
+        x, truth, pm = self._as_pair(x, truth, pad, [f])
+        g = torch.empty(f.n, dtype=torch.float32, device=self.device)
+        self._launch_pair(f, x, truth, pm, EMD_K_TRAIN_SQRT_ABOVE_1 if sqrt_above_1 else 0, self._elem_ptr(self._loss_buf, 0),
+                          grad_out=g)
+        return float(self._loss_buf[0].item()), g.cpu().numpy()
+
+    def _pair_step(self, x, truth, pad_mode, flags, buf, k):
+        """One paired step of every filter on device batches; the losses go to row k of buf.  (train_pairs' only device work.)"""
+        nf = len(self.filters)
+        for i, f in enumerate(self.filters):
+            self._launch_pair(f, x, truth, pad_mode, flags, self._elem_ptr(buf, k * nf + i))
+
+    def train_pairs(self, x_stack, t_stack, steps: int, batch_size: int = 1, shuffle: bool = False, pad: str = "valid",
+                    sqrt_above_1: bool = True, val_x=None, val_t=None, val_skip_n: int = VAL_SKIP_N, chunk: int = 1000,
+                    save_every: int = 0, directory=None):
+        """``steps`` paired steps over two aligned stacks [N,p,p(,1)] (host or device), x_stack the inputs and t_stack the targets,
+        as make_pairs / distill return them.  The pairs are used as stored, in order, wrapping round (pair_order; the reference
+        zips two sorted file lists, repeats, and takes one pair per step, noise_removal_kernels_duplicate.py:54, :561-590; its
+        flip_rotate is pinned to the identity, :460, and its random crop is commented out, :485-488, so there is no augmentation).
+        shuffle: one permutation of the pairs, drawn from a generator seeded by the trainer's seed, replaces the stored order.
+        val_x / val_t: an optional validation pair stack, evaluated whole after every ``val_skip_n``-th step (the reference has
+        its validation commented out).  save_every > 0 writes a checkpoint to ``directory`` whenever the step count reaches a
+        multiple of it (the reference: every 5000 steps, :784-785).  The device is read once per ``chunk`` steps.
+        Returns {"loss": [steps, configs], "val_step": [k], "val_loss": [k, configs]}."""
+        import torch
+
+        if steps < 0 or batch_size < 1 or chunk < 1:
+            raise ValueError("bad steps / batch_size / chunk")
+        if val_skip_n < 1:
+            raise ValueError("val_skip_n must be >= 1")
+        if save_every < 0 or (save_every and directory is None):
+            raise ValueError("save_every needs a directory")
+        if (val_x is None) != (val_t is None):
+            raise ValueError("val_x and val_t come together")
+        n_x, n_t = len(x_stack), len(t_stack)
+        if n_x != n_t:
+            raise ValueError(f"the stacks hold {n_x} and {n_t} pairs")
+        if n_x < 1:
+            raise ValueError("no pairs")
+        self._check_steps(steps)
+        xs, ts, pm = self._as_pair(x_stack, t_stack, pad)
+        val = self._as_pair(val_x, val_t, pad)[:2] if val_x is not None else None
+        nf = len(self.filters)
+        flags = EMD_K_TRAIN_UPDATE | (EMD_K_TRAIN_SQRT_ABOVE_1 if sqrt_above_1 else 0)
+        vflags = EMD_K_TRAIN_LOSS_ONLY | (EMD_K_TRAIN_SQRT_ABOVE_1 if sqrt_above_1 else 0)
+        if shuffle:
+            perm = torch.from_numpy(np.random.default_rng(self.seed).permutation(n_x)).to(self.device)
+            xs, ts = xs[perm].contiguous(), ts[perm].contiguous()
+        losses, val_steps, val_losses = [], [], []
+        done = 0
+        while done < steps:
+            n = min(chunk, steps - done)
+            order = pair_order(n_x, self.step, n, batch_size)
+            buf = torch.empty((n, nf), dtype=torch.float32, device=self.device)
+            vbuf = torch.empty((n // val_skip_n + 1, nf), dtype=torch.float32, device=self.device)
+            nval = 0
+            for k in range(n):
+                first = int(order[k, 0])
+                if first + batch_size <= n_x:   # a contiguous run of the stacks: no copy
+                    xb, tb = xs[first:first + batch_size], ts[first:first + batch_size]
+                else:                           # the batch wraps round the end
+                    idx = torch.from_numpy(order[k]).to(self.device)
+                    xb, tb = xs[idx].contiguous(), ts[idx].contiguous()
+                self._pair_step(xb, tb, pm, flags, buf, k)
+                self.step += 1
+                if val is not None and self.step % val_skip_n == 0:
+                    self._pair_step(val[0], val[1], pm, vflags, vbuf, nval)
+                    val_steps.append(self.step)
+                    nval += 1
+                if save_every and self.step % save_every == 0:
+                    self.save_checkpoint(directory)
+            losses.append(buf.cpu().numpy())
+            if nval:
+                val_losses.append(vbuf[:nval].cpu().numpy())
+            done += n
+        return {"loss": np.concatenate(losses) if losses else np.zeros((0, nf), np.float32),
+                "val_step": np.asarray(val_steps, np.int64),
+                "val_loss": np.concatenate(val_losses) if val_losses else np.zeros((0, nf), np.float32)}
 
     def _check_steps(self, steps):
         if self.step + steps > self.total_steps:

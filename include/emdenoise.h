@@ -136,6 +136,48 @@ int emd_k_train_fused_f32(const emd_k_fused_job_t* jobs, int njobs, const float*
                           int nbatches, int B, int crop, unsigned long long seed, int nsteps, int loss_mode, double lr0,
                           long total_steps, float beta1, float beta2, float eps, emd_stream_t stream);
 
+/* Paired training (csrc/k_pair.hip): the filter is trained to turn x into a second tensor, `truth`.
+ * replaces: misc_py/noise_removal_kernels_duplicate.py:406-434 (the filter over the unpadded patch, the interior target, the MSE
+ *           and its sqrt rule), :449 and :720-724 (Adam at beta1 = 0.5, lr = 0.01 (1 - t / 10001)) -- the caller passes those.
+ *
+ * emd_k_train_pair_step_f32: emd_k_train_step_f32 with two device batches x and truth, both [B,H,W].  theta, the Adam
+ *   arguments, grad_out / loss_out / params_out and the workspace (emd_k_train_workspace_bytes(B, H, W, width, depth) bytes) are
+ *   as there.  What differs:
+ *   pad_mode  EMD_K_PAD_VALID: no padding (pad(inputs, (0, 0)), :406).  The filter is evaluated on the (H-w+1) x (W-w+1)
+ *             interior only, no mirrored tap is read, and output pixel (r, c) is compared with truth[r + w/2][c + w/2]
+ *             (:431-432).  Needs width <= min(H,W).  EMD_K_PAD_REFLECT: emd_k_train_step_f32's border rule, output H x W,
+ *             compared with truth[r][c]; needs width/2 < min(H,W).
+ *   target    F(x) against truth in image orientation.  The reference assembles its output transposed (:425-428) and is fed
+ *             the truth transposed (:735-736); the two cancel, so there is no "reference" / "image" choice here.
+ *   loss      L = mean((F(x) - truth)^2) over the compared pixels.  With EMD_K_TRAIN_SQRT_ABOVE_1 the loss is sqrt(L) when
+ *             L > 1 (:433; at exactly L == 1 the plain branch holds) and the gradient is then dL/dtheta / (2 sqrt(L)); the
+ *             factor is applied in the fixed-order reduction.  loss_out holds the value after this rule.
+ *   flags     EMD_K_TRAIN_UPDATE, EMD_K_TRAIN_LOSS_ONLY or neither, as emd_k_train_step_f32; EMD_K_TRAIN_SQRT_ABOVE_1 with any.
+ * Deterministic: no atomics; the same inputs give the same bits.
+ *
+ * emd_k_make_pairs_f32: misc_py/autoencoder_train-val-test.py:35-55 for a stack, one workgroup per image.  a (the autoencoder's
+ *   input crops) and b (its outputs) are device [N,H,W].  Per image, separately for a[n] and b[n]: c = min (NaN if any pixel
+ *   is, as np.min), m = float32(mean, accumulated in double) - c, img = (img - c) / m in float32 (:38-44).  One offset pair
+ *   (i, j) per image, the same for both, each uniform in [lo, hi) (np.random.randint(lo, hi), :51-52; the reference's 20 and
+ *   160 - 40): Philox4x32-10(counter = (first_index + n, 0, tag 6), key = seed), i from word 0 and j from word 1.
+ *   x, t [N,patch,patch] receive a's and b's patch at (i, j); draws_out (int32 [N][2] = i, j; may be NULL) the draws.  If
+ *   either patch holds a non-finite value (a flat image has m == 0) both become 0.5, the rule of the paired trainer's
+ *   record_parser (noise_removal_kernels_duplicate.py:534-548).  Needs 0 <= lo < hi and hi - 1 + patch <= min(H,W). */
+#define EMD_K_PAD_REFLECT 0
+#define EMD_K_PAD_VALID 1
+#define EMD_K_TRAIN_SQRT_ABOVE_1 4u
+int emd_k_train_pair_step_f32(const float* x, const float* truth, int B, int H, int W, int width, int depth, int pad_mode,
+                              float* theta, float* adam_m, float* adam_v, int* step, double lr0, long total_steps, float beta1,
+                              float beta2, float eps, unsigned flags, float* grad_out, float* loss_out, float* params_out,
+                              void* workspace, size_t workspace_bytes, emd_stream_t stream);
+int emd_k_make_pairs_f32(const float* a, const float* b, int N, int H, int W, int patch, int lo, int hi, unsigned long long seed,
+                         unsigned long long first_index, float* x, float* t, int* draws_out, emd_stream_t stream);
+/* The inverse map of autoencoder.Micrograph_Autoencoder.denoise_crop (apply_autoencoders.py:376-381), one workgroup per crop:
+ * pred, out [N][npix] (out may alias pred), crop_stats [N][2] = (offset, scale) as emd_tile_gather_f32 writes them.
+ * out = scale * pred + offset in float32 (multiply, then add), or pred * offset / mean(pred) where scale == 0 (a flat crop; the
+ * mean accumulated in double and rounded once). */
+int emd_s_crop_unscale_f32(const float* pred, const float* crop_stats, int N, int npix, float* out, emd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Graph S training (misc_py/autoencoder.py:177-274 trains the separable autoencoder of apply_autoencoders.py:91-187).
  * The reverse pass of the encoder and decoder is the graph-D' entry points (batch-form norms with mask 4, relu); these
