@@ -379,6 +379,24 @@ SIGNATURES = {
     "emd_tile_blend_f32": (C.c_int, [_c_float_p, _c_float_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                                                C.c_void_p, C.c_int, _c_float_p, C.c_void_p]),
     "emd_tile_affine_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]),
+    # ---- image-quality metrics (csrc/ssim.hip)
+    "emd_ssim_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # x y B H W taps_host size means ssim_map cs_map workspace ws_bytes stream
+    "emd_ssim_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _c_float_p, _c_float_p,
+                               _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_ssim_loss_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # x y B H W taps_host size per_image scale scale_dev dout result loss_acc acc_stride acc_weight workspace ws_bytes stream
+    "emd_ssim_loss_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                    _c_float_p, _c_float_p, _c_float_p, _c_float_p, C.c_int, C.c_float, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "emd_avgpool2x2_same_c1_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "emd_ms_ssim_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # x y B H W level taps_host size value level_means workspace ws_bytes stream
+    "emd_ms_ssim_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, _c_float_p,
+                                  _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_psnr_workspace_bytes": (C.c_size_t, [C.c_int, C.c_long]),
+    # x y B npix data_range out workspace ws_bytes stream
+    "emd_psnr_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_float, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

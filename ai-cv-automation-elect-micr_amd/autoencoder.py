@@ -258,6 +258,16 @@ class Micrograph_Autoencoder(object):
         x = torch.from_numpy(np.ascontiguousarray(crops, dtype=np.float32)[..., None]).to(self.device)
         return self.engine.forward(x)[..., 0].cpu().numpy()
 
+    def score(self, lq, truth):
+        """{"mse", "psnr", "ssim"} of the network's output for the crops ``lq`` [B,160,160,1] (as given: no rescaling) against
+        ``truth``, computed on the device (emdenoise.metrics)."""
+        import torch
+
+        from . import metrics
+
+        x = lq if isinstance(lq, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(lq, dtype=np.float32))
+        return metrics.score(self.engine.forward(x.to(self.device, dtype=torch.float32).contiguous()), truth)
+
     # ---- :360-383
     def denoise_crop(self, crop, preprocess=True, scaling=True, postprocess=True):
         crop = np.array(crop, dtype=np.float32, copy=True)

@@ -695,6 +695,12 @@ class Denoiser(object):
             return y.cpu().numpy()
         return y if on_dev else y.cpu()
 
+    def score(self, lq, truth):
+        """{"mse", "psnr", "ssim"} of ``denoise_batch(lq)`` against ``truth``, computed on the device (emdenoise.metrics)."""
+        from . import metrics
+
+        return metrics.score(self.denoise_batch(lq), truth)
+
     # ---- :653-682 (the reference's body is not executable as written: no `self`, float slice indices,
     #      `=` instead of `+=`); this implements its stated intent, with all tiles in one batch
     def denoise(self, img, preprocess=True, postprocess=True, overlap=80, max_batch=32):

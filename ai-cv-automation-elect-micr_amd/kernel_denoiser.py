@@ -164,6 +164,12 @@ class Micrograph_Autoencoder(object):
             return y.cpu().numpy()
         return y if dev_in else y.cpu()
 
+    def score(self, lq, truth):
+        """{"mse", "psnr", "ssim"} of ``denoise_batch(lq)`` against ``truth``, computed on the device (emdenoise.metrics)."""
+        from . import metrics
+
+        return metrics.score(self.denoise_batch(lq), truth)
+
     # ---- apply_kernels+MLPs.py:638-703
     def denoise(self, img, preprocess=True, postprocess=True, used_overlap=1):
         """Whole-image filtering.  The reference reflect-pads by w//2, rescales by the PADDED image's

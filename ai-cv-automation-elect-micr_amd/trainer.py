@@ -56,13 +56,16 @@ def sync_gradients(grads, moving, group=None):
 class DenoiserTrainer:
     """Parameters, gradients and momentum of graph D' resident on one GPU + the forward/backward launch sequence."""
 
-    def __init__(self, weights, device, precision="bf16x3", learning_rate=INITIAL_LEARNING_RATE, momentum=MOMENTUM):
+    def __init__(self, weights, device, precision="bf16x3", learning_rate=INITIAL_LEARNING_RATE, momentum=MOMENTUM, ssim_weight=0.0):
         import torch
 
         _lib.load()
         self.device = device
         self.precision = {"bf16x3": ops.PREC_BF16X3, "bf16": ops.PREC_BF16}[precision]
         self.lr, self.momentum = learning_rate, momentum
+        # weight of the structural-similarity term of the tower loss, tower_loss += w * (1 - tf_ssim(out, truth)) (:775, which the
+        # reference keeps behind a comment sign); 0 = off: no kernel of csrc/ssim.hip is launched
+        self.ssim_weight = float(ssim_weight)
         self.layers = declare_layers("Dprime")
         specs = variable_specs("Dprime")
         self.trainable = OrderedDict((n, s) for n, s in specs.items() if not _is_moving(n))
@@ -581,7 +584,7 @@ class DenoiserTrainer:
                   lambda dst: ops.conv3x3(dr, pk, self.ones, self.zeros, dst, stride=2, act=False, res=dst, precision=self.precision))
 
     # ---- one tower ---------------------------------------------------------------------------------------------
-    def tower(self, lq, truth, update_moving=True, grad_scale=1.0, per_image=False, wgrad_stream=False):
+    def tower(self, lq, truth, update_moving=True, grad_scale=1.0, per_image=False, wgrad_stream=False, ssim_weight=None):
         """Forward (phase=True) + loss + backward for the images of one tower; parameter gradients are ADDED into
         self.grads.  lq, truth: CUDA float32 [B,S,S,1] contiguous, S a multiple of 32.  Returns (out, result3) with
         result3 a device tensor (mse, loss, dloss/dout factor) -- no host synchronisation.
@@ -591,6 +594,9 @@ class DenoiserTrainer:
         Same arithmetic per image as B separate towers (the moving statistics follow image 0), B times the GEMM M, B times
         fewer launches.  result3 is then [B, 3].
         wgrad_stream=True: the weight-gradient launches of the backward pass go to a side stream (see _wg); same arithmetic.
+        ssim_weight (default: the trainer's): w != 0 adds w * (1 - ssim(out, truth)) to the loss (:775) -- of the batch mean, or of
+        each image's own mean with per_image -- and its gradient to dloss/dout; result3's loss is then the total, the SSIM value
+        itself is self.last["ssim"].
 
         The pass is six segments (_enc_fwd, _mid_fwd, _dec_fwd, _dec_bwd, _mid_bwd, _enc_bwd) so that the
         1/16-resolution part can be driven on its own (round 3 ran it for several groups as ONE pass: slower, removed in round 4); here
@@ -602,7 +608,7 @@ class DenoiserTrainer:
         self._wg_side = self._side_streams(1)[0] if wgrad_stream else None
         st = self._enc_fwd(lq)
         ms = self._mid_fwd(st.cnn3_strided)
-        self._dec_fwd(st, ms.aspp, truth, grad_scale)
+        self._dec_fwd(st, ms.aspp, truth, grad_scale, self.ssim_weight if ssim_weight is None else float(ssim_weight))
         daspp = self._E(ms.aspp.B, ms.aspp.H, ms.aspp.W, ms.aspp.C)
         self._dec_bwd(st, ms.aspp, daspp)
         dx = self._mid_bwd(ms, daspp)
@@ -610,7 +616,7 @@ class DenoiserTrainer:
         if self._wg_side is not None:   # join: the gradient vector is complete, the tensors the side stream read may go
             torch.cuda.current_stream().wait_stream(self._wg_side)
             self._wg_side, self._wg_keep = None, []
-        self.last = {"out": st.out, "result": st.result}
+        self.last = {"out": st.out, "result": st.result, "dout": st.dout, "ssim": st.ssim}
         return st.out, st.result
 
     def forward_train(self, lq, truth=None, update_moving=False, per_image=False):
@@ -696,7 +702,7 @@ class DenoiserTrainer:
         ms.aspp, C["aspp_reduce"] = self._conv_fwd("aspp_reduce", cat)
         return ms
 
-    def _dec_fwd(self, st, aspp, truth, grad_scale=1.0):
+    def _dec_fwd(self, st, aspp, truth, grad_scale=1.0, ssim_weight=0.0):
         """Decoder from the ASPP output (``aspp``: this tower's images) to the output, and the loss."""
         import torch
 
@@ -739,6 +745,14 @@ class DenoiserTrainer:
             result = torch.stack([TO.denoise_loss(out[b:b + 1], truth[b:b + 1], dout[b:b + 1], grad_scale=grad_scale) for b in range(B)])
         else:
             result = TO.denoise_loss(out, truth, dout, grad_scale=grad_scale)
+        st.ssim = None
+        if ssim_weight != 0.0:
+            # tower_loss += w * (1.0 - tf_ssim(out, truth)) (:775) on the clipped output: the loss entry of result becomes the total and
+            # dout += grad_scale * w * dL_ssim/dout, both inside emd_ssim_loss_f32 (no extra pass over dout)
+            from . import metrics
+
+            _, st.ssim = metrics.ssim_loss(out, truth, dout, scale=grad_scale * ssim_weight, per_image=self._per_image,
+                                           loss_acc=result.view(-1)[1:], acc_stride=3, acc_weight=ssim_weight, return_ssim=True)
         st.out, st.result = out, result
 
     def _dec_bwd(self, st, aspp, daspp):
@@ -866,7 +880,7 @@ class DenoiserTrainer:
             return 4
         return 2 if B >= 4 and B % 2 == 0 else 1
 
-    def local_gradients(self, lq, truth, tower_batch=1, streams=1, batched=False):
+    def local_gradients(self, lq, truth, tower_batch=1, streams=1, batched=False, ssim_weight=None):
         """zero_grad + every tower of this rank's images (forward, loss, backward) -> device tensor [n_towers, 3] of
         (mse, loss, factor); the gradient sets are summed into self.grads.  streams > 1: the towers are independent
         (they only meet in the atomically accumulated parameter gradients), so they are issued round-robin on that
@@ -896,14 +910,15 @@ class DenoiserTrainer:
                 for k, s in enumerate(side):
                     with torch.cuda.stream(s):
                         _, r = self.tower(lq[k * per:(k + 1) * per].contiguous(), truth[k * per:(k + 1) * per].contiguous(),
-                                          update_moving=(k == 0), per_image=True)
+                                          update_moving=(k == 0), per_image=True, ssim_weight=ssim_weight)
                         r.record_stream(main)
                     outs.append(r)
                 for s in side:
                     main.wait_stream(s)
                 self._unpad_grads()
                 return torch.cat(outs)
-            _, res = self.tower(lq, truth, update_moving=True, per_image=True, wgrad_stream=os.environ.get("EMD_T_WGRAD_STREAM", "0") == "1")
+            _, res = self.tower(lq, truth, update_moving=True, per_image=True, wgrad_stream=os.environ.get("EMD_T_WGRAD_STREAM", "0") == "1",
+                                ssim_weight=ssim_weight)
             self._unpad_grads()
             return res
         results = []
@@ -915,10 +930,10 @@ class DenoiserTrainer:
             sl = slice(k * tower_batch, (k + 1) * tower_batch)
             if side:
                 with torch.cuda.stream(side[k % len(side)]):
-                    _, res = self.tower(lq[sl].contiguous(), truth[sl].contiguous(), update_moving=(k == 0))
+                    _, res = self.tower(lq[sl].contiguous(), truth[sl].contiguous(), update_moving=(k == 0), ssim_weight=ssim_weight)
                     res.record_stream(main)
             else:
-                _, res = self.tower(lq[sl].contiguous(), truth[sl].contiguous(), update_moving=(k == 0))
+                _, res = self.tower(lq[sl].contiguous(), truth[sl].contiguous(), update_moving=(k == 0), ssim_weight=ssim_weight)
             results.append(res)
         for s in side:
             main.wait_stream(s)
@@ -931,19 +946,19 @@ class DenoiserTrainer:
                          self.momentum, grad_scale=1.0 / n_sets)
         self.repack()
 
-    def _warm(self):
+    def _warm(self, ssim_weight=None):
         """Launch every kernel family once outside of stream capture (code objects load on first use)."""
         import torch
 
         z = torch.zeros((1, 32, 32, 1), dtype=torch.float32, device=self.device)
         keep = self.grads.clone(), {k: t.clone() for k, t in self.pad_g.items()}
-        self.tower(z, z, update_moving=False)
+        self.tower(z, z, update_moving=False, ssim_weight=ssim_weight)
         self.grads.copy_(keep[0])
         for k, t in keep[1].items():
             self.pad_g[k].copy_(t)
         torch.cuda.synchronize()
 
-    def _capture(self, lq, truth, tower_batch, streams, group, batched=False):
+    def _capture(self, lq, truth, tower_batch, streams, group, batched=False, ssim_weight=None):
         """Capture local_gradients for this input shape into a hipGraph.  Returns (graph, static lq, static truth,
         static results), or None if capture failed on ANY rank (all ranks then run eagerly: a rank that skipped the
         graph while the others replay it would still meet them at the all-reduce, but the decision must be common
@@ -953,12 +968,12 @@ class DenoiserTrainer:
 
         entry, err = None, None
         try:
-            self._warm()
+            self._warm(ssim_weight)
             slq, str_ = torch.empty_like(lq), torch.empty_like(truth)
             g = torch.cuda.CUDAGraph()
             # thread_local: other threads (e.g. the RCCL watchdog polling its events) may touch the runtime meanwhile
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                sres = self.local_gradients(slq, str_, tower_batch, streams, batched)
+                sres = self.local_gradients(slq, str_, tower_batch, streams, batched, ssim_weight)
             entry = (g, slq, str_, sres)
         except Exception as e:  # noqa: BLE001 -- fall back to eager launches
             err = e
@@ -973,20 +988,24 @@ class DenoiserTrainer:
             return None
         return entry
 
-    def train_step(self, lq, truth, tower_batch=1, learning_rate=None, group=None, streams=1, graph=False, batched=False):
+    def train_step(self, lq, truth, tower_batch=1, learning_rate=None, group=None, streams=1, graph=False, batched=False,
+                   ssim_weight=None):
         """One optimizer step on this rank's images (misc_py/denoiser-multi-gpu.py:1169-1206): every ``tower_batch``
         images form a tower (gradient set); all sets of all ranks are averaged (:1040) and applied with Nesterov
         momentum (:1064-1066).  Returns the device tensor [n_towers_local, 3] of (mse, loss, factor).
         graph=True: the whole local part (all towers on their streams) is captured once per input shape into a
-        hipGraph and replayed -- ~9000 launches per step become one."""
+        hipGraph and replayed -- ~9000 launches per step become one.
+        ssim_weight (default: the trainer's): the weight of the SSIM term of every tower's loss (see tower); part of the key of a
+        captured graph."""
         import torch
 
         n_local = lq.shape[0] // tower_batch
-        key = (tuple(lq.shape), tower_batch, streams, bool(batched))
+        sw = self.ssim_weight if ssim_weight is None else float(ssim_weight)
+        key = (tuple(lq.shape), tower_batch, streams, bool(batched)) + ((sw,) if sw != 0.0 else ())
         if graph and key not in self._graphs:
-            self._graphs[key] = self._capture(lq, truth, tower_batch, streams, group, batched)
+            self._graphs[key] = self._capture(lq, truth, tower_batch, streams, group, batched, sw)
         if not graph or self._graphs[key] is None:
-            results = self.local_gradients(lq, truth, tower_batch, streams, batched)
+            results = self.local_gradients(lq, truth, tower_batch, streams, batched, sw)
         else:
             g, slq, str_, sres = self._graphs[key]
             slq.copy_(lq)

@@ -971,6 +971,52 @@ int emd_tile_blend_f32(const float* preds, const float* crop_stats, int N, int H
 int emd_tile_affine_f32(const float* x, float* y, int N, long npix, const double* stats, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image-quality metrics (csrc/ssim.hip): SSIM, MS-SSIM, PSNR and the SSIM loss term with its gradient.
+ * replaces: misc_py/denoiser-multi-gpu.py:124-139 (_tf_fspecial_gauss), :142-167 (tf_ssim), :170-192 (tf_ms_ssim) and the
+ *           loss term of _tower_fn, :775 (tower_loss += 1.0 - tf_ssim(out, truth)); the same functions again in
+ *           misc_py/modified_Xception.py:123-191, :649.
+ *
+ * x, y       : [B,H,W] float32 (NHWC with C == 1), contiguous; 0 <= B <= 65535 (B == 0 is a no-op).
+ * taps_host  : HOST array of `size` floats, the 1-D window g (the reference's 2-D window is the outer product g x g:
+ *              exp(-i^2 / (2 sigma^2)), i = -size/2 .. size/2, divided by its sum); size odd, 3..15, H, W >= size.
+ * Maps are VALID correlations, [B, H-size+1, W-size+1]; C1 = 0.01^2, C2 = 0.03^2 (L = 1).
+ * Workspaces are the caller's, 16-byte aligned, sized by the emd_*_workspace_bytes of the same arguments (0 for arguments
+ * the routine would refuse).  Sums over a map are formed per tile in float32, then in double in a fixed order: no atomics,
+ * every result is bitwise reproducible. */
+size_t emd_ssim_workspace_bytes(int B, int H, int W, int size);
+/* means [B+1][2] = (mean ssim_map, mean cs_map) of each image, row B the mean over the whole batch (the mean of the rows;
+ * tf.reduce_mean of :166, :176-177).  ssim_map / cs_map: optional outputs [B, H-size+1, W-size+1] (NULL: no map and no
+ * moment is written to memory). */
+int emd_ssim_f32(const float* x, const float* y, int B, int H, int W, const float* taps_host, int size, float* means,
+                 float* ssim_map, float* cs_map, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_ssim_loss_workspace_bytes(int B, int H, int W, int size);
+/* L = 1 - mean(ssim_map) and its gradient with respect to x (none for y).  result [B+1][2] = (mean ssim, L) per image, row B for
+ * the batch mean.  dout (optional, [B,H,W], may not alias x or y) is ACCUMULATED: per_image != 0: dout[b] += scale *
+ * (scale_dev ? scale_dev[b] : 1) * dL_b/dx[b] with L_b image b's own loss; per_image == 0: the same with L the batch loss
+ * (dL/dx[b] = dL_b/dx[b] / B).  loss_acc (optional): loss_acc[b * acc_stride] += acc_weight * L_b (per_image), or
+ * loss_acc[0] += acc_weight * L.  scale_dev: optional DEVICE array of B floats.  The taps must be symmetric (the gradient
+ * is the full correlation with the same window, gathered per input pixel). */
+int emd_ssim_loss_f32(const float* x, const float* y, int B, int H, int W, const float* taps_host, int size, int per_image,
+                      float scale, const float* scale_dev, float* dout, float* result, float* loss_acc, int acc_stride,
+                      float acc_weight, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+/* tf.nn.avg_pool(x, [1,2,2,1], [1,2,2,1], 'SAME') on one channel (:178-179): x [B,H,W] -> y [B,(H+1)/2,(W+1)/2]; for an odd
+ * extent the last window holds one row / column and the sum is divided by the number of valid elements.  y != x. */
+int emd_avgpool2x2_same_c1_f32(const float* x, float* y, int B, int H, int W, emd_stream_t stream);
+size_t emd_ms_ssim_workspace_bytes(int B, int H, int W, int level, int size);
+/* tf_ms_ssim (:170-192): `level` (1..5) SSIM passes with the 2x2 SAME average pool between them, weights 0.0448, 0.2856,
+ * 0.3001, 0.2363, 0.1333; value [B+1]: value[B] = prod(mcs[0:level-1] ** w[0:level-1]) * mssim[level-1] ** w[level-1] from
+ * the batch means (the reference's value), value[b] the same formula on image b's own means.  A negative mean cs under a
+ * fractional power gives NaN, as in the reference.  Needs H, W >= size * 2^(level-1).
+ * level_means: optional output [level][B+1][2], the emd_ssim_f32 means of every level. */
+int emd_ms_ssim_f32(const float* x, const float* y, int B, int H, int W, int level, const float* taps_host, int size, float* value,
+                    float* level_means, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_psnr_workspace_bytes(int B, long npix);
+/* out [B+1][2] = (mse, 10 log10(data_range^2 / mse)) of each image of npix pixels, row B for the batch mse (the mean of
+ * the images'); sums in double; mse == 0 gives +inf. */
+int emd_psnr_f32(const float* x, const float* y, int B, long npix, float data_range, float* out, void* workspace,
+                 size_t workspace_bytes, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
