@@ -80,6 +80,11 @@ SIGNATURES = {
     "emd_sep3x3_fused_s2_f32": (C.c_int, [_c_float_p, C.c_int, _c_float_p, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p,
                                           _c_float_p, _c_float_p, _c_float_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "emd_sep3x3_fused_s2_genres_supported": (C.c_int, [C.c_int] * 4),
+    # x ldx dw whi wlo scale1 shift1 scale2 shift2 img ldimg img_stride res_a res_t res_act y ldy B H W Cin Cout act stream
+    "emd_sep3x3_fused_s2_genres_f32": (C.c_int, [_c_float_p, C.c_int, _c_float_p, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p,
+                                                 _c_float_p, _c_float_p, _c_float_p, C.c_int, C.c_int, _c_float_p, _c_float_p, C.c_int,
+                                                 _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "emd_sep3x3_fused_s2_reflect_f32": (C.c_int, [_c_float_p, C.c_int, _c_float_p, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p,
                                           _c_float_p, _c_float_p, _c_float_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -484,13 +484,25 @@ struct Run {
             cnn0_last = sep("cnn0_last", cnn0, nullptr, nullptr);
             free(cnn0);
         }
-        T4 residual0 = E(B, S2, S2, F1);
-        if (live()) call(emd_cin1_f32(xin, nullptr, P["residual0"].a, P["residual0"].shift, residual0.ptr(), residual0.ld, B, S, S, F1, 2, 1, st));
         T4 concat1 = E(B, S2, S2, F2 + F1);
         T4 c1s = concat1.slice(F2, F1);
-        T4 cnn0_strided = sep("cnn0_strided", cnn0_last, &c1s, &residual0);
+        T4 cnn0_strided;
+        const LayerParams& ps = P["cnn0_strided"];
+        if (ps.d.stride == 2 && ps.d.rate == 1 && emd_sep3x3_fused_supported(S, S, ps.d.cin, ps.d.cout, 2, 1) &&
+            emd_sep3x3_fused_s2_genres_supported(S, S, ps.d.cin, ps.d.cout)) {
+            // residual0 = relu6(x[2y, 2x] * a + shift), rank 1 in the 1-channel input: generated in cnn0_strided's epilogue, never written
+            cnn0_strided = c1s;
+            if (live())
+                call(emd_sep3x3_fused_s2_genres_f32(cnn0_last.ptr(), cnn0_last.ld, ps.dw, ps.pw.hi, ps.pw.lo, ps.scale, ps.shift, ps.scale2, ps.shift2,
+                                                    xin, 1, 2, P["residual0"].a, P["residual0"].shift, 1, c1s.ptr(), c1s.ld, B, S, S, ps.d.cin,
+                                                    ps.d.cout, EMD_ACT_RELU6, st));
+        } else {
+            T4 residual0 = E(B, S2, S2, F1);
+            if (live()) call(emd_cin1_f32(xin, nullptr, P["residual0"].a, P["residual0"].shift, residual0.ptr(), residual0.ld, B, S, S, F1, 2, 1, st));
+            cnn0_strided = sep("cnn0_strided", cnn0_last, &c1s, &residual0);
+            free(residual0);
+        }
         free(cnn0_last);
-        free(residual0);
         // encoder 1 (:267-279)
         T4 residual1 = conv1x1("residual1", cnn0_strided, nullptr);
         T4 cnn1 = sep("cnn1", cnn0_strided, nullptr, nullptr);

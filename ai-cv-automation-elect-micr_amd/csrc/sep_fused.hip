@@ -602,9 +602,43 @@ extern "C" int emd_sep3x3_fused_f32(const float* x, int ldx, const float* dw, co
 // The stride-2 separable block (strided_conv_block(stride=2), machine_learning/denoiser.py:258, :273, :288) in one launch: x [B,H,W,Cin]
 // (H, W even; TF SAME = no padding before, one pixel after) -> y [B,H/2,W/2,Cout].  Split-bf16.  Same arithmetic as emd_dw3x3_f32(stride 2)
 // followed by emd_conv1x1_f32; the depthwise result never exists in memory.
+struct GenRes {   // the generated residual of emd_sep3x3_fused_s2_genres_f32 (SepParams::rg_*)
+    const float* img;
+    int ld, stride;
+    const float* a;
+    const float* t;
+    int act;
+};
+
 static int sep_s2_entry(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
                         const float* shift1, const float* scale2, const float* shift2, const float* res, int ldres, float* y, int ldy,
-                        int B, int H, int W, int Cin, int Cout, int act, int reflect, emd_stream_t stream);
+                        int B, int H, int W, int Cin, int Cout, int act, int reflect, emd_stream_t stream, const GenRes* gr = nullptr);
+
+// The same block with the residual GENERATED in the epilogue: res[b][oy][ox][c] = f(img[b][oy * img_stride][ox * img_stride] * res_a[c] +
+// res_t[c]), f = relu6 if res_act else the identity -- what emd_cin1_f32(img, NULL, res_a, res_t, ..., stride = img_stride, res_act) writes
+// for a residual projection of the 1-channel image (residual0 of graph D, machine_learning/denoiser.py:252: a 1x1 conv of one channel is
+// rank 1), same fma, same clamp; that tensor is then neither written nor read.  Cout <= 128.
+extern "C" int emd_sep3x3_fused_s2_genres_supported(int H, int W, int Cin, int Cout) {
+    emd::SepParams q{};
+    q.H = H; q.W = W; q.Cin = Cin; q.N = Cout; q.stride = 2; q.rg_stride = 2;
+    return Cout % 4 == 0 && Cout >= 4 && 64 % (Cout / 4) == 0 && emd::sep_pipe_covers(q, 3);   // (Cout / 4 divides 64: emd_cin1_f32's rule)
+}
+
+extern "C" int emd_sep3x3_fused_s2_genres_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
+                                              const float* scale1, const float* shift1, const float* scale2, const float* shift2,
+                                              const float* img, int ldimg, int img_stride, const float* res_a, const float* res_t,
+                                              int res_act, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
+                                              emd_stream_t stream) {
+    EMD_REQUIRE(img && res_a && res_t, EMD_E_INVALID, "emd_sep3x3_fused_s2_genres_f32: null pointer");
+    EMD_REQUIRE(ldimg >= 1 && img_stride >= 1, EMD_E_INVALID, "emd_sep3x3_fused_s2_genres_f32: image pitch and sampling stride must be >= 1");
+    // what emd_cin1_f32 takes (stride 1 or 2; Cout / 4 a divisor of 64: the predicate), so that the promised equivalence has a left-hand
+    // side; the pixel pitch is the one thing beyond it (d as channel 0 of a wider scratch tensor, as emd_sep3x3_fused_gen_f32 takes it)
+    EMD_REQUIRE(img_stride <= 2 && ldimg <= 64, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_s2_genres_f32: sampling stride 1 or 2, image pitch <= 64");
+    EMD_REQUIRE(emd_sep3x3_fused_s2_genres_supported(H, W, Cin, Cout), EMD_E_UNSUPPORTED,
+                "emd_sep3x3_fused_s2_genres_f32: needs H%8==0, W%32==0, Cin%32==0, Cout%4==0, Cout<=128 (use emd_cin1_f32 + emd_sep3x3_fused_s2_f32)");
+    const GenRes gr{img, ldimg, img_stride, res_a, res_t, res_act ? 1 : 0};
+    return sep_s2_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, nullptr, 0, y, ldy, B, H, W, Cin, Cout, act, 0, stream, &gr);
+}
 
 extern "C" int emd_sep3x3_fused_s2_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
                                        const float* scale1, const float* shift1, const float* scale2, const float* shift2,
@@ -625,7 +659,7 @@ extern "C" int emd_sep3x3_fused_s2_reflect_f32(const float* x, int ldx, const fl
 
 static int sep_s2_entry(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
                         const float* shift1, const float* scale2, const float* shift2, const float* res, int ldres, float* y, int ldy,
-                        int B, int H, int W, int Cin, int Cout, int act, int reflect, emd_stream_t stream) {
+                        int B, int H, int W, int Cin, int Cout, int act, int reflect, emd_stream_t stream, const GenRes* gr) {
     EMD_REQUIRE(x && dw && whi && wlo && scale1 && shift1 && y, EMD_E_INVALID, "emd_sep3x3_fused_s2_f32: null pointer");
     EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_s2_f32: scale2/shift2 pair");
     EMD_REQUIRE(B >= 0 && H >= 2 && W >= 2, EMD_E_INVALID, "emd_sep3x3_fused_s2_f32: bad shape");
@@ -646,6 +680,9 @@ static int sep_s2_entry(const float* x, int ldx, const float* dw, const uint16_t
     p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
     p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
     p.ldx = ldx; p.ldy = ldy; p.ldres = ldres; p.act = act; p.stride = 2; p.reflect = reflect ? 1 : 0;
+    if (gr) {
+        p.rg_x = gr->img; p.rg_ld = gr->ld; p.rg_stride = gr->stride; p.rg_a = gr->a; p.rg_t = gr->t; p.rg_act = gr->act;
+    }
     EMD_REQUIRE(emd::sep_pipe_covers(p, 3), EMD_E_UNSUPPORTED, "emd_sep3x3_fused_s2_f32: the pipelined kernel is switched off (dev knob sep_pipe)");
     return emd::sep_pipe_launch(p, B, static_cast<hipStream_t>(stream));
 }

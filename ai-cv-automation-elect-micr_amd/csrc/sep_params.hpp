@@ -27,20 +27,30 @@ struct SepParams {
     const float* gen_a;
     const float* gen_t;
     int gen_act;
+    int rg_stride;        // > 0: the residual is generated (below)
     // second output of the DUAL instances (emd_sep3x3_dual_f32): y2 = relu6(x * W2 * scale_b + shift_b), a 1x1 conv of the block's
     // INPUT -- the decoder's residual projection (denoiser.py:359/:371/:383), which reads the same tensor as the separable conv
-    const uint16_t* W2hi;
+    // Generated residual (rg_stride > 0; sep_pipe.hip, the stride-2 128-column instance: emd_sep3x3_fused_s2_genres_f32): where res would be
+    // read, the epilogue computes what emd_cin1_f32 (no depthwise stage) would have written there -- fma(d, rg_a[c], rg_t[c]), relu6 if
+    // rg_act -- from the one-value-per-pixel image rg_x (pitch rg_ld floats) sampled every rg_stride pixels: d = rg_x[b][oy * rg_stride]
+    // [ox * rg_stride].  That instance has one output: its three pointers share the second output's storage and its three ints sit in
+    // what was alignment padding, so the block keeps its size and offsets -- a longer block changes the code the compiler makes for
+    // EVERY instance (argument loads regroup, scratch sizes and VGPR counts move), which this one must not.
+    union { const uint16_t* W2hi; const float* rg_x; };
     const uint16_t* W2lo;
     float* y2;
-    const float* scale_b;
-    const float* shift_b;
+    union { const float* scale_b; const float* rg_a; };
+    union { const float* shift_b; const float* rg_t; };
     int N2, ldy2;
     int out_split;        // y is a split32 tensor (pitch ldy 4-byte units; N % 32 == 0): the consumer is a split32 GEMM
+    int rg_ld;
     long long* stamps;    // dev hook: per-workgroup phase cycle sums (NULL otherwise)
     int nt;               // outputs leave with non-temporal stores (they are not re-read by this launch: keep L2 for the patch halos)
     int ablate;           // dev: sep_pipe phase ablation bits (0 in every product launch)
     int xcd;              // workgroup -> tile map that gives each XCD (workgroup id mod 8) one contiguous run of tiles
+    int rg_act;
 };
+static_assert(sizeof(SepParams) == 232, "SepParams: the rg_* fields fill padding and share storage; see above before adding a field");
 
 // sep_pipe.hip: true when the LDS-DMA pipelined kernel covers the launch (stride 1, split-bf16, no generated input, W % 32 == 0)
 bool sep_pipe_covers(const SepParams& p, int precision);

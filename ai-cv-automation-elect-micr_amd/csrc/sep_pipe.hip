@@ -52,7 +52,11 @@ __device__ __attribute__((aligned(16))) float g_zero_pipe[4096];
 // there is no patch to fetch: where the other instances request the DMA pieces of a chunk, every lane computes the 16 bytes its DMA
 // lane would have received and writes them to the same place.  d of the NEXT tile is loaded one tile ahead; the depthwise weights of
 // all chunks (Cin <= 64) sit in their own 2.25 KiB of LDS for the workgroup's life.
-template <int BN, bool DUAL, int MODE, bool OSPLIT, int NW = 8, int STRIDE = 1, int EPI = 1, bool GEN = false>     // EPI: dwords a lane stores at a time (epilogue)
+// RGEN: the RESIDUAL is generated -- relu6(d * rg_a[c] + rg_t[c]), d the 1-channel image sampled under the output pixel (cin1_kernel of
+// dw_misc.hip without its depthwise stage, same fma and clamp: residual0 of graph D) -- where the other instances prefetch the tile's
+// residual values a lane fetches the sixteen d of its pixels instead (as many loads, so the vmcnt arithmetic is the same; a half wave
+// reads one address) and the epilogue evaluates the expression for its channel: no [B,H/2,W/2,N] tensor is written and read back.
+template <int BN, bool DUAL, int MODE, bool OSPLIT, int NW = 8, int STRIDE = 1, int EPI = 1, bool GEN = false, bool RGEN = false>     // EPI: dwords a lane stores at a time (epilogue)
 __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p) {
     constexpr int TW = STRIDE == 2 ? 16 : 4 * NW, TH = STRIDE == 2 ? 4 : 8, BM = TH * TW;
     constexpr int PW = STRIDE * TW + 3 - STRIDE, PH = STRIDE * TH + 3 - STRIDE, PWS = PW | 1;   // patch pixels per row; slot pitch odd (see above): 34 -> 35, 18 -> 19, 33
@@ -233,6 +237,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
 
     // ---- epilogue constants: lane = output channel
     float es1[TN], et1[TN], es2[TN], et2[TN];
+    float rga = 0.f, rgt = 0.f;   // RGEN: this lane's channel of the generated residual's a / shift
     const bool two = p.scale2 != nullptr && !out2;
     const int nlim = out2 ? p.N2 : p.N;
     const bool full = DUAL ? (p.N == BN / 2 && p.N2 == BN / 2) : p.N == BN;   // no lane is masked in the epilogue: store counts are exact
@@ -245,6 +250,11 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
         et1[j] = valid ? (out2 ? p.shift_b : p.shift1)[nn] : 0.f;
         es2[j] = (valid && two) ? p.scale2[nn] : 1.f;
         et2[j] = (valid && two) ? p.shift2[nn] : 0.f;
+        if constexpr (RGEN) {   // (TN == 1)
+            rga = valid ? p.rg_a[nn] : 0.f;
+            rgt = valid ? p.rg_t[nn] : 0.f;
+            asm volatile("" ::"v"(rga), "v"(rgt));
+        }
         // first use here: the wait for these loads stays in front of the loop (inside it, it would also wait for every older DMA)
         asm volatile("" ::"v"(es1[j]), "v"(et1[j]), "v"(es2[j]), "v"(et2[j]));
     }
@@ -349,8 +359,24 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
     constexpr bool RPRE = TM <= 2 && !DUAL;
     constexpr int R = RPRE ? 16 / EPI * TM * TN : 0;         // residual loads per wave and tile
     f32x4 rpre[RPRE ? TM : 1][TN][4];
-    const bool res_on = p.res != nullptr && !out2 && !(abl & 32);
+    static_assert(!RGEN || (RPRE && STRIDE == 2 && EPI == 1 && TM == 1 && TN == 1 && MODE == 1), "generated residual: the stride-2 128-column instance");
+    const bool res_on = (RGEN || p.res != nullptr) && !out2 && !(abl & 32);
     auto res_prefetch = [&](int x0) {
+        if constexpr (RGEN) {
+            // element k of rpre[0][0][q] = the image value under output pixel 8 q + 4 fh + k of the M tile (cin1_kernel: img[oy * stride][ox * stride])
+            int gs = p.rg_stride, gld = p.rg_ld;
+            asm volatile("" : "+s"(gs), "+s"(gld));
+            const long gW = (long)Wo * gs;                       // image row pitch in pixels
+            const float* gbase = p.rg_x + (((long)bz * (p.H / STRIDE) * gs + (long)(y0 + row0 / TW) * gs) * gW + (long)x0 * gs) * gld;
+            const unsigned goff = (unsigned)(4 * fh * gs * gld) * 4u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float* gb = gbase + ((8 * q / TW) * gs * gW + (8 * q % TW) * gs) * gld;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) rpre[0][0][q][k] = load_s1(gb + k * gs * gld, goff);
+            }
+            return;
+        }
         int ldr = p.ldres;
         asm volatile("" : "+s"(ldr));
         const int li = fr & 3, cq = fr >> 2;
@@ -501,6 +527,16 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
                             }
 #pragma unroll
                             for (int q = 0; q < 4; ++q) rv[q] = rpre[i][j][q];
+                            if constexpr (RGEN) {   // cin1_kernel's expression for (pixel, this lane's channel): fma, then relu6 as min(max(., 0), 6)
+                                const bool ract = p.rg_act != 0;
+#pragma unroll
+                                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                                    for (int k = 0; k < 4; ++k) {
+                                        const float g = fmaf(rv[q][k], rga, rgt);
+                                        rv[q][k] = ract ? fminf(fmaxf(g, 0.f), 6.f) : g;
+                                    }
+                            }
                         }
                     } else if (has_res) {
                         if (n < nlim) {
@@ -811,6 +847,7 @@ bool sep_pipe_covers(const SepParams& p, int precision) {
     if (p.gen_a)   // generated input (round 4, opt-in: dev knob sep_gen_pipe): the 4-wave 64-column instance only -- cnn0_last of graphs D / X and its likes
         return g_knobs.sep_gen_pipe && p.stride == 1 && p.H % 8 == 0 && p.W % 16 == 0 && (p.Cin == 32 || p.Cin == 64) && p.N <= 64 && p.N2 == 0 &&
                !p.out_split && !p.res && g_knobs.sep_nw != 8;
+    if (p.rg_stride && (p.stride != 2 || p.N2 > 0 || p.N > 128 || p.res || p.reflect)) return false;   // generated residual: the stride-2 128-column instance only
     if (p.stride == 2)   // output tiles of 4 x 16 pixels: H % 8 == 0, W % 32 == 0 (input sizes); one fp32 output of up to 256 channels
         return p.H % 8 == 0 && p.W % 32 == 0 && p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 4064 && p.N2 == 0 && !p.out_split && p.N <= 256;
     if (p.H % 8 != 0 || p.W % (use_nw4(p) ? 16 : 32) != 0 || p.Cin % 32 != 0 || p.Cin < 32 || p.Cin > 4064) return false;
@@ -827,7 +864,7 @@ bool sep_pipe_covers(const SepParams& p, int precision) {
 // issues ~1.9 x the instructions per chunk -- and graph D 22.10 ms with 0, 22.26 with 1, 23.07 with 2 in one process.  A forced 4-wave
 // form (dev knob sep_nw = 4) always means this file's kernel.
 static bool use_pipe2(const SepParams& p) {
-    if (p.gen_a) return false;
+    if (p.gen_a || p.rg_stride) return false;
     if (!g_knobs.sep_pipe2 || g_knobs.sep_ablate || g_knobs.sep_nw == 4 || !sep_pipe2_covers(p)) return false;
     if (g_knobs.sep_pipe2 == 2) return true;
     return p.N2 > 0 && (p.N > 64 || p.N2 > 64);
@@ -859,6 +896,10 @@ int sep_pipe_launch(const SepParams& p, int B, hipStream_t st) {
         if (g_knobs.epi_width == 4) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 4, true>), grid, dim3(256), 0, st, q);
         else hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 1, true>), grid, dim3(256), 0, st, q);
         return emd::check_launch("sep_pipe_kernel<generated input>");
+    }
+    if (p.rg_stride) {   // one instance: the schedule and the epilogue the rule gives the same layer with a residual tensor (the knobs do not apply)
+        hipLaunchKernelGGL((sep_pipe_kernel<128, false, 1, false, 8, 2, 1, false, true>), grid, dim3(512), 0, st, q);
+        return emd::check_launch("sep_pipe_kernel<stride 2, generated residual>");
     }
     const int epi = g_knobs.epi_width ? g_knobs.epi_width : ((p.res && p.N > 128) ? 4 : 1);
     return epi == 4 ? launch_epi<4>(p, q, grid, mode, nw, st) : launch_epi<1>(p, q, grid, mode, nw, st);

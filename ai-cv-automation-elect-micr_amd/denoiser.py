@@ -352,6 +352,14 @@ class DenoiserEngine:
                     res=res, precision=self.precision)
         return out
 
+    def _residual0_generated(self, x):
+        """True where cnn0_strided (input x) takes emd_sep3x3_fused_s2_genres_f32: wherever _sep would take the one-launch stride-2 form
+        and the generated-residual instance covers the shape; elsewhere residual0 is written by cin1 and read back as before."""
+        L = self.layers["cnn0_strided"]
+        return bool(self.fuse_sep and self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_SEP_S2", "1") != "0"
+                    and L.stride == 2 and L.rate == 1 and ops.sep_fused_supported(x, L.cout, L.stride, L.rate)
+                    and ops.sep_fused_s2_genres_supported(x, L.cout))
+
     def _sep_gemm_ok(self, x, L):
         return (self.fuse_sep and self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_SEPGEMM", "0") == "1"   # opt-in: measured slower than the two-kernel route (DESIGN.md 3.2c)
                 and ops.sep_gemm_supported(x, L.cout, L.stride, L.rate))
@@ -532,10 +540,19 @@ class DenoiserEngine:
         else:
             cnn0 = ops.cin1(x, P["cnn0"]["w9"], P["cnn0"]["a"], P["cnn0"]["shift"], E(S, f0))
             cnn0_last = self._sep("cnn0_last", cnn0)
-        residual0 = ops.cin1(x, None, P["residual0"]["a"], P["residual0"]["shift"], E(S2, f1), stride=2)
         concat1 = E(S2, f2 + f1)
-        cnn0_strided = self._sep("cnn0_strided", cnn0_last, out=concat1.slice(f2, f1), res=residual0)
-        del cnn0, cnn0_last, residual0
+        if self._residual0_generated(cnn0_last):
+            # residual0 = relu6(x[2y, 2x] * a + shift) is rank 1 in the 1-channel input: cnn0_strided's epilogue evaluates it where it
+            # would have read it (emd_sep3x3_fused_s2_genres_f32, same bits) -- one launch, a [B,S/2,S/2,128] write and its read less
+            ps, pr = P["cnn0_strided"], P["residual0"]
+            cnn0_strided = ops.sep_fused(cnn0_last, ps["dw"], ps["pw"], ps["scale"], ps["shift"], concat1.slice(f2, f1),
+                                         scale2=ps.get("scale2"), shift2=ps.get("shift2"), precision=self.precision, stride=2,
+                                         gen_res=(x, pr["a"], pr["shift"]))   # (through sep_fused: the launch stays in its kernel family)
+        else:
+            residual0 = ops.cin1(x, None, P["residual0"]["a"], P["residual0"]["shift"], E(S2, f1), stride=2)
+            cnn0_strided = self._sep("cnn0_strided", cnn0_last, out=concat1.slice(f2, f1), res=residual0)
+            del residual0
+        del cnn0, cnn0_last
         # encoder 1 (:267-279); cnn1_strided lives in concat2 (:353)
         residual1 = self._conv1x1("residual1", cnn0_strided)
         cnn1 = self._sep("cnn1", cnn0_strided)

@@ -192,13 +192,16 @@ def sep_fused_supported(x: Act, cout: int, stride: int, rate: int) -> bool:
 
 
 def sep_fused(x: Act, dw_dev, w: PackedWeights, scale1, shift1, out: Act, act=True, scale2=None, shift2=None,
-              res: Act | None = None, precision=PREC_BF16X3, stream=None, reflect=False, stride=1):
+              res: Act | None = None, precision=PREC_BF16X3, stream=None, reflect=False, stride=1, gen_res=None):
     """Depthwise 3x3 + pointwise + epilogue in one launch (emd_sep3x3_fused_f32; reflect=True: the depthwise stage reads the
     REFLECT-padded border, emd_sep3x3_fused_reflect_f32; stride=2: emd_sep3x3_fused_s2_f32, split-bf16 only)."""
     lib = _lib.load()
     assert (out.B, out.H, out.W, out.C) == (x.B, -(-x.H // stride), -(-x.W // stride), w.cout) and w.cin == x.C and w.taps == 1
     if res is not None:
         assert (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, out.C)
+    if gen_res is not None:   # (img, a, shift): the residual is generated in the epilogue (sep_fused_s2_genres), res is not a tensor
+        assert stride == 2 and res is None and not reflect and precision == PREC_BF16X3
+        return sep_fused_s2_genres(x, dw_dev, w, scale1, shift1, out, *gen_res, act=act, scale2=scale2, shift2=shift2, stream=stream)
     if stride == 2:
         assert precision == PREC_BF16X3 and not isinstance(out, SplitAct)
         rc = (lib.emd_sep3x3_fused_s2_reflect_f32 if reflect else lib.emd_sep3x3_fused_s2_f32)(x.ptr, x.ld, _p(dw_dev), _p(w.hi), _p(w.lo), _p(scale1), _p(shift1), _p(scale2), _p(shift2),
@@ -220,6 +223,26 @@ def sep_fused(x: Act, dw_dev, w: PackedWeights, scale1, shift1, out: Act, act=Tr
                                   res.ld if res is not None else 0, out.ptr, out.ld, x.B, x.H, x.W, x.C, w.cout,
                                   _act(act), precision, _lib.stream_ptr(stream))
     _lib.check(rc, "emd_sep3x3_fused_f32")
+    return out
+
+
+def sep_fused_s2_genres_supported(x: Act, cout: int) -> bool:
+    return bool(_lib.load().emd_sep3x3_fused_s2_genres_supported(x.H, x.W, x.C, cout))
+
+
+def sep_fused_s2_genres(x: Act, dw_dev, w: PackedWeights, scale1, shift1, out: Act, img, res_a, res_shift, img_stride=2, res_act=True,
+                        act=True, scale2=None, shift2=None, stream=None):
+    """The stride-2 separable block whose residual is generated in the epilogue (emd_sep3x3_fused_s2_genres_f32): the same bits as
+    cin1(img, None, res_a, res_shift, res, stride=img_stride, act=res_act) + sep_fused(..., res=res, stride=2), without the tensor res.
+    img: torch CUDA float32 [B,Hi,Wi] or [B,Hi,Wi,1] contiguous, Hi = out.H * img_stride."""
+    lib = _lib.load()
+    assert (out.B, out.H, out.W, out.C) == (x.B, x.H // 2, x.W // 2, w.cout) and w.cin == x.C and w.taps == 1 and not isinstance(out, SplitAct)
+    assert img.is_contiguous() and img.numel() == out.B * out.H * img_stride * out.W * img_stride
+    assert res_a.numel() >= w.cout and res_shift.numel() >= w.cout
+    rc = lib.emd_sep3x3_fused_s2_genres_f32(x.ptr, x.ld, _p(dw_dev), _p(w.hi), _p(w.lo), _p(scale1), _p(shift1), _p(scale2), _p(shift2),
+                                            _p(img), 1, img_stride, _p(res_a), _p(res_shift), 1 if res_act else 0, out.ptr, out.ld,
+                                            x.B, x.H, x.W, x.C, w.cout, _act(act), _lib.stream_ptr(stream))
+    _lib.check(rc, "emd_sep3x3_fused_s2_genres_f32")
     return out
 
 

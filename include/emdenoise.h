@@ -315,6 +315,18 @@ int emd_sep3x3_fused_s2_f32(const float* x, int ldx, const float* dw, const uint
                             const float* scale1, const float* shift1, const float* scale2, const float* shift2,
                             const float* res, int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
                             emd_stream_t stream);
+/* The same with the residual GENERATED in the epilogue instead of read: res[b][oy][ox][c] = f(img[b][oy*img_stride][ox*img_stride] *
+ * res_a[c] + res_t[c]), f = relu6 if res_act else the identity; img is a one-value-per-pixel tensor [B, H/2*img_stride, W/2*img_stride]
+ * with pixel pitch ldimg floats.  Bit for bit emd_cin1_f32(img, NULL, res_a, res_t, res, ..., stride = img_stride, res_act) followed by
+ * emd_sep3x3_fused_s2_f32(..., res, ...) -- the residual projection of the 1-channel input (residual0, machine_learning/denoiser.py:252)
+ * is rank 1 and never exists in memory.  img_stride 1 or 2, ldimg <= 64; the image must be exactly H/2*img_stride rows of W/2*img_stride
+ * pixels per batch entry (the kernel derives its row pitch from W; nothing else tells it).  Cout <= 128 with Cout/4 a divisor of 64
+ * (emd_cin1_f32's rule); emd_sep3x3_fused_s2_genres_supported(H, W, Cin, Cout) says where it applies. */
+int emd_sep3x3_fused_s2_genres_supported(int H, int W, int Cin, int Cout);
+int emd_sep3x3_fused_s2_genres_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
+                                   const float* scale1, const float* shift1, const float* scale2, const float* shift2,
+                                   const float* img, int ldimg, int img_stride, const float* res_a, const float* res_t, int res_act,
+                                   float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act, emd_stream_t stream);
 /* The same on the tf.pad(REFLECT, 1) image with VALID padding: graph G's down-sampling strided_conv_block(stride 2, pad_size = (1, 1))
  * (misc_py/gan-infilling-100.py:205-243, :345-352).  Same shape rules (emd_sep3x3_fused_supported(H, W, Cin, Cout, 2, 1)). */
 int emd_sep3x3_fused_s2_reflect_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
