@@ -14,16 +14,11 @@
 // (a bias added before a training-mode batch norm cancels: its gradient is zero and it only shifts the moving mean).
 #include "emd_common.hpp"
 #include "bn_chain_dev.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
-__device__ __forceinline__ float grad_mask(float dy, float z, int mask) {
-    if (mask == 1) return (z > 0.f && z < 6.f) ? dy : 0.f;   // tf.nn.relu6 (Relu6Grad: 0 < z < 6)
-    if (mask == 2) return (z > 0.f && z <= 1.f) ? dy : 0.f;  // relu6 then tf.clip_by_value(., 0, 1) (passes on [0,1])
-    if (mask == 3) return z > 0.f ? dy : 0.2f * dy;           // tf.nn.leaky_relu, alpha 0.2 (graph G)
-    if (mask == 4) return z > 0.f ? dy : 0.f;                 // tf.nn.relu (ReluGrad: z > 0; graph S)
-    return dy;
-}
+using namespace emd;
 
 // Round 4: dy given as the data gradient of a 3x3 conv to ONE output channel (the network's final conv: dy[p][c] = sum_taps g1[p + (1-ky,
 // 1-kx)] * w9[ky*3+kx][c], TF SAME) -- never written; formed here from the 1-channel image g1 in dw_bwd_data_kernel<true>'s order (its bits).
@@ -815,7 +810,6 @@ extern "C" int emd_bn_bwd_prep_images_f32(const float* s1, const float* t, const
                                           emd_stream_t stream) {
     return bwd_prep_impl(s1, t, gamma1, gamma2, rstd1, rstd2, eps, npix, B, C, K, m1, m2, dgamma1, dgamma2, dbeta2, stream);
 }
-
 
 // ---- the small-map one-launch forms (round 4; kernels above).  Per-image statistics only (a tower of one image, or B such towers as
 // one batched pass: B = 1 is the plain batch norm of one image).  npix <= 4096 (EMD_E_UNSUPPORTED above: one workgroup per 64 channels

@@ -8,20 +8,11 @@
 //   emd_denoise_loss_f32                                 mse, the capped loss and dLoss/dOutput
 //   emd_nesterov_step_f32                                tf.train.MomentumOptimizer(use_nesterov=True)
 #include "emd_common.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-// relu (hi = +inf) / relu6 (hi = 6) in affine_relu6_kernel's order (dw_misc.hip): the PRE forms rebuild its bits
-__device__ __forceinline__ float4 clamp4(float4 a, float hi) {
-    return make_float4(fminf(fmaxf(a.x, 0.f), hi), fminf(fmaxf(a.y, 0.f), hi), fminf(fmaxf(a.z, 0.f), hi), fminf(fmaxf(a.w, 0.f), hi));
-}
-__device__ __forceinline__ float4 fma4s(float4 a, float s, float4 c) {
-    return make_float4(fmaf(a.x, s, c.x), fmaf(a.y, s, c.y), fmaf(a.z, s, c.z), fmaf(a.w, s, c.w));
-}
+using namespace emd;
 
 inline int same_pad_before(int n, int s, int r) {  // TF SAME, k = 3
     const int o = (n + s - 1) / s;

@@ -1,4 +1,4 @@
-// Parameter block of the patch-resident dense 3x3 convolution (conv3_pipe.hip), shared with its dispatcher (gemm_split.hip).
+// Parameter block of the patch-resident dense 3x3 convolution (conv3_pipe.hip), shared with its dispatcher (conv_split.hip).
 #pragma once
 
 #include "mfma_common.hpp"

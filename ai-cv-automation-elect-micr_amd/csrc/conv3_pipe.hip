@@ -1,8 +1,8 @@
 // Dense 3x3 convolution (stride 1, rate 1, TF SAME) from a split32 input with the input PATCH resident in LDS across the nine taps.
 // replaces: tf.layers.conv2d(k = 3) + bias -> relu -> batch norm -> relu = conv_block of misc_py/modified_Xception.py:215-229 for the
-//           decoder's narrow layers (:538-621: 128 -> 64 and 64 -> 64 at full resolution), reached through emd_conv3x3_split32_f32.
+//           decoder's narrow layers (:538-621: 128 -> 64 and 64 -> 64 at full resolution), reached through emd_conv3x3_split32_f32 (conv_split.hip).
 //
-// Why: gemm_split_conv_kernel<64> brings a tap's 256 A rows into LDS for every (tap, 32-channel step) -- nine times the input per tile,
+// Why: gemm_split_conv_kernel<64> (conv_split.hip) brings a tap's 256 A rows into LDS for every (tap, 32-channel step) -- nine times the input per tile,
 // 40 KB of DMA writes per K step for 64 output columns -- and a 64 x 32 wave tile reads 1 KB of fragments per MFMA: 1.4 KB of LDS
 // traffic per MFMA against the 1 KB/MFMA the LDS pipe can feed at the matrix cores' issue rate; the two 512^2 layers of graph X ran
 // at 0.27 of 2.5 PFLOP/s issued.  Here the (8+2) x (32+2) pixel patch of a 32-channel chunk (already bf16 hi | lo lines of 128 B: the
@@ -27,55 +27,7 @@ namespace {
 
 using namespace emd;
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 __device__ __attribute__((aligned(128))) unsigned char g_zero_c3[16384];   // padding pixels: "+ chunk offset" stays inside for Cin <= 4064
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N < 63 ? N : 63) : "memory");
-}
-// Fragment reads by hand: the compiler neither sees them nor waits for them (it would wait with lgkmcnt(0), i.e. also for the NEXT
-// unit's reads issued behind them); the wait in front of a unit's MFMAs lets the younger reads stay in flight and ties the registers.
-template <int OFF>
-__device__ __forceinline__ bf16x8 lds_read16(const unsigned char* p) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"((lptr_t)p), "n"(OFF) : "memory");
-    return v;
-}
-__device__ __forceinline__ void store_nt_d(const void* sbase, unsigned voff, unsigned v) {
-    asm volatile("global_store_dword %0, %1, %2 nt" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void store_nt_s(const void* sbase, unsigned voff, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 3" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void store_nt_s(const void* sbase, unsigned voff, u32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 3" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ float dpp_f(float v, int xor2) {
-    return xor2 ? __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true))
-                : __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-}
-// 4 x 4 transpose inside a lane quad: in, lane i holds column i of the block; out, row i (sep_pipe.hip has the same helper)
-__device__ __forceinline__ void quad_transpose(float (&r)[4], int li) {
-    const bool b0 = li & 1, b1 = li & 2;
-    float s0 = b0 ? r[0] : r[1], s1 = b0 ? r[2] : r[3];
-    s0 = dpp_f(s0, 0);
-    s1 = dpp_f(s1, 0);
-    r[0] = b0 ? s0 : r[0]; r[1] = b0 ? r[1] : s0;
-    r[2] = b0 ? s1 : r[2]; r[3] = b0 ? r[3] : s1;
-    float t0 = b1 ? r[0] : r[2], t1 = b1 ? r[1] : r[3];
-    t0 = dpp_f(t0, 1);
-    t1 = dpp_f(t1, 1);
-    r[0] = b1 ? t0 : r[0]; r[2] = b1 ? r[2] : t0;
-    r[1] = b1 ? t1 : r[1]; r[3] = b1 ? r[3] : t1;
-}
-__device__ __forceinline__ unsigned xchg4(unsigned v, bool oddq) {
-    const unsigned up = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xF, 0xF, true);   // row_shl:4
-    const unsigned dn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    return oddq ? dn : up;
-}
 
 template <bool OSPLIT, int EPI>      // EPI: dwords a lane stores at a time (1; 4 behind dev knob epi_width)
 __global__ __launch_bounds__(512, 1) void conv3_pipe_kernel(const Conv3Params p) {
@@ -91,16 +43,7 @@ __global__ __launch_bounds__(512, 1) void conv3_pipe_kernel(const Conv3Params p)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {   // XCD k takes the k-th contiguous eighth of the tile list: halo rows meet in one L2
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned t = (id & 7) * (total >> 3) + (id >> 3);
-        if ((total & 7) == 0) {
-            bx = t % gridDim.x;
-            by = (t / gridDim.x) % gridDim.y;
-            bz = t / (gridDim.x * gridDim.y);
-        }
-    }
+    xcd_remap((gridDim.x * gridDim.y * gridDim.z & 7) == 0, bx, by, bz);   // halo rows meet in one L2
     // the column tiles (64 output channels each) of one pixel tile are neighbours in the launch order: the patch they share comes from L2
     const int n0 = (bx % p.n_ntiles) * BN;
     bx /= p.n_ntiles;

@@ -2,8 +2,8 @@
 // input with the input PATCH resident in LDS: the four output phases of a tile's 8 x 32 input pixels read their A fragments from one
 // (8+1) x (32+1) pixel patch per 32-channel chunk (the taps reach one pixel up and one to the left), nine (phase, tap) weight tiles
 // stream past it three per step, four accumulator sets (one per phase) of 32 pixels x 64 columns per wave.  Structure, swizzles, ring
-// and vmcnt bookkeeping: conv3_pipe.hip.  Sums chunk-major (the one-launch GEMM form sums tap-major per phase): same error class,
-// other last bits.  Reached through emd_deconv3x3s2_fused_split32_f32 (dev knob deconv_direct = 3).
+// and vmcnt bookkeeping: conv3_pipe.hip.  Sums chunk-major (the one-launch GEMM form, conv_split.hip, sums tap-major per phase): same error class,
+// other last bits.  Reached through emd_deconv3x3s2_fused_split32_f32 (conv_split.hip; dev knob deconv_direct = 3).
 #include <type_traits>
 
 #include "conv3_params.hpp"
@@ -12,55 +12,7 @@ namespace {
 
 using namespace emd;
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 __device__ __attribute__((aligned(128))) unsigned char g_zero_dc[16384];   // padding pixels: "+ chunk offset" stays inside for Cin <= 4064
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N < 63 ? N : 63) : "memory");
-}
-__device__ __forceinline__ void store_nt_s(const void* sbase, unsigned voff, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 3" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void store_nt_s(const void* sbase, unsigned voff, u32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 3" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-// Fragment reads by hand: the compiler neither sees them nor waits for them (it would wait with lgkmcnt(0), i.e. also for the NEXT
-// unit's reads issued behind them); wait_frags<N> lets the N youngest LDS reads stay in flight and ties the registers to the wait.
-template <int OFF>
-__device__ __forceinline__ bf16x8 lds_read16(const unsigned char* p) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"((lptr_t)p), "n"(OFF) : "memory");
-    return v;
-}
-__device__ __forceinline__ void store_nt_d(const void* sbase, unsigned voff, unsigned v) {
-    asm volatile("global_store_dword %0, %1, %2 nt" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ float dpp_f(float v, int xor2) {
-    return xor2 ? __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true))
-                : __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-}
-// 4 x 4 transpose inside a lane quad: in, lane i holds column i of the block; out, row i (sep_pipe.hip has the same helper)
-__device__ __forceinline__ void quad_transpose(float (&r)[4], int li) {
-    const bool b0 = li & 1, b1 = li & 2;
-    float s0 = b0 ? r[0] : r[1], s1 = b0 ? r[2] : r[3];
-    s0 = dpp_f(s0, 0);
-    s1 = dpp_f(s1, 0);
-    r[0] = b0 ? s0 : r[0]; r[1] = b0 ? r[1] : s0;
-    r[2] = b0 ? s1 : r[2]; r[3] = b0 ? r[3] : s1;
-    float t0 = b1 ? r[0] : r[2], t1 = b1 ? r[1] : r[3];
-    t0 = dpp_f(t0, 1);
-    t1 = dpp_f(t1, 1);
-    r[0] = b1 ? t0 : r[0]; r[2] = b1 ? r[2] : t0;
-    r[1] = b1 ? t1 : r[1]; r[3] = b1 ? r[3] : t1;
-}
-__device__ __forceinline__ unsigned xchg4(unsigned v, bool oddq) {
-    const unsigned up = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x104, 0xF, 0xF, true);   // row_shl:4
-    const unsigned dn = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    return oddq ? dn : up;
-}
 
 // Tap table of slim.conv2d_transpose(k = 3, s = 2, SAME) in the order the nine (phase, tap) weight tiles are brought in, three per step.
 // Phase = 2 py + px of the output pixel (2 i + py, 2 j + px); emd_deconv_phase_taps (gemm_conv.hip) fixes the tap order inside a phase:
@@ -104,16 +56,7 @@ __global__ __launch_bounds__(512, 1) void deconv_pipe_kernel(const DeconvPipePar
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv >> 1, wn = wv & 1;      // tile rows 2 wm, 2 wm + 1; columns 32 wn ..
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {   // XCD k takes the k-th contiguous eighth of the tile list
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned t = (id & 7) * (total >> 3) + (id >> 3);
-        if ((total & 7) == 0) {
-            bx = t % gridDim.x;
-            by = (t / gridDim.x) % gridDim.y;
-            bz = t / (gridDim.x * gridDim.y);
-        }
-    }
+    xcd_remap((gridDim.x * gridDim.y * gridDim.z & 7) == 0, bx, by, bz);
     const int n0 = (bx % p.n_ntiles) * BN;
     bx /= p.n_ntiles;
     const int xbase = bx * p.tpw * TW, y0 = by * TH;

@@ -13,21 +13,11 @@
 //           _batch_norm_fn(is_training) + relu6 of the previous block (machine_learning/denoiser.py:110-136 under tf.gradients).
 #include "emd_common.hpp"
 #include "bn_chain_dev.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float grad_mask(float dy, float z, int mask) {   // bn_train.hip
-    if (mask == 1) return (z > 0.f && z < 6.f) ? dy : 0.f;
-    if (mask == 2) return (z > 0.f && z <= 1.f) ? dy : 0.f;
-    if (mask == 3) return z > 0.f ? dy : 0.2f * dy;
-    if (mask == 4) return z > 0.f ? dy : 0.f;
-    return dy;
-}
+using namespace emd;
 
 struct DwBnArgs {
     const float* dd;      // [B,H,W,C] gradient w.r.t. the consumer's depthwise output, pitch ldd

@@ -12,8 +12,11 @@
 
 #include "mfma_common.hpp"
 #include "bn_chain_dev.hpp"
+#include "f4_math.hpp"
 
 namespace {
+
+using namespace emd;
 
 // Workgroup ids are dealt to the 8 XCDs round-robin (id mod 8).  xcd_run gives XCD k the k-th contiguous eighth of the tile
 // list instead, so the tiles that share halo rows / columns (neighbours in the list) run on ONE XCD at about the same time and the
@@ -30,17 +33,7 @@ inline int dw_xcd(int H, int W) {
     return v == 2 || (v == 1 && (long)H * W <= 128L * 128);
 }
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float relu6f(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ float4 relu4(float4 a) { return make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)); }
-// relu (hi = +inf) or relu6 (hi = 6), in the order affine_relu6_kernel applies them: the PRE forms produce its bits
-__device__ __forceinline__ float4 clamp4(float4 a, float hi) {
-    return make_float4(fminf(fmaxf(a.x, 0.f), hi), fminf(fmaxf(a.y, 0.f), hi), fminf(fmaxf(a.z, 0.f), hi), fminf(fmaxf(a.w, 0.f), hi));
-}
 // act code of the Cout=1 kernels: 0 none, 1 relu6, 2 relu6 followed by tf.clip_by_value(0,1) = clamp to [0,1]
 __device__ __forceinline__ float act_out(float v, int act) { return act == 0 ? v : fminf(fmaxf(v, 0.f), act == 2 ? 1.f : 6.f); }
 // the Cout=1 kernels' output stage: optional "+pre_bias, relu" first (tf.layers.conv2d(activation=relu) before the

@@ -4,18 +4,12 @@
 // The pointwise halves, the SAME-padded separable convs of deconv_block and the resizes are the graph-D kernels.
 // All HBM-bound, fp32.
 #include "mfma_common.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-// tf.pad(mode="REFLECT"): index -1 -> 1, n -> n-2 (the border sample is not repeated)
-__device__ __forceinline__ int reflect(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
+using namespace emd;
+
 __device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : 0.2f * v; }
 
 // Depthwise 3x3 over the reflect-padded (1 px) input, VALID, stride 1 or 2: output (oy,ox) reads rows

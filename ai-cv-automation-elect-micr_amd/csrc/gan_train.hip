@@ -2,8 +2,11 @@
 // :1378-1379 / :1429-1431 Adam wrapped in clip_gradients_by_norm).  Everything here is tiny or HBM-bound; the
 // convolution gradients are the graph-D' kernels (wgrad.hip, bn_train.hip, bwd_misc.hip) with a leaky-relu mask.
 #include "emd_common.hpp"
+#include "f4_math.hpp"
 
 namespace {
+
+using namespace emd;
 
 // Head of one tower (batch_size = 1, :74): out = sigmoid(max(logit[0..2])).
 //   mode 0 (discriminator, :1080): loss = -log(clip(1 - |label - out|, 1e-8, 1 - 1e-8))
@@ -102,18 +105,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ param, co
     m[i] = mi;
     v[i] = vi;
     param[i] -= lr_t * mi / (sqrtf(vi) + eps);
-}
-
-__device__ __forceinline__ int reflect(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-__device__ __forceinline__ float4 fma4s(float4 a, float s, float4 c) {
-    return make_float4(fmaf(a.x, s, c.x), fmaf(a.y, s, c.y), fmaf(a.z, s, c.z), fmaf(a.w, s, c.w));
 }
 
 // ---- reflect-padded depthwise 3x3 (tf.pad REFLECT 1 + VALID, stride 1 or 2), backward.

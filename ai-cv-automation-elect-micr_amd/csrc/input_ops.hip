@@ -16,8 +16,11 @@
 
 #include "emd_common.hpp"
 #include "philox.hpp"
+#include "wave_reduce.hpp"
 
 namespace {
+
+using namespace emd;
 
 // stream tags (counter word 3): independent sequences under one seed (philox.hpp lists every tag of the library)
 constexpr unsigned kTagRaw = emd::kPhiloxTagRaw, kTagScale = emd::kPhiloxTagScale, kTagChoice = emd::kPhiloxTagChoice,
@@ -102,16 +105,6 @@ __global__ void __launch_bounds__(256) flip_rotate_kernel(const float* __restric
 }
 
 // ---- per-image min / max (scale0to1, :817-828).  min and max are exact and order-independent.
-__device__ inline float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 
 // grid (slabs, B); partial[b][slab] = {min, max}; NaNs are ignored by fminf/fmaxf (the reference replaces them first)
 __global__ void __launch_bounds__(256) minmax_partial_kernel(const float* __restrict__ x, long npix, float2* __restrict__ part) {

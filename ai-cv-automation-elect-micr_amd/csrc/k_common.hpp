@@ -6,8 +6,12 @@
 #include <cmath>
 
 #include "emd_common.hpp"
+#include "f4_math.hpp"
+#include "wave_reduce.hpp"
 
 namespace {
+
+using namespace emd;
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kThreads = 256, kWaves = kThreads / 64, kPx = 4, kChunk = kThreads * kPx;
@@ -19,19 +23,8 @@ constexpr int kUpdThreads = 1024;
 inline int nsym_of(int width) { return (width / 2 + 1) * (width / 2 + 2) / 2; }
 inline int nscal_of(int width, int depth) { return (2 * depth - 1) * nsym_of(width) + depth - 1; }
 
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
-
 __device__ __forceinline__ float sigm(float z) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-kLog2e * z));
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // class of tap (i, j) of a width-w map: the creation index of (max(|i-o|,|j-o|), min(..)) in make_layer's order

@@ -17,15 +17,13 @@
 //     MODE_LIN  (depth 1): plain 3x3 correlation.
 // k_generic        any odd width <= 15, depth <= 5, any H,W: one thread per pixel.
 #include "emd_common.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
+using namespace emd;
 
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    i = i < 0 ? -i : i;
-    return i >= n ? 2 * n - 2 - i : i;
-}
+constexpr float kLog2e = 1.4426950408889634f;
 
 // a / (1 + 2^(p*ws + bs))  ==  a * sigmoid(w*p + b)  with ws = -w*log2(e), bs = -b*log2(e)
 __device__ __forceinline__ float sig_term(float p, float ws, float bs, float a) {
@@ -51,9 +49,9 @@ __global__ __launch_bounds__(256) void k_generic(const float* __restrict__ x, fl
         const float* img = x + (t / H) * (long)H * W;
         float acc = 0.f;
         for (int i = 0; i < width; ++i) {
-            const int rr = reflect_idx(r + i - p, H);
+            const int rr = reflect(r + i - p, H);
             for (int j = 0; j < width; ++j) {
-                const int cc = reflect_idx(c + j - p, W);
+                const int cc = reflect(c + j - p, W);
                 const int k = i * width + j;
                 float f = wm[k] * img[(long)rr * W + cc];
                 for (int l = 1; l < depth; ++l) {
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(256) void k3_rows(const float* __restrict__ x, floa
     float s0[kPx], s1[kPx];
 #pragma unroll
     for (int t = 0; t < R + 2; ++t) {
-        int rr = reflect_idx(r0 - 1 + t, H);
+        int rr = reflect(r0 - 1 + t, H);
         rr = rr < 0 ? 0 : (rr >= H ? H - 1 : rr);  // rows past a ragged last strip: any valid row
         const float* row = img + (long)rr * W;
         float p[kPx + 2];
@@ -223,7 +221,6 @@ int launch_k3(const float* x, float* y, int B, int H, int W, int depth, const fl
     return emd::check_launch("k3_rows");
 }
 
-
 // ------------------------------------------------------------------------------------------------
 // k3_tile<R,NW>  (D4-symmetric maps, depth 2 -- the reference's configuration).
 // Built for thread-level parallelism: a wave owns only R rows x 512 pixels, so a batch is tens of
@@ -268,7 +265,7 @@ __global__ __launch_bounds__(NW * 64) void k3_tile(const float* __restrict__ x, 
 
     struct Raw { float4 g[2]; float ext; };
     auto load_row = [&](int r, Raw& p) {
-        int rr = reflect_idx(r, H);
+        int rr = reflect(r, H);
         rr = rr < 0 ? 0 : (rr >= H ? H - 1 : rr);
         const float* row = img + rr * W;
         p.g[0] = p.g[1] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -414,7 +411,7 @@ __global__ __launch_bounds__(NW * 64) void k3_roll(const float* __restrict__ x, 
 
     struct Raw { float4 g[2]; float ext; };
     auto load_row = [&](int r, Raw& p) {
-        int rr = reflect_idx(r, H);
+        int rr = reflect(r, H);
         rr = rr < 0 ? 0 : (rr >= H ? H - 1 : rr);
         const float* row = img + rr * W;
         p.g[0] = p.g[1] = make_float4(0.f, 0.f, 0.f, 0.f);

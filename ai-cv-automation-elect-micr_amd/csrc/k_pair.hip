@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kThreads) void k_pair_grad_kernel(const float* __re
     // input element under tap (i, j) of output pixel (r, c): VALID rows r .. r + w - 1 are all inside the image
     auto tap_at = [&](int r, int c, int i, int j) -> long {
         if constexpr (kValid) return (long)(r + i) * W + (c + j);
-        else return (long)reflect_idx(r + i - o, H) * W + reflect_idx(c + j - o, W);
+        else return (long)reflect(r + i - o, H) * W + reflect(c + j - o, W);
     };
 
     for (long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {

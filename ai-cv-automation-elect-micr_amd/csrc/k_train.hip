@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kThreads) void k_grad_kernel(const float* __restric
                 }
 #pragma unroll
                 for (int q = 0; q < kPx; ++q) {
-                    const int rr = reflect_idx((pr[q] < 0 ? 0 : pr[q]) + i - o, H), cc = reflect_idx(pc[q] + j - o, W);
+                    const int rr = reflect((pr[q] < 0 ? 0 : pr[q]) + i - o, H), cc = reflect(pc[q] + j - o, W);
                     float f = wl[0] * img[q][(long)rr * W + cc];
 #pragma unroll
                     for (int l = 1; l < D; ++l) f = wl[l] * (sl[l] * sigm(f + bl[l]));
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void k_grad_kernel(const float* __restric
                 }
 #pragma unroll
                 for (int q = 0; q < kPx; ++q) {
-                    const int rr = reflect_idx((pr[q] < 0 ? 0 : pr[q]) + i - o, H), cc = reflect_idx(pc[q] + j - o, W);
+                    const int rr = reflect((pr[q] < 0 ? 0 : pr[q]) + i - o, H), cc = reflect(pc[q] + j - o, W);
                     const float v = img[q][(long)rr * W + cc];
                     float g[D];
                     float f = wl[0] * v;
@@ -248,7 +248,6 @@ __global__ __launch_bounds__(kThreads) void k_sample_kernel(const float* __restr
         for (int k = tid; k < np_; k += kThreads) x4[((size_t)b * np_ + k) * 4] = out[k];
 }
 
-
 // ---- (c) the fused small-batch form: one workgroup per filter runs `nsteps` complete steps in one launch ----------------
 // Per step: the batch is sampled into LDS (one wave per crop; the arithmetic of k_sample_kernel with wave-level reductions,
 // so the mean can differ from emd_k_sample_crops_f32's in the last bit) or copied from the caller's fixed batches; forward +
@@ -261,12 +260,6 @@ constexpr int kMaxFusedJobs = 32;
 struct FusedArgs {
     emd_k_fused_job_t job[kMaxFusedJobs];
 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // crop b of the batch drawn for crop index `idx`, by one wave, into dst[crop*crop]
 __device__ void sample_crop_wave(const float* __restrict__ stack, int N, int H, int W, int crop, unsigned long long seed,
@@ -305,7 +298,7 @@ __device__ void sample_crop_wave(const float* __restrict__ stack, int N, int H, 
         dst[k] = v;
         s += (double)v;
     }
-    const float mean = (float)(wave_sum_d(s) / (double)np_);
+    const float mean = (float)(wave_sum(s) / (double)np_);
     int bad = 0;
     for (int k = lane; k < np_; k += 64) {
         const float v = dst[k] / mean;
@@ -385,7 +378,7 @@ __global__ __launch_bounds__(kFThreads) void k_fused_kernel(FusedArgs args, cons
                     }
 #pragma unroll
                     for (int q = 0; q < kPx; ++q) {
-                        const int rr = reflect_idx((pr[q] < 0 ? 0 : pr[q]) + i - o, S), cc = reflect_idx(pc[q] + j - o, S);
+                        const int rr = reflect((pr[q] < 0 ? 0 : pr[q]) + i - o, S), cc = reflect(pc[q] + j - o, S);
                         float f = wl[0] * img[pb[q] * SS + rr * S + cc];
 #pragma unroll
                         for (int l = 1; l < D; ++l) f = wl[l] * (sl[l] * sigm(f + bl[l]));
@@ -412,7 +405,7 @@ __global__ __launch_bounds__(kFThreads) void k_fused_kernel(FusedArgs args, cons
                     }
 #pragma unroll
                     for (int q = 0; q < kPx; ++q) {
-                        const int rr = reflect_idx((pr[q] < 0 ? 0 : pr[q]) + i - o, S), cc = reflect_idx(pc[q] + j - o, S);
+                        const int rr = reflect((pr[q] < 0 ? 0 : pr[q]) + i - o, S), cc = reflect(pc[q] + j - o, S);
                         const float v = img[pb[q] * SS + rr * S + cc];
                         float g[D];
                         float f = wl[0] * v;

@@ -1,27 +1,10 @@
 // Shared device helpers of the matrix-core kernels (gemm_conv.hip, sep_fused.hip).
 #pragma once
 
+#include "dev_prims.hpp"
 #include "emd_common.hpp"
 
 namespace emd {
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;      // native vectors for the staging registers:
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // HIP's float4/uint4 structs end up in scratch
-
-// 16-byte global store with the non-temporal hint.  Inline asm on purpose: behind a run-time flag, "if (nt) __builtin_nontemporal_store
-// else plain store" is merged into ONE plain store by the optimizer (the merged store keeps only the metadata both sides share).
-// The s_nop covers the store-data hazard the compiler cannot see inside the asm.
-__device__ __forceinline__ void store_nt16(void* dst, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 3" ::"v"(dst), "v"(v) : "memory");
-}
-__device__ __forceinline__ void store_nt16(void* dst, u32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 3" ::"v"(dst), "v"(v) : "memory");
-}
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr int kBK = 64;       // channel padding unit of the packed weights (and the GEMM's K step)
 constexpr int kNPadTo = 128;  // packed weights are padded to a multiple of the widest BN
@@ -48,12 +31,6 @@ __device__ __forceinline__ void split2(float a0, float a1, unsigned& hi, unsigne
     const bf16x2 l = __builtin_convertvector(r, bf16x2);
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, l);
-}
-
-// The value of the other lane of an (even, odd) lane pair: a DPP quad permute [1,0,3,2] -- what __shfl_xor(v, 1) returns, without
-// the trip through the LDS crossbar (ds_bpermute) that the HIP shuffle compiles to.
-__device__ __forceinline__ unsigned swap_pair(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
 }
 
 // Output stage of the depthwise kernels.  SPLIT = false: 4 fp32 channels at y + pix*ldy + 4*c4.  SPLIT = true: the

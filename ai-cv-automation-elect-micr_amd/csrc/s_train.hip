@@ -13,16 +13,14 @@
 // tile's sum of (out - x)^2); s_head_reduce1/2_kernel sum the slabs in a fixed order in double, in two levels.  No atomics: the same inputs give the
 // same bits.
 #include "emd_common.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
+using namespace emd;
+
 constexpr int kTH = 8, kTW = 32, kThreads = 256;
 constexpr int kHaloW = kTW + 2, kHalo = (kTH + 2) * kHaloW;
-
-__device__ __forceinline__ float4 fma4s(float4 a, float s, float4 c) {
-    return make_float4(fmaf(a.x, s, c.x), fmaf(a.y, s, c.y), fmaf(a.z, s, c.z), fmaf(a.w, s, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 // slab of one workgroup: [9][C] weight-gradient sums, [C] bias sums, then the sum of (out - x)^2; stride slab_stride(C) floats
 __host__ __device__ inline int slab_stride(int C) { return 10 * C + 4; }

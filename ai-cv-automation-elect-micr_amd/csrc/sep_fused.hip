@@ -76,14 +76,7 @@ __global__ __launch_bounds__(256, 2) void sep_fused_kernel(const SepParams p) {
     // Workgroups are handed to the 8 XCDs round-robin (id mod 8), so in launch order the tile under this one -- which shares two of
     // its ten patch rows -- runs on another XCD and the halo is fetched once per L2.  p.xcd: XCD k takes the k-th eighth of the tiles.
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (p.xcd) {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;   // a multiple of 8 (host check)
-        const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned t = (id & 7) * (total >> 3) + (id >> 3);
-        bx = t % gridDim.x;
-        by = (t / gridDim.x) % gridDim.y;
-        bz = t / (gridDim.x * gridDim.y);
-    }
+    xcd_remap(p.xcd, bx, by, bz);   // the tile count is a multiple of 8 (host check)
     const int xbase = bx * p.tpw * TW, y0 = by * TH;
     int x0 = xbase;       // tile whose chunks are being computed (the epilogue's tile)
     const long img = (long)bz * p.H * p.W;  // pixel index of this image's (0,0)

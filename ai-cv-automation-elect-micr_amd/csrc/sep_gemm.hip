@@ -32,9 +32,6 @@ using namespace emd;
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 __device__ __attribute__((aligned(128))) unsigned char g_sg_zero[4096];
 
 struct SepGemmParams {

@@ -31,12 +31,11 @@
 // 512^2 x 128 -> 64 layer, slower on every shape.  profiles/r03_experiments.txt.)
 // vmcnt bookkeeping is exact for full tiles (every wave issues the same number of DMA pieces per step and, per tile, a fixed number
 // of stores), conservative otherwise.
-#include "sep_pipe_common.hpp"
+#include "sep_params.hpp"
 
 namespace {
 
 using namespace emd;
-using namespace emd::sp;
 
 // source of the zero-padding pixels (TF SAME) and of the unused slots: 16 KB, so that "+ chunk offset" stays inside for Cin <= 4064
 __device__ __attribute__((aligned(16))) float g_zero_pipe[4096];
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv / WN, wn = wv % WN;
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (p.xcd) {   // XCD k (workgroup id mod 8) takes the k-th contiguous eighth of the tile list: halo rows meet in one L2
+    if (p.xcd) {   // xcd_remap (dev_prims.hpp) written out: through the helper this kernel's registers are allocated differently
         const unsigned total = gridDim.x * gridDim.y * gridDim.z;
         const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
         const unsigned t = (id & 7) * (total >> 3) + (id >> 3);

@@ -30,12 +30,11 @@
 // Patch swizzle: 16-byte chunk c of patch pixel column px is stored at c ^ ((px >> 1) & 7) (applied to the DMA's source address): the
 // depthwise stage's 8-byte reads (a 32-lane group = 2 rows x pixel groups {g, g + 2} x 8 channel pairs), and the projection's 16-byte
 // centre reads (16 consecutive pixels of a row) then cover the 64 banks evenly.  A / B rows (64 B): chunk ^ ((row >> 2) & 3).
-#include "sep_pipe_common.hpp"
+#include "sep_params.hpp"
 
 namespace {
 
 using namespace emd;
-using namespace emd::sp;
 
 // source of the zero-padding pixels (TF SAME) and of the unused slots: 16 KB, so that "+ chunk offset" stays inside for Cin <= 4064
 __device__ __attribute__((aligned(16))) float g_zero_pipe2[4096];
@@ -75,14 +74,7 @@ __global__ __launch_bounds__(512, 2) void sep_pipe2_kernel(const SepParams p) {
     }
     const bool out2 = DUAL && wv >= 4;
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    if (p.xcd) {   // XCD k (workgroup id mod 8) takes the k-th contiguous eighth of the tile list: halo rows meet in one L2
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned t = (id & 7) * (total >> 3) + (id >> 3);
-        bx = t % gridDim.x;
-        by = (t / gridDim.x) % gridDim.y;
-        bz = t / (gridDim.x * gridDim.y);
-    }
+    xcd_remap(p.xcd, bx, by, bz);   // halo rows meet in one L2
     const int xbase = bx * p.tpw * TW, y0 = by * TH;
     const int Wo = p.W;
     const long img = (long)bz * p.H * p.W;

@@ -61,8 +61,8 @@ __device__ __forceinline__ void roll_rows(const Taps& taps, HFn&& hrow, OFn&& or
     }
 }
 
-// Sum of one double per lane over the wave, in a fixed order.
-__device__ __forceinline__ double wave_sum(double v) {
+// Sum of one double per lane over the wave, in a fixed order; the result is valid in lane 0 only (emd::wave_sum is the butterfly).
+__device__ __forceinline__ double wave_sum_lane0(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
                 }
             });
     }
-    const double ws = wave_sum((double)sum_s), wc = wave_sum((double)sum_c);
+    const double ws = wave_sum_lane0((double)sum_s), wc = wave_sum_lane0((double)sum_c);
     if (lane == 0) {
         red[2 * wave] = ws;
         red[2 * wave + 1] = wc;
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256) void sqdiff_images_kernel(const float* __restr
         const float d = xb[i] - yb[i];
         s += (double)d * (double)d;
     }
-    s = wave_sum(s);
+    s = wave_sum_lane0(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];

@@ -11,12 +11,15 @@
 // sums them in a fixed order, so every result is deterministic.  The tile plan is the caller's (tiling.py): kernels read it,
 // never recompute it, and index with REFLECT folding so that any plan content stays inside the image.
 #include "emd_common.hpp"
+#include "wave_reduce.hpp"
 
 #include <cmath>
 
 #pragma clang fp contract(off)  // every float operation rounds where numpy's does (no fused multiply-adds)
 
 namespace {
+
+using namespace emd;
 
 constexpr int kThreads = 256;
 
@@ -31,7 +34,7 @@ struct ImgStat {  // per image, between the launches of one emd_tile_prep_f32 ca
 };
 
 // numpy's mode="reflect" (no edge repeat) for any offset: the periodic mirror of period 2(n-1)
-__device__ inline int reflect_idx(int i, int n) {
+__device__ inline int reflect_idx_periodic(int i, int n) {
     if (n == 1) return 0;
     const int p = 2 * (n - 1);
     i %= p;
@@ -47,28 +50,6 @@ __device__ inline int pad_weight(int r, int n, int p) {
 __device__ inline float fix0(float v) { return isfinite(v) ? v : 0.f; }
 // scale0to1 of one pixel with numpy's rounding: (x - lo) / (hi - lo); lo == hi -> 0.5; NaN lo / hi -> NaN
 __device__ inline float s01(float v, float lo, float hi) { return lo == hi ? 0.5f : (v - lo) / (hi - lo); }
-
-template <typename T>
-__device__ inline T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ inline float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ inline int wave_or(int v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v |= __shfl_xor(v, o);
-    return v;
-}
 
 // (sum, min, max, nan) of a block of NW waves, in a fixed order; the result is valid in thread 0
 template <int NW>
@@ -258,7 +239,7 @@ __global__ void __launch_bounds__(kThreads) gather_copy_kernel(const float* __re
     const int rows = min(kCopyRows, cs - a0);
     for (int e = threadIdx.x; e < rows * cs; e += kThreads) {
         const int a = a0 + e / cs, b = e % cs;
-        o[(long)a * cs + b] = s[(long)reflect_idx(y0 + a, H) * W + reflect_idx(x0 + b, W)];
+        o[(long)a * cs + b] = s[(long)reflect_idx_periodic(y0 + a, H) * W + reflect_idx_periodic(x0 + b, W)];
     }
 }
 
@@ -282,7 +263,7 @@ __global__ void __launch_bounds__(kRescaleThreads) gather_rescale_kernel(const f
 #pragma unroll 4
     for (int e = threadIdx.x; e < npc; e += kRescaleThreads) {
         const int a = e / cs, b = e - a * cs;
-        const float v = s[(long)reflect_idx(y0 + a, H) * W + reflect_idx(x0 + b, W)];
+        const float v = s[(long)reflect_idx_periodic(y0 + a, H) * W + reflect_idx_periodic(x0 + b, W)];
         sum += (double)v;
         mn = fminf(mn, v);
         nan |= (v != v);
@@ -301,7 +282,7 @@ __global__ void __launch_bounds__(kRescaleThreads) gather_rescale_kernel(const f
 #pragma unroll 4
     for (int e = threadIdx.x; e < npc; e += kRescaleThreads) {
         const int a = e / cs, b = e - a * cs;
-        const float v = s[(long)reflect_idx(y0 + a, H) * W + reflect_idx(x0 + b, W)];
+        const float v = s[(long)reflect_idx_periodic(y0 + a, H) * W + reflect_idx_periodic(x0 + b, W)];
         o[e] = scale == 0.f ? 1.f : (v - off) / scale;
     }
 }

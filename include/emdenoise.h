@@ -378,7 +378,7 @@ int emd_conv1x1_split32_stats_fold_f32(const void* xs, int ldx, const uint16_t* 
                                        float* var, void* workspace, const float* gamma, const float* beta, float eps,
                                        float* scale, float* shift, emd_stream_t stream);
 /* Dense 3x3 convolution (emd_conv3x3_f32: TF SAME, stride 1/2, dilation) and the 3x3 stride-2 transposed convolution
- * (emd_deconv3x3s2_f32) on a split32 input, same packed weights, same arithmetic (bit-identical results); out_split != 0
+ * (emd_deconv3x3s2_f32) on a split32 input (csrc/conv_split.hip), same packed weights, same arithmetic (bit-identical results); out_split != 0
  * writes y itself as a split32 tensor (pitch ldy 4-byte units, % 32; channels Cout..ceil32(Cout) zero) for a following
  * split32 convolution -- tf.layers.conv2d / conv2d_transpose chains (misc_py/modified_Xception.py:215-229, :538-621;
  * machine_learning/denoiser.py:141-148) then never write an fp32 activation.  Cin <= 2048. */
