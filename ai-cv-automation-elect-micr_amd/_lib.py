@@ -402,6 +402,23 @@ SIGNATURES = {
     "emd_psnr_workspace_bytes": (C.c_size_t, [C.c_int, C.c_long]),
     # x y B npix data_range out workspace ws_bytes stream
     "emd_psnr_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_float, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- classical baseline filters (csrc/filters.hip)
+    # x out B H W taps_host ksize stream
+    "emd_filter_gaussian_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    # x out B H W ksize stream
+    "emd_filter_median_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # x out B H W d sigma_color sigma_space stream
+    "emd_filter_bilateral_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                           C.c_void_p]),
+    "emd_filter_wiener_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x out B H W ksize noise noise_out workspace ws_bytes stream
+    "emd_filter_wiener_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _c_float_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_filter_tv_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x out B H W weight n_iter workspace ws_bytes stream
+    "emd_filter_tv_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "emd_filter_clip01_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_long, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

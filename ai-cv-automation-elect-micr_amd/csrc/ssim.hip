@@ -14,59 +14,18 @@
 //
 // Images are single-channel and W-contiguous: a lane is a column.  No atomics anywhere: every result is bitwise
 // reproducible run to run.
-#include "emd_common.hpp"
+#include "stencil_rows.hpp"
 
 namespace {
 
-constexpr int kMaxSize = 15;   // widest window
 constexpr int kTW = 64;        // tile columns = lanes of a wave
 constexpr int kWaves = 4;      // a wave owns a strip of rows of the tile
 constexpr int kLW = 80;        // LDS row stride in floats: kTW + kMaxSize - 1 = 78, rounded up to whole float4s
 constexpr int kFwdSH = 16;     // rows per strip: forward (two planes in LDS)
 constexpr int kGradSH = 12;    // ... gradient (three planes in LDS)
 
-struct Taps {
-    float g[kMaxSize];
-};
-
 constexpr float kC1 = 0.01f * 0.01f;   // (K1 L)^2, L = 1 (:144-148)
 constexpr float kC2 = 0.03f * 0.03f;
-
-// Vertical 1-D pass over a strip of SH output rows of one column, without a second LDS buffer: hrow(i, v) yields the NC
-// horizontally filtered values of strip row i (0 <= i < SH + S - 1); they go round a ring of S rows held in registers
-// (the row loop is unrolled S times, so every ring index is a compile-time constant), and orow(o, v) receives output row o.
-template <int S, int SH, int NC, class HFn, class OFn>
-__device__ __forceinline__ void roll_rows(const Taps& taps, HFn&& hrow, OFn&& orow) {
-    constexpr int NR = SH + S - 1;
-    float ring[S][NC];
-    for (int base = 0; base < NR; base += S) {
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            const int i = base + j;
-            if (i < NR) {
-                hrow(i, ring[j]);
-                if (i >= S - 1) {
-                    float v[NC];
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) v[c] = 0.f;
-#pragma unroll
-                    for (int k = 0; k < S; ++k) {
-#pragma unroll
-                        for (int c = 0; c < NC; ++c) v[c] = fmaf(taps.g[k], ring[(j + 1 + k) % S][c], v[c]);
-                    }
-                    orow(i - (S - 1), v);
-                }
-            }
-        }
-    }
-}
-
-// Sum of one double per lane over the wave, in a fixed order; the result is valid in lane 0 only (emd::wave_sum is the butterfly).
-__device__ __forceinline__ double wave_sum_lane0(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // Forward: grid (tiles per image, B).  part[(b * tiles + tile) * 2 + {0, 1}] = sums of ssim_map / cs_map over the tile.
 // G != NULL: the planes Ga, Gb, Gc (d map / d mu1, d E[xx], d E[xy], times neg_inv_n) at G + {0, 1, 2} * plane.
@@ -177,21 +136,6 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
         p[0] = a;
         p[1] = c;
     }
-}
-
-// Sum of p[0], p[stride], ..., p[(n - 1) * stride] by the 256 threads of a workgroup, in a fixed order (every thread returns it).
-__device__ double block_sum_fixed(const double* __restrict__ p, int n, int stride, double* sh) {
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int i = tid; i < n; i += 256) s += p[(long)i * stride];
-    __syncthreads();   // sh may still be read from the previous call
-    sh[tid] = s;
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-        if (tid < off) sh[tid] += sh[tid + off];
-        __syncthreads();
-    }
-    return sh[0];
 }
 
 // grid (B): sums[b * NC + c] = scale * (sum over the n partial sums of component c of image b), in a fixed order

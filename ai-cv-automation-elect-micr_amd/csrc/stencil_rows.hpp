@@ -1,0 +1,66 @@
+// What the single-channel image stencils share (ssim.hip: the metrics; filters.hip: the classical filters): the window taps as a
+// kernel argument, the vertical 1-D pass on a register ring, and the fixed-order sums.  One definition of each.
+#pragma once
+
+#include "emd_common.hpp"
+
+namespace {
+
+constexpr int kMaxSize = 15;   // widest window
+
+struct Taps {
+    float g[kMaxSize];
+};
+
+// Vertical 1-D pass over a strip of SH output rows of one column, without a second LDS buffer: hrow(i, v) yields the NC
+// horizontally filtered values of strip row i (0 <= i < SH + S - 1); they go round a ring of S rows held in registers
+// (the row loop is unrolled S times, so every ring index is a compile-time constant), and orow(o, v) receives output row o.
+template <int S, int SH, int NC, class HFn, class OFn>
+__device__ __forceinline__ void roll_rows(const Taps& taps, HFn&& hrow, OFn&& orow) {
+    constexpr int NR = SH + S - 1;
+    float ring[S][NC];
+    for (int base = 0; base < NR; base += S) {
+#pragma unroll
+        for (int j = 0; j < S; ++j) {
+            const int i = base + j;
+            if (i < NR) {
+                hrow(i, ring[j]);
+                if (i >= S - 1) {
+                    float v[NC];
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) v[c] = 0.f;
+#pragma unroll
+                    for (int k = 0; k < S; ++k) {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) v[c] = fmaf(taps.g[k], ring[(j + 1 + k) % S][c], v[c]);
+                    }
+                    orow(i - (S - 1), v);
+                }
+            }
+        }
+    }
+}
+
+// Sum of one double per lane over the wave, in a fixed order; the result is valid in lane 0 only (emd::wave_sum is the butterfly).
+__device__ __forceinline__ double wave_sum_lane0(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// Sum of p[0], p[stride], ..., p[(n - 1) * stride] by the 256 threads of a workgroup, in a fixed order (every thread returns it).
+__device__ double block_sum_fixed(const double* __restrict__ p, int n, int stride, double* sh) {
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int i = tid; i < n; i += 256) s += p[(long)i * stride];
+    __syncthreads();   // sh may still be read from the previous call
+    sh[tid] = s;
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+        if (tid < off) sh[tid] += sh[tid + off];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+}  // namespace

@@ -1029,6 +1029,44 @@ int emd_psnr_f32(const float* x, const float* y, int B, long npix, float data_ra
                  size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Classical baseline filters (csrc/filters.hip): the methods of the reference's comparison table,
+ * misc_py/err_hist_maker.py:26-45 (Gaussian, Bilateral, Median, Wiener, Chambolle; "Wavelet" is not built), and the ground-truth
+ * blur of misc_py/blur_images.py:13 (cv2.GaussianBlur(img, (3,3), 1.5) = the Gaussian with ksize 3, sigma 1.5).
+ *
+ * x, out : [B,H,W] float32 (NHWC with C == 1), contiguous, finite; 0 <= B <= 65535 (B == 0 is a no-op); every image of the
+ *          batch is filtered on its own.  out may NOT alias or overlap x in any of the five filters: a tile reads the pixels
+ *          of its neighbours (the total-variation iteration re-reads x with a halo in every launch, the last one included).
+ * "Mirror" border: reflect-101, d c b | a b c d | c b a (cv2's default, tf.pad REFLECT, graph K's); needs radius < min(H,W).
+ * Workspaces are the caller's, 16-byte aligned, sized by the emd_*_workspace_bytes of the same arguments (0 for arguments the
+ * routine would refuse).  No atomics: every result is bitwise reproducible.  All arguments are checked before any launch. */
+/* Separable correlation with the 1-D taps taps_host (HOST array of ksize floats; ksize odd, 3..15), mirror border. */
+int emd_filter_gaussian_f32(const float* x, float* out, int B, int H, int W, const float* taps_host, int ksize, emd_stream_t stream);
+/* Median of the ksize x ksize window, ksize 3 or 5, mirror border: one of the input values, bit for bit. */
+int emd_filter_median_f32(const float* x, float* out, int B, int H, int W, int ksize, emd_stream_t stream);
+/* out[p] = sum_q w x[q] / sum_q w over the taps q = p + (dx, dy) with dx^2 + dy^2 <= (d/2)^2 (cv2's circular support),
+ * w = exp(-(dx^2 + dy^2) / (2 sigma_space^2)) exp(-(x[q] - x[p])^2 / (2 sigma_color^2)); d odd, 3..9; mirror border. */
+int emd_filter_bilateral_f32(const float* x, float* out, int B, int H, int W, int d, float sigma_color, float sigma_space,
+                             emd_stream_t stream);
+size_t emd_filter_wiener_workspace_bytes(int B, int H, int W);
+/* scipy.signal.wiener: m, v = mean and variance of the ksize x ksize window of the ZERO-padded image (divided by ksize^2 at the
+ * border too); out = m + (x - m) (1 - n / v) where v >= n and v > 0, else m (scipy's 0 / 0 on a constant image: here m).
+ * ksize odd, 3..9.  noise >= 0: n = noise, one launch, the workspace is not used (may be NULL).  noise < 0: n of each image
+ * = the mean of its own v, two launches.  noise_out (optional, [B]) receives the n used. */
+int emd_filter_wiener_f32(const float* x, float* out, int B, int H, int W, int ksize, float noise, float* noise_out, void* workspace,
+                          size_t workspace_bytes, emd_stream_t stream);
+size_t emd_filter_tv_workspace_bytes(int B, int H, int W);
+/* Chambolle's dual projection for total-variation denoising, a FIXED number of iterations (no stopping rule: capturable):
+ * p = 0; n_iter times: u = x + div p, div p [i,j] = -p1[i,j] - p2[i,j] + p1[i-1,j] + p2[i,j-1] (0 outside the image);
+ * g1 = u[i+1,j] - u[i,j] (0 on the last row), g2 = u[i,j+1] - u[i,j] (0 on the last column);
+ * p <- (p - tau g) / (1 + (tau / weight) sqrt(g1^2 + g2^2)), tau = 0.25.  out = the last u (n_iter == 1: x).  weight > 0,
+ * n_iter >= 1; one launch per iteration. */
+int emd_filter_tv_f32(const float* x, float* out, int B, int H, int W, float weight, int n_iter, void* workspace,
+                      size_t workspace_bytes, emd_stream_t stream);
+/* out = min(max(x, 0), 1) over n floats (the comparison table's optional clip before scoring).  Element-wise: here, and only
+ * here, out may be x itself (in place); a partial overlap is refused. */
+int emd_filter_clip01_f32(const float* x, float* out, long n, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
