@@ -419,6 +419,20 @@ SIGNATURES = {
     "emd_filter_tv_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_size_t,
                                     C.c_void_p]),
     "emd_filter_clip01_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_long, C.c_void_p]),
+    # ---- wavelet transform and wavelet shrinkage (csrc/wavelet.hip)
+    # H W ntaps levels bands
+    "emd_wavelet_pyramid_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "emd_wavelet_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # x pyramid B H W rec_lo_host ntaps levels workspace ws_bytes stream
+    "emd_wavelet_forward_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]),
+    # pyramid out B H W rec_lo_host ntaps levels workspace ws_bytes stream
+    "emd_wavelet_inverse_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_size_t, C.c_void_p]),
+    "emd_filter_wavelet_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # x out B H W rec_lo_host ntaps levels method sigma sigma_used workspace ws_bytes stream
+    "emd_filter_wavelet_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

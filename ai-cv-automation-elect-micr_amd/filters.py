@@ -5,7 +5,11 @@ reference's evaluation compares its networks with (misc_py/err_hist_maker.py:26-
 Images are float32 ``[B,H,W,1]`` (or ``[B,H,W]`` / ``[H,W]``); every image of a batch is filtered on its own.  numpy in -> numpy
 out; torch CUDA tensor in -> device tensor of the same shape out, on the current stream, with no host synchronisation (the
 conventions of ``emdenoise.metrics``).  Python here only shapes buffers: every number comes from a HIP kernel.  "Mirror" border
-= reflect-101 (cv2's default), which needs the window radius < min(H, W)."""
+= reflect-101 (cv2's default), which needs the window radius < min(H, W).
+
+``wavedec2`` / ``waverec2`` / ``denoise_wavelet`` (csrc/wavelet.hip) are the 2-D orthogonal wavelet transform with
+the half-sample symmetric border and the reference table's "Wavelet" method, built as ``skimage.restoration.denoise_wavelet``'s
+arithmetic at its defaults from the formulas in include/emdenoise.h (neither skimage nor pywt is used)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +20,8 @@ from . import _lib, metrics
 from .metrics import _dims, _images, _p, _ws, gaussian_taps
 
 LABELS = ["Unfiltered", "Gaussian", "Bilateral", "Median", "Wiener", "Chambolle"]   # err_hist_maker.py:27 without "Wavelet"
+REFERENCE_LABELS = ["Unfiltered", "Gaussian", "Bilateral", "Median", "Wiener", "Wavelet", "Chambolle"]   # err_hist_maker.py:27
+WAVELET_METHODS = {"BayesShrink": 0, "VisuShrink": 1}                               # EMD_WAVELET_BAYES, EMD_WAVELET_VISU
 
 
 def _shaped(y, like, as_np):
@@ -128,6 +134,151 @@ def tv_chambolle(x, weight=0.1, n_iter=50):
     return _shaped(out, x, as_np)
 
 
+# ---- wavelets (csrc/wavelet.hip) ---------------------------------------------------------------------------------------------
+
+def wavelet_taps(wavelet):
+    """Reconstruction low-pass taps rec_lo (float64, even count, 2..8) of a named wavelet ("haar" = "db1", "db2") or of an array
+    holding the taps of any other orthogonal filter; the other three filters follow from them (include/emdenoise.h)."""
+    if isinstance(wavelet, str):
+        if wavelet in ("haar", "db1"):
+            return np.array([1.0, 1.0]) / np.sqrt(2.0)
+        if wavelet == "db2":
+            s3 = np.sqrt(3.0)
+            return np.array([1.0 + s3, 3.0 + s3, 3.0 - s3, 1.0 - s3]) / (4.0 * np.sqrt(2.0))
+        raise ValueError(f"wavelet: unknown name {wavelet!r} (\"haar\", \"db1\", \"db2\", or an array of reconstruction low-pass taps)")
+    taps = np.ascontiguousarray(wavelet, dtype=np.float64)
+    if taps.ndim != 1 or taps.size < 2 or taps.size > 8 or taps.size % 2:
+        raise ValueError(f"wavelet: the tap count must be even, 2..8 (got shape {taps.shape})")
+    if not np.isfinite(taps).all():
+        raise ValueError("wavelet: the taps must be finite")
+    return taps
+
+
+def wavelet_max_levels(H, W, ntaps):
+    """floor(log2(min(H, W) / (ntaps - 1))): the deepest decomposition allowed (< 1: the image is too small for the filter)."""
+    k = -1
+    while (ntaps - 1) * 2 ** (k + 1) <= min(H, W):
+        k += 1
+    return k
+
+
+def _wavelet_args(name, wavelet, levels, H, W):
+    """(taps, levels) checked on the shape alone, before anything is moved to the device; levels=None is skimage's rule."""
+    taps = wavelet_taps(wavelet)
+    top = wavelet_max_levels(H, W, taps.size)
+    if top < 1 or max(H, W) > 32768:
+        raise ValueError(f"{name}: an image of {H} x {W} allows no level of a {taps.size}-tap wavelet (needs min(H, W) >= "
+                         f"{2 * (taps.size - 1)}, H, W <= 32768)")
+    if levels is None:
+        return taps, max(top - 3, 1)
+    if int(levels) != levels or not 1 <= levels <= top:
+        raise ValueError(f"{name}: levels must be 1..{top} for an image of {H} x {W} and {taps.size} taps (got {levels})")
+    return taps, int(levels)
+
+
+def _layout(H, W, ntaps, levels):
+    """(floats per image, [(offset, rows, cols)] of cA_n, ad_n, da_n, dd_n, ..., dd_1) from the library."""
+    bands = (C.c_long * (3 * (1 + 3 * levels)))()
+    total = _lib.load().emd_wavelet_pyramid_floats(H, W, ntaps, levels, bands)
+    if not total:
+        raise ValueError(f"wavelet: no pyramid for an image of {H} x {W}, {ntaps} taps, {levels} levels")
+    return int(total), [tuple(bands[3 * i:3 * i + 3]) for i in range(1 + 3 * levels)]
+
+
+def _taps_p(taps):
+    return taps.ctypes.data_as(C.c_void_p)
+
+
+def wavedec2(x, wavelet="db1", levels=None):
+    """2-D wavelet decomposition with the half-sample symmetric border (pywt's default mode) -> ``[cA_n, {"ad","da","dd"}_n, ...,
+    {...}_1]``, coarsest first: ``ad`` is low along H and high along W, ``da`` high along H and low along W, ``dd`` high along both;
+    a band of an axis of length N has (N + L - 1) // 2 samples.  ``wavelet``: "haar" = "db1", "db2", or the reconstruction low-pass
+    taps of any orthogonal filter of up to 8 taps.  ``levels``: 1..floor(log2(min(H,W) / (L-1))); None is skimage's rule, that
+    bound minus 3 (at least 1).  Bands are ``[B,h,w]`` (``[h,w]`` for an ``[H,W]`` image, ``[B,h,w,1]`` for ``[B,H,W,1]``); for a
+    tensor they are views of one packed buffer."""
+    import torch
+
+    B, H, W = _dims(x)
+    taps, levels = _wavelet_args("wavedec2", wavelet, levels, H, W)
+    xd, as_np = _images(x)
+    lib = _lib.load()
+    total, bands = _layout(H, W, taps.size, levels)
+    pyr = torch.empty((B, total), dtype=torch.float32, device=xd.device)
+    nbytes = lib.emd_wavelet_workspace_bytes(B, H, W, taps.size, levels)
+    ws = _ws(nbytes, xd.device)
+    _lib.check(lib.emd_wavelet_forward_f32(_p(xd), _p(pyr), B, H, W, _taps_p(taps), taps.size, levels, _p(ws), nbytes, _lib.stream_ptr()),
+               "emd_wavelet_forward_f32")
+    nd = len(np.shape(x))
+
+    def band(i):
+        off, h, w = bands[i]
+        v = pyr[:, off:off + h * w].reshape((h, w) if nd == 2 else (B, h, w, 1) if nd == 4 else (B, h, w))
+        return v.cpu().numpy() if as_np else v
+
+    return [band(0)] + [{k: band(1 + 3 * i + j) for j, k in enumerate(("ad", "da", "dd"))} for i in range(levels)]
+
+
+def waverec2(coeffs, wavelet, shape):
+    """The inverse of ``wavedec2``: ``coeffs`` as it returns them, ``shape`` the image's (``[H,W]``, ``[B,H,W]`` or ``[B,H,W,1]``: the
+    result has that shape).  Synthesis along W, then along H; a level's result is cropped to the shape of the level below."""
+    import torch
+
+    shape = tuple(int(v) for v in shape)
+    B, H, W = _dims(np.empty(shape, np.bool_))
+    levels = len(coeffs) - 1
+    taps, levels = _wavelet_args("waverec2", wavelet, levels, H, W)
+    total, bands = _layout(H, W, taps.size, levels)
+    flat = [coeffs[0]] + [c[k] for c in coeffs[1:] for k in ("ad", "da", "dd")]
+    for v, (_, h, w) in zip(flat, bands):
+        want = (h, w) if len(shape) == 2 else (B, h, w, 1) if len(shape) == 4 else (B, h, w)
+        if tuple(np.shape(v)) != want:
+            raise ValueError(f"waverec2: a band of shape {tuple(np.shape(v))} where the image {shape} has {want}")
+    as_np = not isinstance(flat[0], torch.Tensor)
+    device = torch.device("cuda", torch.cuda.current_device()) if as_np else flat[0].device
+    pyr = torch.empty((B, total), dtype=torch.float32, device=device)
+    for v, (off, h, w) in zip(flat, bands):
+        t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) if as_np else v
+        pyr[:, off:off + h * w].copy_(t.reshape(B, h * w))
+    lib = _lib.load()
+    out = torch.empty((B, H, W), dtype=torch.float32, device=device)
+    nbytes = lib.emd_wavelet_workspace_bytes(B, H, W, taps.size, levels)
+    ws = _ws(nbytes, device)
+    _lib.check(lib.emd_wavelet_inverse_f32(_p(pyr), _p(out), B, H, W, _taps_p(taps), taps.size, levels, _p(ws), nbytes, _lib.stream_ptr()),
+               "emd_wavelet_inverse_f32")
+    out = out.reshape(shape)
+    return out.cpu().numpy() if as_np else out
+
+
+def denoise_wavelet(x, wavelet="db1", levels=None, method="BayesShrink", sigma=None, return_sigma=False):
+    """Wavelet shrinkage, ``skimage.restoration.denoise_wavelet``'s arithmetic at its defaults: ``wavedec2``, a soft threshold
+    sign(d) max(|d| - t, 0) on every detail band of every level (never on cA), ``waverec2``.  method "BayesShrink": t = var /
+    sqrt(max(mean(d^2) - var, float32's epsilon)) per band, var = sigma^2; "VisuShrink": t = sigma sqrt(2 ln(H W)) for all.
+    sigma=None: per image, median(|dd_1| over its non-zero coefficients) / 0.6745 with dd_1 the finest diagonal band, an exact
+    median found on the device with no host synchronisation (an image without a non-zero coefficient: 0, and it comes back through
+    the transform unthresholded).  ``wavelet`` and ``levels`` as in ``wavedec2``.  return_sigma=True: the pair (denoised, sigma
+    ``[B]``).  Hard thresholding is not built (it is discontinuous: its parity cannot be stated as a norm), and skimage's final clip
+    to [0, 1] is not applied (``baseline_table(clip=True)`` clips).  Launches only, on the current stream: capturable."""
+    import torch
+
+    B, H, W = _dims(x)
+    taps, levels = _wavelet_args("denoise_wavelet", wavelet, levels, H, W)
+    if method not in WAVELET_METHODS:
+        raise ValueError(f"denoise_wavelet: method must be one of {sorted(WAVELET_METHODS)} (got {method!r})")
+    if sigma is not None and not (sigma >= 0 and np.isfinite(sigma)):
+        raise ValueError("denoise_wavelet: sigma must be None (estimate it) or finite and >= 0")
+    xd, as_np = _images(x)
+    lib = _lib.load()
+    out = torch.empty_like(xd)
+    used = torch.empty(B, dtype=torch.float32, device=xd.device)
+    nbytes = lib.emd_filter_wavelet_workspace_bytes(B, H, W, taps.size, levels)
+    ws = _ws(nbytes, xd.device)
+    _lib.check(lib.emd_filter_wavelet_f32(_p(xd), _p(out), B, H, W, _taps_p(taps), taps.size, levels, WAVELET_METHODS[method],
+                                          C.c_float(-1.0 if sigma is None else sigma), _p(used), _p(ws), nbytes, _lib.stream_ptr()),
+               "emd_filter_wavelet_f32")
+    y = _shaped(out, x, as_np)
+    return (y, used.cpu().numpy() if as_np else used) if return_sigma else y
+
+
 def _clip01(y):
     """min(max(y, 0), 1) on the device, into a new tensor (y may be a buffer its maker keeps)."""
     import torch
@@ -150,11 +301,12 @@ def _mse_ssim(pred, truth):
     return mse, metrics.ssim(pred, truth, per_image=True)
 
 
-def baseline_table(lq, truth, extra=None, clip=False, **filter_args):
+def baseline_table(lq, truth, extra=None, clip=False, reference_columns=False, **filter_args):
     """The reference's comparison array (misc_py/err_hist_maker.py:26-45) -> ``(data, labels)``: ``data`` float32 ``[N, M, 2]`` with
     ``data[n, m, 0]`` the MSE of method m's output for image n against ``truth`` and ``data[n, m, 1]`` its SSIM (``emdenoise.ssim(...,
     per_image=True)``); ``labels`` = ["Unfiltered", "Gaussian", "Bilateral", "Median", "Wiener", "Chambolle"], the reference's order,
-    then the keys of ``extra``.  The reference's "Wavelet" column is not built: it needs a wavelet-transform pipeline of its own.
+    then the keys of ``extra``.  reference_columns=True: the reference's seven, ``REFERENCE_LABELS``, with "Wavelet"
+    (``denoise_wavelet``) between "Wiener" and "Chambolle"; only then is the filter-argument key ``denoise_wavelet={...}`` accepted.
 
     ``extra``: ``{label: callable(lq) -> denoised}`` appended as further rows, e.g. ``{"D": den.denoise_batch}``: one call then gives
     the paper's comparison.  ``filter_args``: keyword arguments per filter, keyed by its function name, e.g. ``gaussian={"sigma": 1.0},
@@ -163,7 +315,7 @@ def baseline_table(lq, truth, extra=None, clip=False, **filter_args):
     tensors, and only ``data`` comes back; numpy in -> numpy out, CUDA tensors in -> a device tensor."""
     import torch
 
-    unknown = set(filter_args) - {"gaussian", "bilateral", "median", "wiener", "tv_chambolle"}
+    unknown = set(filter_args) - {"gaussian", "bilateral", "median", "wiener", "tv_chambolle"} - ({"denoise_wavelet"} if reference_columns else set())
     if unknown:
         raise TypeError(f"baseline_table: unknown filter(s) {sorted(unknown)}")
     arg = lambda name: dict(filter_args.get(name) or {})
@@ -174,6 +326,9 @@ def baseline_table(lq, truth, extra=None, clip=False, **filter_args):
                ("Wiener", lambda a: wiener(a, **arg("wiener"))),
                ("Chambolle", lambda a: tv_chambolle(a, **arg("tv_chambolle")))]
     assert [m[0] for m in methods] == LABELS
+    if reference_columns:
+        methods.insert(5, ("Wavelet", lambda a: denoise_wavelet(a, **arg("denoise_wavelet"))))
+        assert [m[0] for m in methods] == REFERENCE_LABELS
     for label, fn in (extra or {}).items():
         if label in [m[0] for m in methods]:
             raise ValueError(f"baseline_table: the label {label!r} is taken")

@@ -1030,7 +1030,7 @@ int emd_psnr_f32(const float* x, const float* y, int B, long npix, float data_ra
 
 /* ------------------------------------------------------------------------------------------------
  * Classical baseline filters (csrc/filters.hip): the methods of the reference's comparison table,
- * misc_py/err_hist_maker.py:26-45 (Gaussian, Bilateral, Median, Wiener, Chambolle; "Wavelet" is not built), and the ground-truth
+ * misc_py/err_hist_maker.py:26-45 (Gaussian, Bilateral, Median, Wiener, Chambolle; "Wavelet": csrc/wavelet.hip, below), and the ground-truth
  * blur of misc_py/blur_images.py:13 (cv2.GaussianBlur(img, (3,3), 1.5) = the Gaussian with ksize 3, sigma 1.5).
  *
  * x, out : [B,H,W] float32 (NHWC with C == 1), contiguous, finite; 0 <= B <= 65535 (B == 0 is a no-op); every image of the
@@ -1065,6 +1065,51 @@ int emd_filter_tv_f32(const float* x, float* out, int B, int H, int W, float wei
 /* out = min(max(x, 0), 1) over n floats (the comparison table's optional clip before scoring).  Element-wise: here, and only
  * here, out may be x itself (in place); a partial overlap is refused. */
 int emd_filter_clip01_f32(const float* x, float* out, long n, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2-D orthogonal wavelet transform and wavelet-shrinkage denoising (csrc/wavelet.hip): the "Wavelet" method of
+ * misc_py/err_hist_maker.py:27.  The script that filled the reference's array is not in the reference; what is built is the
+ * arithmetic of skimage.restoration.denoise_wavelet at its defaults (BayesShrink, soft threshold, sigma estimated from the image),
+ * from the formulas below -- neither skimage nor pywt is a dependency.
+ *
+ * A wavelet is its reconstruction low-pass taps rec_lo[0..L-1] (HOST array of doubles; L = ntaps even, 2..8; rounded to float32
+ * once): dec_lo[k] = rec_lo[L-1-k], dec_hi[k] = (-1)^(k+1) rec_lo[k], rec_hi[k] = dec_hi[L-1-k].
+ * Analysis along an axis of length N -> n = (N + L - 1) / 2 coefficients: c[i] = sum_k dec[k] x~[2i + 1 - k] with x~ the
+ * half-sample symmetric extension (x~[-1] = x[0], x~[N] = x[N-1], period 2N: pywt's "symmetric"; NOT the reflect-101 of the
+ * filters above).  A 2-D step filters along H, then along W: cA (low, low), ad (low along H, high along W), da (high along H, low
+ * along W), dd (high, high), each nH x nW; `levels` steps, each on the previous cA.
+ * Synthesis along an axis: x[j] = sum_i a[i] rec_lo[j + L - 2 - 2i] + d[i] rec_hi[j + L - 2 - 2i] over 0 <= j + L - 2 - 2i < L,
+ * 2n - L + 2 samples, along W first, then along H; a level's result is cropped to the shape of the level below (pywt's waverecn
+ * rule: an approximation one sample longer than its detail bands loses its last sample), the last to (H, W).
+ * 1 <= levels <= floor(log2(min(H,W) / (L - 1))), which must be >= 1; H, W <= 32768; 0 <= B <= 65535 (B == 0 is a no-op).
+ *
+ * The pyramid of one image is packed: cA_levels, then ad, da, dd of level `levels`, of level levels - 1, ..., of level 1; the
+ * batch is [B][emd_wavelet_pyramid_floats].  Workspaces are the caller's, 16-byte aligned, sized by the *_workspace_bytes of the
+ * same arguments (0 for arguments the routine would refuse); no buffer may overlap another.  No float atomics: every result is
+ * bitwise reproducible.  All arguments are checked before any launch; one analysis / synthesis launch per level. */
+/* Floats of one image's pyramid (0: refused).  bands (optional, HOST, [1 + 3 levels][3]): (offset in floats, rows, columns) of
+ * cA_levels, then ad, da, dd from the coarsest level to the finest. */
+size_t emd_wavelet_pyramid_floats(int H, int W, int ntaps, int levels, long* bands);
+size_t emd_wavelet_workspace_bytes(int B, int H, int W, int ntaps, int levels);
+/* x [B,H,W] -> pyramid [B][emd_wavelet_pyramid_floats]. */
+int emd_wavelet_forward_f32(const float* x, float* pyramid, int B, int H, int W, const double* rec_lo_host, int ntaps, int levels,
+                            void* workspace, size_t workspace_bytes, emd_stream_t stream);
+/* pyramid -> out [B,H,W]. */
+int emd_wavelet_inverse_f32(const float* pyramid, float* out, int B, int H, int W, const double* rec_lo_host, int ntaps, int levels,
+                            void* workspace, size_t workspace_bytes, emd_stream_t stream);
+#define EMD_WAVELET_BAYES 0 /* t = var / sqrt(max(mean(d^2) - var, FLT_EPSILON)) for every detail band d of every level */
+#define EMD_WAVELET_VISU 1  /* t = sigma sqrt(2 ln(H W)), the same for every band */
+size_t emd_filter_wavelet_workspace_bytes(int B, int H, int W, int ntaps, int levels);
+/* out = inverse(soft(forward(x))), soft(d) = sign(d) max(|d| - t, 0) on the detail bands only (applied as synthesis loads them: no
+ * thresholded coefficient is written to memory; cA is never thresholded); var = sigma^2; mean(d^2) from per-tile double sums added
+ * in a fixed order.  sigma >= 0: used for every image.  sigma < 0: per image, median(|dd_1| over the coefficients that are not
+ * exactly 0) / 0.6744897501960817 with dd_1 the finest diagonal band (skimage's _sigma_est_dwt); the median is exact (an even
+ * count: (a + b) 0.5 of the two middle values, in float32), found by a radix selection on integer histograms, so it is the same
+ * bits on every run; no non-zero coefficient: sigma = 0 and every threshold is 0.  sigma_used (optional, [B]) receives the sigma
+ * used.  Hard thresholding and skimage's final clip to [0,1] are not built (emd_filter_clip01_f32 is the clip).  Launches only, on
+ * `stream`: capturable. */
+int emd_filter_wavelet_f32(const float* x, float* out, int B, int H, int W, const double* rec_lo_host, int ntaps, int levels, int method,
+                           float sigma, float* sigma_used, void* workspace, size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
