@@ -433,6 +433,16 @@ SIGNATURES = {
     # x out B H W rec_lo_host ntaps levels method sigma sigma_used workspace ws_bytes stream
     "emd_filter_wavelet_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_float, _c_float_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- harvesting raw micrographs (csrc/harvest.hip; the table: csrc/host_utils.cpp)
+    # n_in n_out tab_host
+    "emd_box_resize_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    # x image_stride row_stride B d y S tab_dev stream
+    "emd_box_resize_f32": (C.c_int, [_c_float_p, C.c_long, C.c_int, C.c_int, C.c_int, _c_float_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "emd_image_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x B H W stats workspace ws_bytes stream
+    "emd_image_stats_f64": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # x y B n stats stream
+    "emd_scale01_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

@@ -1112,6 +1112,65 @@ int emd_filter_wavelet_f32(const float* x, float* out, int B, int H, int W, cons
                            float sigma, float* sigma_used, void* workspace, size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Harvesting raw micrographs (csrc/harvest.hip): what the reference's MATLAB harvester does to a raw image before
+ * it becomes a training image -- DM3stoTIFs-batch/img_params.m, img_params_lq.m, estimate_noise.m: crop to the smaller dimension,
+ * box-resize to 2048 x 2048, a table of statistics, rescale to [0, 1].  MATLAB is not a dependency: the arithmetic is restated
+ * from the formulas below.
+ *
+ * Crop: d = min(H, W), the top-left d x d pixels (imcrop(img, [1, 1, d-1, d-1])).
+ *
+ * Box resize d -> S (imresize(crop, [S, S], 'method', 'box'), antialiasing on).  For one axis, with 1-based indices, everything in
+ * IEEE double, evaluated in exactly this order with no fused multiply-add:
+ *     scale = S / d;   kw = scale < 1 ? 1 / scale : 1
+ *     for x = 1..S:    u = x / scale + 0.5 * (1 - 1 / scale);   left = floor(u - kw / 2)
+ *                      candidates i = left .. left + ceil(kw) + 1
+ *                      i is a member iff -0.5 <= t && t < 0.5,  t = scale < 1 ? scale * (u - i) : (u - i)
+ * An output sample is the UNWEIGHTED mean of its member pixels (not fractional coverage: this is not cv2.INTER_AREA); S > d is
+ * nearest neighbour.  The members of an output are one contiguous run inside 1..d (MATLAB's mirror fold of indices never applies
+ * to this kernel), but where a candidate lands on a tie the double arithmetic above decides, not exact rational arithmetic: the
+ * table must come from these expressions.  The crop is square, so both axes share one table, and an output pixel is the mean over
+ * (its row run) x (its column run), summed in double in a fixed order and rounded to float32 once.
+ *
+ * Statistics of an H x W image (H, W >= 3; finite values: NaN / Inf are the caller's problem), N = H W, EMD_NSTATS doubles in
+ * this order:
+ *      0 min                 1 max
+ *      2 nonzero             count of x != 0                       3 negative      count of x < 0
+ *      4 mean                                                      5 std           N - 1 denominator (MATLAB std2)
+ *      6 skewness            m3 / m2^1.5                           7 kurtosis      m4 / m2^2  (population central moments m_k =
+ *                                                                                  sum (x - mean)^k / N; not excess)
+ *      8 median              even N: the mean of the two middle values, formed in double; -0 and +0 are equal
+ *      9 rms                 sqrt(sum x^2 / N)                    10 coeff_variation  100 std / mean
+ *     11 noise               sum |conv2_full(x, [1 -2 1; -2 4 -2; 1 -2 1])| sqrt(pi / 2) / (6 (W - 2) (H - 2)), the sum over the
+ *                            (H + 2) x (W + 2) full, zero-padded convolution (estimate_noise.m:8; Immerkaer's estimate)
+ *     12 sqrt_mean  13 sqrt_std  14 sqrt_skewness  15 sqrt_kurtosis    the same four moments of sqrt(max(x, 0))
+ *     16 sqrt_mean_ratio     sqrt_mean / mean
+ * Central moments are two-pass (the mean first, then sum (x - mean)^k in double); every sum is in double, per-workgroup partial
+ * sums combined in a fixed order; the median is exact, by a four-pass radix selection on integer histograms.  No floating-point
+ * atomics: bitwise reproducible, and an image's result does not depend on B.  A constant image has m2 = 0: skewness and kurtosis
+ * are NaN, as in MATLAB.
+ *
+ * Scale to [0, 1]: (x - min) / (max - min) in float32; |max - min| < 1e-6 (a constant image) gives 0.5 -- this library's
+ * scale0to1 rule; the MATLAB gives NaN there (a documented deviation).
+ *
+ * 0 <= B <= 65535 (B == 0 is a no-op); launches only, on `stream`, no host synchronisation: capturable. */
+#define EMD_NSTATS 17
+/* HOST only: tab[n_out][2] = (first member, 0-based; member count) of every output sample of the box resize n_in -> n_out, from
+ * the expressions above.  The one copy of the table arithmetic.  1 <= n_in <= 32768, 1 <= n_out <= 8192. */
+int emd_box_resize_table(int n_in, int n_out, int* tab);
+/* y[b] ([B,S,S], contiguous) = box resize of the top-left d x d pixels of image b at x + b * image_stride, rows row_stride floats
+ * apart (the crop is expressed by row_stride and d).  tab_dev: DEVICE copy of emd_box_resize_table(d, S); runs are clamped to
+ * 0..d-1 whatever it holds.  1 <= d <= 32768, 1 <= S <= 8192, row_stride >= d.  y may not overlap x. */
+int emd_box_resize_f32(const float* x, long image_stride, int row_stride, int B, int d, float* y, int S, const int* tab_dev,
+                       emd_stream_t stream);
+size_t emd_image_stats_workspace_bytes(int B, int H, int W);
+/* x [B,H,W] -> stats [B][EMD_NSTATS] (DEVICE, doubles).  3 <= H, W <= 32768.  The workspace is the caller's, 16-byte aligned. */
+int emd_image_stats_f64(const float* x, int B, int H, int W, double* stats, void* workspace, size_t workspace_bytes,
+                        emd_stream_t stream);
+/* y [B][n] = scale to [0, 1] of x [B][n] with min, max = stats[b][0], stats[b][1] of emd_image_stats_f64, read on the device.
+ * Element-wise: y may be x itself. */
+int emd_scale01_f32(const float* x, float* y, int B, long n, const double* stats, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
