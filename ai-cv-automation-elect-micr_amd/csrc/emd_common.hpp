@@ -49,6 +49,13 @@ int launch_bn_stats_final(const double* part, int nslab, int C, long npix, float
                           float* shift = nullptr, int images = 1, const BnFoldArgs* train_fold = nullptr);   // scale != NULL: the norm is folded in the same launch; images > 1 (no fold): per-image statistics
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline int tiles_of(int n, int t) { return (n + t - 1) / t; }
+inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }   // workspace parts start 256 bytes aligned
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return na && nb && pa < pb + nb && pb < pa + na;
+}
 
 constexpr int kWave = 64;  // CDNA4 wavefront
 

@@ -314,25 +314,17 @@ __global__ __launch_bounds__(256) void filter_clip01_kernel(const float* __restr
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-inline int tiles_of(int n, int t) { return (n + t - 1) / t; }
-inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
 // what every filter checks first: pointers, the batch, the extents (a grid of TH-row tiles must fit) and that out is not x
 int check_images(const char* who, const float* x, const float* out, int B, int H, int W, int TH) {
     if (!x || !out) {
         emd::set_error("%s: null pointer", who);
         return EMD_E_INVALID;
     }
-    if (B < 0 || B > 65535 || H < 1 || W < 1 || (long)tiles_of(H, TH) * tiles_of(W, kTW) > INT_MAX) {
+    if (B < 0 || B > 65535 || H < 1 || W < 1 || (long)emd::tiles_of(H, TH) * emd::tiles_of(W, kTW) > INT_MAX) {
         emd::set_error("%s: bad shape (batch 0..65535, H, W >= 1; got %d x %d x %d)", who, B, H, W);
         return EMD_E_INVALID;
     }
-    if (B > 0 && overlap(x, (size_t)B * H * W * sizeof(float), out, (size_t)B * H * W * sizeof(float))) {
+    if (B > 0 && emd::overlap(x, (size_t)B * H * W * sizeof(float), out, (size_t)B * H * W * sizeof(float))) {
         emd::set_error("%s: out may not alias x (a tile reads its neighbours' pixels)", who);
         return EMD_E_INVALID;
     }
@@ -348,17 +340,17 @@ int check_mirror(const char* who, int radius, int H, int W) {
 }
 
 dim3 grid_of(int B, int H, int W, int TH, int* tiles_x) {
-    *tiles_x = tiles_of(W, kTW);
-    return dim3((unsigned)(*tiles_x * tiles_of(H, TH)), (unsigned)B);
+    *tiles_x = emd::tiles_of(W, kTW);
+    return dim3((unsigned)(*tiles_x * emd::tiles_of(H, TH)), (unsigned)B);
 }
 
 constexpr int kWienerTH = kWaves * kWienerSH, kSmallTH = kWaves * kSmallSH, kGaussTH = kWaves * kGaussSH;
 
 bool wiener_size_ok(int ksize) { return ksize >= 3 && ksize <= 9 && ksize % 2 == 1; }
 size_t wiener_ws_bytes(int B, int H, int W) {
-    return round256((size_t)B * tiles_of(H, kWienerTH) * tiles_of(W, kTW) * sizeof(double));
+    return emd::round256((size_t)B * emd::tiles_of(H, kWienerTH) * emd::tiles_of(W, kTW) * sizeof(double));
 }
-size_t tv_plane_bytes(int B, int H, int W) { return round256((size_t)B * H * W * sizeof(float)); }
+size_t tv_plane_bytes(int B, int H, int W) { return emd::round256((size_t)B * H * W * sizeof(float)); }
 
 template <int MODE>
 void launch_wiener(int ksize, dim3 grid, hipStream_t st, const float* x, float* out, int H, int W, int tiles_x, float noise,
@@ -458,7 +450,7 @@ extern "C" int emd_filter_bilateral_f32(const float* x, float* out, int B, int H
 }
 
 extern "C" size_t emd_filter_wiener_workspace_bytes(int B, int H, int W) {
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long)tiles_of(H, kWienerTH) * tiles_of(W, kTW) > INT_MAX) return 0;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long)emd::tiles_of(H, kWienerTH) * emd::tiles_of(W, kTW) > INT_MAX) return 0;
     return wiener_ws_bytes(B, H, W);
 }
 
@@ -491,7 +483,7 @@ extern "C" int emd_filter_wiener_f32(const float* x, float* out, int B, int H, i
 }
 
 extern "C" size_t emd_filter_tv_workspace_bytes(int B, int H, int W) {
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long)tiles_of(H, kSmallTH) * tiles_of(W, kTW) > INT_MAX) return 0;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long)emd::tiles_of(H, kSmallTH) * emd::tiles_of(W, kTW) > INT_MAX) return 0;
     return 4 * tv_plane_bytes(B, H, W);
 }
 
@@ -506,7 +498,7 @@ extern "C" int emd_filter_tv_f32(const float* x, float* out, int B, int H, int W
     EMD_REQUIRE(emd::aligned16(workspace), EMD_E_ALIGN, "emd_filter_tv_f32: workspace must be 16-byte aligned");
     if (B == 0) return EMD_OK;
     const size_t n = (size_t)B * H * W * sizeof(float);
-    EMD_REQUIRE(!overlap(workspace, 4 * tv_plane_bytes(B, H, W), x, n) && !overlap(workspace, 4 * tv_plane_bytes(B, H, W), out, n), EMD_E_INVALID, "emd_filter_tv_f32: the workspace may not overlap x or out");
+    EMD_REQUIRE(!emd::overlap(workspace, 4 * tv_plane_bytes(B, H, W), x, n) && !emd::overlap(workspace, 4 * tv_plane_bytes(B, H, W), out, n), EMD_E_INVALID, "emd_filter_tv_f32: the workspace may not overlap x or out");
     int tiles_x;
     const dim3 grid = grid_of(B, H, W, kSmallTH, &tiles_x);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -528,7 +520,7 @@ extern "C" int emd_filter_tv_f32(const float* x, float* out, int B, int H, int W
 extern "C" int emd_filter_clip01_f32(const float* x, float* out, long n, emd_stream_t stream) {
     EMD_REQUIRE(x && out, EMD_E_INVALID, "emd_filter_clip01_f32: null pointer");
     EMD_REQUIRE(n >= 0, EMD_E_INVALID, "emd_filter_clip01_f32: n must be >= 0");
-    EMD_REQUIRE(out == x || !overlap(x, (size_t)n * sizeof(float), out, (size_t)n * sizeof(float)), EMD_E_INVALID,
+    EMD_REQUIRE(out == x || !emd::overlap(x, (size_t)n * sizeof(float), out, (size_t)n * sizeof(float)), EMD_E_INVALID,
                 "emd_filter_clip01_f32: out is x itself or does not overlap it");
     if (n == 0) return EMD_OK;
     const long nb = (n + 255) / 256;

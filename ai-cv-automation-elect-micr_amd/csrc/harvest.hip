@@ -15,6 +15,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "radix_select.hpp"
 #include "stencil_rows.hpp"
 #include "wave_reduce.hpp"
 
@@ -24,23 +25,6 @@ namespace {
 
 constexpr int kMaxExtent = 32768;   // H, W, d
 constexpr int kMaxOut = 8192;       // S
-
-inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return na && nb && pa < pb + nb && pb < pa + na;
-}
-
-// Sum of one double per thread over the 256 threads of a workgroup: lanes, then the four waves, in a fixed order.  Valid in
-// thread 0.  sh: 4 doubles, not otherwise in use between two calls' barriers.
-__device__ __forceinline__ double block_sum_thread0(double v, double* sh) {
-    v = wave_sum_lane0(v);
-    __syncthreads();   // sh may still be read from the previous call
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
 
 // ---- box resize ------------------------------------------------------------------------------------------------------------
 constexpr int kRT = 16;    // output rows of a tile (a wave: 4)
@@ -124,29 +108,19 @@ constexpr int kChunk = 4096;     // pixels per workgroup of the 1-D passes
 constexpr int kPart1 = 8;        // per tile: sum x, sum x^2, sum sqrt, sum |laplacian|, min, max, nonzero, negative
 constexpr int kPart2 = 6;        // per chunk: sum (x - mean)^k, k = 2, 3, 4; the same of sqrt(max(x, 0))
 constexpr int kAcc = 16;         // per image: the eight of kPart1 reduced, then mean, sqrt_mean
-constexpr int kStateWords = 4;   // (prefix, prefix, rank, rank) of the two middle ranks
-
-// The order-preserving key of a signed float: negative -> all bits flipped, else the sign bit set.  -0 is +0 first (they are equal).
-__device__ __forceinline__ unsigned key_of(float v) {
-    unsigned u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned key) { return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); }
-
 struct StatsBuffers {
     double* part1;     // [B][kPart1][tiles]
     double* part2;     // [B][kPart2][chunks]
     double* acc;       // [B][kAcc]
-    unsigned* hist;    // [B][4 passes][2 ranks][256]
-    unsigned* state;   // [B][4][kStateWords]: [q] what pass q works with (q = 1..3)
+    unsigned* hist;    // the selection's (radix_select.hpp): the key is signed_key, every pixel is counted
+    unsigned* state;
 };
 
 // Pass 0 of everything: grid (tiles of the (H + 2) x (W + 2) full-convolution grid, B).  Position (er, ec) of that grid is centred on
 // pixel (er - 1, ec - 1); a pixel is counted by the workgroup whose tile holds its centre, so every pixel is counted once.
 __global__ __launch_bounds__(256) void stats_tile_kernel(const float* __restrict__ x, int H, int W, int tiles_x, StatsBuffers sb) {
     __shared__ float xs[kLH * kLW];
-    __shared__ unsigned h[256];
+    __shared__ unsigned h[1][256];
     __shared__ double sh[4];
     __shared__ float shf[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(256) void stats_tile_kernel(const float* __restrict
     const int er0 = (tile / tiles_x) * kTH, ec0 = (tile % tiles_x) * kTW;
     const long b = blockIdx.y;
     const float* xb = x + b * (long)H * W;
-    h[tid] = 0;
+    h[0][tid] = 0;
     // xs[r][c] = pixel (er0 - 2 + r, ec0 - 2 + c), 0 outside the image
     for (int i = tid; i < kLH * kLW; i += 256) {
         const int r = i / kLW, c = i - r * kLW;
@@ -184,7 +158,7 @@ __global__ __launch_bounds__(256) void stats_tile_kernel(const float* __restrict
                 mx = fmaxf(mx, v);
                 nz += v != 0.f;
                 neg += v < 0.f;
-                atomicAdd(&h[key_of(v) >> 24], 1u);
+                select_count_first(h, signed_key(v));
             }
         }
     }
@@ -213,59 +187,20 @@ __global__ __launch_bounds__(256) void stats_tile_kernel(const float* __restrict
         out[4L * tiles] = (double)fminf(fminf(shf[0][0], shf[0][1]), fminf(shf[0][2], shf[0][3]));
         out[5L * tiles] = (double)fmaxf(fmaxf(shf[1][0], shf[1][1]), fmaxf(shf[1][2], shf[1][3]));
     }
-    if (h[tid]) atomicAdd(&sb.hist[(b * 4 + 0) * 512 + tid], h[tid]);
+    select_flush<1>(h, sb.hist + select_hist_at(b, 0));
 }
 
-// From the histograms of pass q (for either middle rank; pass 0 has one for both) and the state that pass worked with: the state
-// of pass q + 1 into out, kStateWords words of LDS (after pass 3: the prefixes are the two middle keys).  Every thread of the 256
-// calls it; out is valid for all of them after the call.
-__device__ void select_resolve(const unsigned* __restrict__ hist, const unsigned* __restrict__ in, int q, unsigned rank0, unsigned rank1,
-                               unsigned (*sc)[256], unsigned* out) {
+// Minimum (MAX = false) or maximum of p[0 .. n - 1] by the workgroup; every thread returns it.
+template <bool MAX>
+__device__ double block_extreme(const double* __restrict__ p, int n, double* sh) {
     const int tid = threadIdx.x;
-    const unsigned n0 = hist[tid], n1 = q ? hist[256 + tid] : n0;
-    __syncthreads();   // sc may still be read
-    sc[0][tid] = n0;
-    sc[1][tid] = n1;
-    if (tid < kStateWords) out[tid] = 0;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned a0 = tid >= off ? sc[0][tid - off] : 0u, a1 = tid >= off ? sc[1][tid - off] : 0u;
-        __syncthreads();
-        sc[0][tid] += a0;
-        sc[1][tid] += a1;
-        __syncthreads();
-    }
-    unsigned prefix0 = 0, prefix1 = 0;
-    if (q) {
-        prefix0 = in[0];
-        prefix1 = in[1];
-        rank0 = in[2];
-        rank1 = in[3];
-    }
-    // exactly one bin holds each rank: the counts of a pass add up to the rank's range
-    const unsigned i0 = sc[0][tid], i1 = sc[1][tid];
-    if (n0 && i0 - n0 <= rank0 && rank0 < i0) {
-        out[0] = (prefix0 << 8) | (unsigned)tid;
-        out[2] = rank0 - (i0 - n0);
-    }
-    if (n1 && i1 - n1 <= rank1 && rank1 < i1) {
-        out[1] = (prefix1 << 8) | (unsigned)tid;
-        out[3] = rank1 - (i1 - n1);
-    }
-    __syncthreads();
-}
-
-// Sum, minimum or maximum of p[0 .. n - 1] by the workgroup, in a fixed order; every thread returns it.
-template <int OP>   // 0 sum, 1 min, 2 max
-__device__ double block_reduce_fixed(const double* __restrict__ p, int n, double* sh) {
-    const int tid = threadIdx.x;
-    double s = OP == 0 ? 0.0 : (OP == 1 ? INFINITY : -INFINITY);
-    for (int i = tid; i < n; i += 256) s = OP == 0 ? s + p[i] : (OP == 1 ? fmin(s, p[i]) : fmax(s, p[i]));
+    double s = MAX ? -INFINITY : INFINITY;
+    for (int i = tid; i < n; i += 256) s = MAX ? fmax(s, p[i]) : fmin(s, p[i]);
     __syncthreads();   // sh may still be read from the previous call
     sh[tid] = s;
     __syncthreads();
     for (int off = 128; off >= 1; off >>= 1) {
-        if (tid < off) sh[tid] = OP == 0 ? sh[tid] + sh[tid + off] : (OP == 1 ? fmin(sh[tid], sh[tid + off]) : fmax(sh[tid], sh[tid + off]));
+        if (tid < off) sh[tid] = MAX ? fmax(sh[tid], sh[tid + off]) : fmin(sh[tid], sh[tid + off]);
         __syncthreads();
     }
     return sh[0];
@@ -280,17 +215,16 @@ __global__ __launch_bounds__(256) void stats_mid_kernel(StatsBuffers sb, int til
     const double* p = sb.part1 + b * kPart1 * tiles;
     double v[kPart1];
     for (int k = 0; k < kPart1; ++k)
-        v[k] = k == 4 ? block_reduce_fixed<1>(p + (long)k * tiles, tiles, sh)
-                      : (k == 5 ? block_reduce_fixed<2>(p + (long)k * tiles, tiles, sh) : block_reduce_fixed<0>(p + (long)k * tiles, tiles, sh));
+        v[k] = k == 4 ? block_extreme<false>(p + (long)k * tiles, tiles, sh)
+                      : (k == 5 ? block_extreme<true>(p + (long)k * tiles, tiles, sh) : block_sum_fixed(p + (long)k * tiles, tiles, 1, sh));
     if (threadIdx.x == 0) {
         double* a = sb.acc + b * kAcc;
         for (int k = 0; k < kPart1; ++k) a[k] = v[k];
         a[8] = v[0] / count;
         a[9] = v[2] / count;
     }
-    const unsigned n = (unsigned)count;   // < 2^31
-    select_resolve(sb.hist + (b * 4 + 0) * 512, nullptr, 0, (n - 1) / 2, n / 2, sc, next);
-    if (threadIdx.x < kStateWords) sb.state[(b * 4 + 1) * kStateWords + threadIdx.x] = next[threadIdx.x];
+    select_resolve(sb.hist + select_hist_at(b, 0), nullptr, 0, sc, next);
+    if (threadIdx.x < kStateWords) sb.state[select_state_at(b, 1) + threadIdx.x] = next[threadIdx.x];
 }
 
 // grid (B): pass q's histograms -> the state of pass q + 1 (q = 1, 2)
@@ -298,8 +232,8 @@ __global__ __launch_bounds__(256) void stats_resolve_kernel(StatsBuffers sb, int
     __shared__ unsigned sc[2][256];
     __shared__ unsigned next[kStateWords];
     const long b = blockIdx.x;
-    select_resolve(sb.hist + (b * 4 + q) * 512, sb.state + (b * 4 + q) * kStateWords, q, 0, 0, sc, next);
-    if (threadIdx.x < kStateWords) sb.state[(b * 4 + q + 1) * kStateWords + threadIdx.x] = next[threadIdx.x];
+    select_resolve(sb.hist + select_hist_at(b, q), sb.state + select_state_at(b, q), q, sc, next);
+    if (threadIdx.x < kStateWords) sb.state[select_state_at(b, q + 1) + threadIdx.x] = next[threadIdx.x];
 }
 
 // grid (chunks, B): selection pass `pass` (1..3) over the image as a row of n pixels; MOMENTS: the centred sums as well
@@ -309,7 +243,7 @@ __global__ __launch_bounds__(256) void stats_chunk_kernel(const float* __restric
     __shared__ double sh[4];
     const int tid = threadIdx.x;
     const long b = blockIdx.y;
-    const unsigned* st = sb.state + (b * 4 + pass) * kStateWords;
+    const unsigned* st = sb.state + select_state_at(b, pass);
     const unsigned prefix0 = st[0], prefix1 = st[1];
     h[0][tid] = 0;
     h[1][tid] = 0;
@@ -320,15 +254,11 @@ __global__ __launch_bounds__(256) void stats_chunk_kernel(const float* __restric
         smean = sb.acc[b * kAcc + 9];
     }
     double m2 = 0.0, m3 = 0.0, m4 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
-    const int shift = 24 - 8 * pass;
     const long begin = (long)blockIdx.x * kChunk, end = begin + kChunk < n ? begin + kChunk : n;
     const float* xb = x + b * n;
     for (long i = begin + tid; i < end; i += 256) {
         const float v = xb[i];
-        const unsigned key = key_of(v);
-        const unsigned bin = (key >> shift) & 255u, high = key >> (shift + 8);
-        if (high == prefix0) atomicAdd(&h[0][bin], 1u);
-        if (high == prefix1) atomicAdd(&h[1][bin], 1u);
+        select_count(h, signed_key(v), pass, prefix0, prefix1);
         if (MOMENTS) {
             const double dv = (double)v - mean, d2 = dv * dv;
             m2 += d2;
@@ -341,9 +271,7 @@ __global__ __launch_bounds__(256) void stats_chunk_kernel(const float* __restric
         }
     }
     __syncthreads();
-    unsigned* hb = sb.hist + (b * 4 + pass) * 512;
-    if (h[0][tid]) atomicAdd(&hb[tid], h[0][tid]);
-    if (h[1][tid]) atomicAdd(&hb[256 + tid], h[1][tid]);
+    select_flush<2>(h, sb.hist + select_hist_at(b, pass));
     if (MOMENTS) {
         const long chunks = gridDim.x;
         double* out = sb.part2 + b * kPart2 * chunks + blockIdx.x;
@@ -362,9 +290,9 @@ __global__ __launch_bounds__(256) void stats_final_kernel(StatsBuffers sb, int c
     __shared__ unsigned sc[2][256];
     __shared__ unsigned keys[kStateWords];
     const long b = blockIdx.x;
-    select_resolve(sb.hist + (b * 4 + 3) * 512, sb.state + (b * 4 + 3) * kStateWords, 3, 0, 0, sc, keys);
+    select_resolve(sb.hist + select_hist_at(b, 3), sb.state + select_state_at(b, 3), 3, sc, keys);
     double c[kPart2];
-    for (int k = 0; k < kPart2; ++k) c[k] = block_reduce_fixed<0>(sb.part2 + (b * kPart2 + k) * chunks, chunks, sh);
+    for (int k = 0; k < kPart2; ++k) c[k] = block_sum_fixed(sb.part2 + (b * kPart2 + k) * chunks, chunks, 1, sh);
     if (threadIdx.x != 0) return;
     const double* a = sb.acc + b * kAcc;
     const double N = (double)H * (double)W;
@@ -379,7 +307,7 @@ __global__ __launch_bounds__(256) void stats_final_kernel(StatsBuffers sb, int c
     s[5] = sd;
     s[6] = (c[1] / N) / (m2 * sqrt(m2));
     s[7] = (c[2] / N) / (m2 * m2);
-    s[8] = ((double)value_of(keys[0]) + (double)value_of(keys[1])) * 0.5;
+    s[8] = ((double)signed_key_value(keys[0]) + (double)signed_key_value(keys[1])) * 0.5;
     s[9] = sqrt(a[1] / N);
     s[10] = 100.0 * sd / mean;
     s[11] = a[3] * sqrt(0.5 * M_PI) / (6.0 * (double)(W - 2) * (double)(H - 2));
@@ -420,15 +348,15 @@ StatsLayout stats_layout(int B, int H, int W) {
     l.chunks = (int)(((long)H * W + kChunk - 1) / kChunk);
     size_t bytes = 0;
     l.part1 = bytes;
-    bytes += round256((size_t)B * kPart1 * l.tiles * sizeof(double));
+    bytes += emd::round256((size_t)B * kPart1 * l.tiles * sizeof(double));
     l.part2 = bytes;
-    bytes += round256((size_t)B * kPart2 * l.chunks * sizeof(double));
+    bytes += emd::round256((size_t)B * kPart2 * l.chunks * sizeof(double));
     l.acc = bytes;
-    bytes += round256((size_t)B * kAcc * sizeof(double));
+    bytes += emd::round256((size_t)B * kAcc * sizeof(double));
     l.hist = bytes;
-    bytes += round256((size_t)B * 4 * 512 * sizeof(unsigned));
+    bytes += select_hist_bytes(B);
     l.state = bytes;
-    bytes += round256((size_t)B * 4 * kStateWords * sizeof(unsigned));
+    bytes += select_state_bytes(B);
     l.bytes = bytes;
     return l;
 }
@@ -444,7 +372,7 @@ extern "C" int emd_box_resize_f32(const float* x, long image_stride, int row_str
     if (B == 0) return EMD_OK;
     EMD_REQUIRE(x && y && tab_dev, EMD_E_INVALID, "emd_box_resize_f32: null pointer");
     const size_t nx = ((size_t)(B - 1) * (size_t)image_stride + (size_t)(d - 1) * row_stride + d) * sizeof(float);
-    EMD_REQUIRE(!overlap(x, nx, y, (size_t)B * S * S * sizeof(float)), EMD_E_INVALID, "emd_box_resize_f32: y may not overlap x");
+    EMD_REQUIRE(!emd::overlap(x, nx, y, (size_t)B * S * S * sizeof(float)), EMD_E_INVALID, "emd_box_resize_f32: y may not overlap x");
     const int tiles_x = (S + kRC - 1) / kRC;
     const dim3 grid((unsigned)(tiles_x * ((S + kRT - 1) / kRT)), (unsigned)B);
     hipLaunchKernelGGL(box_resize_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, image_stride, row_stride, d, y, S,
@@ -472,7 +400,7 @@ extern "C" int emd_image_stats_f64(const float* x, int B, int H, int W, double* 
     }
     EMD_REQUIRE(emd::aligned16(workspace), EMD_E_ALIGN, "emd_image_stats_f64: workspace must be 16-byte aligned");
     const size_t nx = (size_t)B * H * W * sizeof(float), ns = (size_t)B * EMD_NSTATS * sizeof(double);
-    EMD_REQUIRE(!overlap(workspace, l.bytes, x, nx) && !overlap(workspace, l.bytes, stats, ns) && !overlap(stats, ns, x, nx), EMD_E_INVALID,
+    EMD_REQUIRE(!emd::overlap(workspace, l.bytes, x, nx) && !emd::overlap(workspace, l.bytes, stats, ns) && !emd::overlap(stats, ns, x, nx), EMD_E_INVALID,
                 "emd_image_stats_f64: x, stats and the workspace may not overlap");
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
@@ -482,7 +410,7 @@ extern "C" int emd_image_stats_f64(const float* x, int B, int H, int W, double* 
     sb.acc = reinterpret_cast<double*>(ws + l.acc);
     sb.hist = reinterpret_cast<unsigned*>(ws + l.hist);
     sb.state = reinterpret_cast<unsigned*>(ws + l.state);
-    const hipError_t e = hipMemsetAsync(sb.hist, 0, (size_t)B * 4 * 512 * sizeof(unsigned), st);
+    const hipError_t e = hipMemsetAsync(sb.hist, 0, select_hist_bytes(B), st);
     if (e != hipSuccess) {
         emd::set_error("emd_image_stats_f64: hipMemsetAsync: %s", hipGetErrorString(e));
         return EMD_E_LAUNCH;
@@ -505,7 +433,7 @@ extern "C" int emd_scale01_f32(const float* x, float* y, int B, long n, const do
     if (B == 0) return EMD_OK;
     EMD_REQUIRE(x && y && stats, EMD_E_INVALID, "emd_scale01_f32: null pointer");
     const size_t nx = (size_t)B * (size_t)n * sizeof(float);
-    EMD_REQUIRE(x == y || !overlap(x, nx, y, nx), EMD_E_INVALID, "emd_scale01_f32: y must be x itself or apart from it");
+    EMD_REQUIRE(x == y || !emd::overlap(x, nx, y, nx), EMD_E_INVALID, "emd_scale01_f32: y must be x itself or apart from it");
     const long want = (n + 256 * 8 - 1) / (256 * 8);
     hipLaunchKernelGGL(scale01_kernel, dim3((unsigned)(want > 2048 ? 2048 : want), (unsigned)B), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, y, n, stats);

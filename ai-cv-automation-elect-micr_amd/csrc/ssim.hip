@@ -306,9 +306,6 @@ __global__ __launch_bounds__(256) void psnr_final_kernel(const double* __restric
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-inline int tiles_of(int n, int t) { return (n + t - 1) / t; }
-inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 int check_window(const char* who, const float* taps_host, int size, int H, int W, Taps* t) {
     if (!taps_host) {
         emd::set_error("%s: null pointer (taps_host)", who);
@@ -330,10 +327,10 @@ bool fwd_vec_ok(const float* x, const float* y, int W) { return W % 4 == 0 && em
 
 size_t fwd_part_bytes(int B, int H, int W, int size) {
     const int Hm = H - size + 1, Wm = W - size + 1;
-    return round256((size_t)B * tiles_of(Hm, kWaves * kFwdSH) * tiles_of(Wm, kTW) * 2 * sizeof(double));
+    return emd::round256((size_t)B * emd::tiles_of(Hm, kWaves * kFwdSH) * emd::tiles_of(Wm, kTW) * 2 * sizeof(double));
 }
 // the whole forward workspace: [per-tile partial sums] [per-image means, double [B][2]]
-size_t fwd_ws_bytes(int B, int H, int W, int size) { return fwd_part_bytes(B, H, W, size) + round256((size_t)B * 2 * sizeof(double)); }
+size_t fwd_ws_bytes(int B, int H, int W, int size) { return fwd_part_bytes(B, H, W, size) + emd::round256((size_t)B * 2 * sizeof(double)); }
 
 template <int S>
 void launch_fwd_s(bool vec, dim3 grid, hipStream_t st, const float* x, const float* y, int H, int W, int Hm, int Wm, int tiles_x,
@@ -350,7 +347,7 @@ void launch_fwd_s(bool vec, dim3 grid, hipStream_t st, const float* x, const flo
 int launch_fwd(const float* x, const float* y, int B, int H, int W, const Taps& t, int size, double* part, float* ssim_map,
                float* cs_map, float* G, hipStream_t st, int* tiles_out) {
     const int Hm = H - size + 1, Wm = W - size + 1;
-    const int tiles_x = tiles_of(Wm, kTW), tiles = tiles_x * tiles_of(Hm, kWaves * kFwdSH);
+    const int tiles_x = emd::tiles_of(Wm, kTW), tiles = tiles_x * emd::tiles_of(Hm, kWaves * kFwdSH);
     const dim3 grid((unsigned)tiles, (unsigned)B);
     const bool vec = fwd_vec_ok(x, y, W);
     const float neg_inv_n = (float)(-1.0 / ((double)Hm * Wm));
@@ -392,11 +389,6 @@ int launch_pool(const float* x0, float* y0, const float* x1, float* y1, int B, i
 
 const MsWeights kMsWeights = {{0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f}};   // :171
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" size_t emd_ssim_workspace_bytes(int B, int H, int W, int size) {
@@ -424,7 +416,7 @@ extern "C" int emd_ssim_f32(const float* x, const float* y, int B, int H, int W,
 
 extern "C" size_t emd_ssim_loss_workspace_bytes(int B, int H, int W, int size) {
     if (B < 1 || size < 3 || size > kMaxSize || size % 2 == 0 || H < size || W < size) return 0;
-    return fwd_ws_bytes(B, H, W, size) + round256((size_t)3 * B * (H - size + 1) * (W - size + 1) * sizeof(float));
+    return fwd_ws_bytes(B, H, W, size) + emd::round256((size_t)3 * B * (H - size + 1) * (W - size + 1) * sizeof(float));
 }
 
 extern "C" int emd_ssim_loss_f32(const float* x, const float* y, int B, int H, int W, const float* taps_host, int size, int per_image,
@@ -440,7 +432,7 @@ extern "C" int emd_ssim_loss_f32(const float* x, const float* y, int B, int H, i
     EMD_REQUIRE(!loss_acc || acc_stride >= 1, EMD_E_INVALID, "emd_ssim_loss_f32: acc_stride must be >= 1");
     if (dout && H >= 1 && W >= 1 && B >= 1) {
         const size_t n = (size_t)B * H * W * sizeof(float);
-        EMD_REQUIRE(!overlap(dout, n, x, n) && !overlap(dout, n, y, n), EMD_E_INVALID, "emd_ssim_loss_f32: dout may not alias x or y");
+        EMD_REQUIRE(!emd::overlap(dout, n, x, n) && !emd::overlap(dout, n, y, n), EMD_E_INVALID, "emd_ssim_loss_f32: dout may not alias x or y");
     }
     if (B == 0) return EMD_OK;
     EMD_REQUIRE(workspace_bytes >= emd_ssim_loss_workspace_bytes(B, H, W, size), EMD_E_INVALID, "emd_ssim_loss_f32: workspace too small");
@@ -455,8 +447,8 @@ extern "C" int emd_ssim_loss_f32(const float* x, const float* y, int B, int H, i
     if (rc != EMD_OK) return rc;
     rc = launch_final(part, im, B, tiles, Hm, Wm, nullptr, result, loss_acc, acc_stride, acc_weight, per_image ? 1 : 0, st);
     if (rc != EMD_OK || !dout) return rc;
-    const int tiles_x = tiles_of(W, kTW);
-    const dim3 grid((unsigned)(tiles_x * tiles_of(H, kWaves * kGradSH)), (unsigned)B);
+    const int tiles_x = emd::tiles_of(W, kTW);
+    const dim3 grid((unsigned)(tiles_x * emd::tiles_of(H, kWaves * kGradSH)), (unsigned)B);
     const float s = per_image ? scale : scale / (float)B;   // the batch mean's gradient: 1 / B of each image's
     const long plane = (long)B * Hm * Wm;
 #define EMD_SSIM_CASE(SZ) \
@@ -494,12 +486,12 @@ MsLayout ms_layout(int B, int H, int W, int level, int size) {
     MsLayout L{};
     L.part = 0;
     L.means = fwd_ws_bytes(B, H, W, size);
-    size_t off = L.means + round256((size_t)level * (B + 1) * 2 * sizeof(float));
+    size_t off = L.means + emd::round256((size_t)level * (B + 1) * 2 * sizeof(float));
     L.h[0] = H, L.w[0] = W;
     for (int l = 1; l < level; ++l) {
         L.h[l] = (L.h[l - 1] + 1) / 2, L.w[l] = (L.w[l - 1] + 1) / 2;
         L.pooled[l] = off;
-        off += 2 * round256((size_t)B * L.h[l] * L.w[l] * sizeof(float));
+        off += 2 * emd::round256((size_t)B * L.h[l] * L.w[l] * sizeof(float));
     }
     L.total = off;
     return L;
@@ -546,7 +538,7 @@ extern "C" int emd_ms_ssim_f32(const float* x, const float* y, int B, int H, int
         if (rc != EMD_OK) return rc;
         if (l + 1 < level) {
             float* nx = reinterpret_cast<float*>(ws + L.pooled[l + 1]);
-            float* ny = reinterpret_cast<float*>(ws + L.pooled[l + 1] + round256((size_t)B * L.h[l + 1] * L.w[l + 1] * sizeof(float)));
+            float* ny = reinterpret_cast<float*>(ws + L.pooled[l + 1] + emd::round256((size_t)B * L.h[l + 1] * L.w[l + 1] * sizeof(float)));
             rc = launch_pool(cx, nx, cy, ny, B, L.h[l], L.w[l], st);
             if (rc != EMD_OK) return rc;
             cx = nx, cy = ny;
@@ -565,7 +557,7 @@ int psnr_blocks(long npix) {
 
 extern "C" size_t emd_psnr_workspace_bytes(int B, long npix) {
     if (B < 1 || npix < 1) return 0;
-    return round256((size_t)B * psnr_blocks(npix) * sizeof(double)) + round256((size_t)B * sizeof(double));
+    return emd::round256((size_t)B * psnr_blocks(npix) * sizeof(double)) + emd::round256((size_t)B * sizeof(double));
 }
 
 extern "C" int emd_psnr_f32(const float* x, const float* y, int B, long npix, float data_range, float* out, void* workspace,
@@ -579,7 +571,7 @@ extern "C" int emd_psnr_f32(const float* x, const float* y, int B, long npix, fl
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nblk = psnr_blocks(npix);
     hipLaunchKernelGGL(sqdiff_images_kernel, dim3((unsigned)nblk, (unsigned)B), dim3(256), 0, st, x, y, npix, static_cast<double*>(workspace));
-    double* im = reinterpret_cast<double*>(static_cast<char*>(workspace) + round256((size_t)B * nblk * sizeof(double)));
+    double* im = reinterpret_cast<double*>(static_cast<char*>(workspace) + emd::round256((size_t)B * nblk * sizeof(double)));
     hipLaunchKernelGGL(image_sums_kernel<1>, dim3((unsigned)B), dim3(256), 0, st, static_cast<const double*>(workspace), nblk, 1.0 / (double)npix, im);
     hipLaunchKernelGGL(psnr_final_kernel, dim3(1), dim3(256), 0, st, static_cast<const double*>(im), B,
                        (double)data_range * (double)data_range, out);

@@ -1,5 +1,9 @@
-// What the single-channel image stencils share (ssim.hip: the metrics; filters.hip: the classical filters): the window taps as a
-// kernel argument, the vertical 1-D pass on a register ring, and the fixed-order sums.  One definition of each.
+// What the single-channel image operations share, one definition of each:
+//   the window taps as a kernel argument, the vertical 1-D pass on a register ring    ssim.hip (the metrics), filters.hip (the
+//                                                                                     classical filters)
+//   wave_sum_lane0, block_sum_fixed: the fixed-order sums of doubles                  those two, wavelet.hip, harvest.hip
+//   block_sum_thread0: one double per thread, behind a barrier of its own             harvest.hip
+// The host helpers they share (overlap, round256, tiles_of) are in emd_common.hpp, the median's selection in radix_select.hpp.
 #pragma once
 
 #include "emd_common.hpp"
@@ -46,6 +50,16 @@ __device__ __forceinline__ double wave_sum_lane0(double v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
+}
+
+// Sum of one double per thread over the 256 threads of a workgroup: lanes, then the four waves, in a fixed order.  Valid in
+// thread 0.  sh: 4 doubles, not otherwise in use between two calls' barriers.
+__device__ __forceinline__ double block_sum_thread0(double v, double* sh) {
+    v = wave_sum_lane0(v);
+    __syncthreads();   // sh may still be read from the previous call
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
 // Sum of p[0], p[stride], ..., p[(n - 1) * stride] by the 256 threads of a workgroup, in a fixed order (every thread returns it).

@@ -16,6 +16,7 @@
 #include <climits>
 #include <cmath>
 
+#include "radix_select.hpp"
 #include "stencil_rows.hpp"
 
 namespace {
@@ -222,56 +223,9 @@ __global__ __launch_bounds__(256) void wavelet_synthesis_kernel(const float* __r
     }
 }
 
-// ---- the noise estimate: exact median of the non-zero |d| by radix selection ------------------------------------------------
-// The bit patterns of |d| order as unsigned integers.  Pass q = 0..3 counts, for either middle rank, the coefficients whose
-// higher bits equal that rank's prefix, by the 8 bits [31 - 8q .. 24 - 8q]; the next launch finds the bin that holds the rank.
-// hist: [B][4 passes][2 ranks][256]; state: [B][4 passes][8] = (prefix 0, prefix 1, rank 0, rank 1, count of non-zeros) that
-// pass q works with.  All counts are integers: the atomics cannot change a result.
-constexpr int kStateWords = 8;
-
-// From the histograms of pass q and the state that pass worked with: the state of pass q + 1 into st (after pass 3: the prefixes
-// are the two middle values' bit patterns).  Every thread of the workgroup calls it; st is valid after the call.
-__device__ void select_resolve(const unsigned* __restrict__ hist, const unsigned* __restrict__ prev, int q, unsigned (*sc)[256],
-                               unsigned* st) {
-    const int tid = threadIdx.x;
-    const unsigned n0 = hist[tid], n1 = hist[256 + tid];
-    __syncthreads();   // sc and st may still be read
-    sc[0][tid] = n0;
-    sc[1][tid] = n1;
-    if (tid < kStateWords) st[tid] = 0;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned a0 = tid >= off ? sc[0][tid - off] : 0u, a1 = tid >= off ? sc[1][tid - off] : 0u;
-        __syncthreads();
-        sc[0][tid] += a0;
-        sc[1][tid] += a1;
-        __syncthreads();
-    }
-    unsigned prefix0 = 0, prefix1 = 0, rank0, rank1, count;
-    if (q == 0) {
-        count = sc[0][255];   // zeros are never counted
-        rank0 = count ? (count - 1) / 2 : 0;
-        rank1 = count / 2;
-    } else {
-        prefix0 = prev[0];
-        prefix1 = prev[1];
-        rank0 = prev[2];
-        rank1 = prev[3];
-        count = prev[4];
-    }
-    const unsigned i0 = sc[0][tid], i1 = sc[1][tid];
-    if (n0 && i0 - n0 <= rank0 && rank0 < i0) {
-        st[0] = (prefix0 << 8) | (unsigned)tid;
-        st[2] = rank0 - (i0 - n0);
-    }
-    if (n1 && i1 - n1 <= rank1 && rank1 < i1) {
-        st[1] = (prefix1 << 8) | (unsigned)tid;
-        st[3] = rank1 - (i1 - n1);
-    }
-    if (tid == 0) st[4] = count;
-    __syncthreads();
-}
-
+// ---- the noise estimate: exact median of the non-zero |d| by radix selection (radix_select.hpp) ------------------------------
+// The key is |d|'s bit pattern, and the exact zeros are left out (as skimage drops them): the count is what pass 0 counted.  Pass
+// q > 0 resolves pass q - 1 at the head of every workgroup; the threshold kernel resolves pass 3.
 // grid (chunks, B): one pass over d[b * stride + 0 .. n - 1]
 __global__ __launch_bounds__(256) void wavelet_select_kernel(const float* __restrict__ d, long stride, long n, unsigned* __restrict__ hist,
                                                              unsigned* __restrict__ state, int pass) {
@@ -280,31 +234,31 @@ __global__ __launch_bounds__(256) void wavelet_select_kernel(const float* __rest
     __shared__ unsigned st[kStateWords];
     const int tid = threadIdx.x;
     const long b = blockIdx.y;
-    unsigned* hb = hist + (b * 4 + pass) * 512;
-    unsigned* sb = state + (b * 4 + pass) * kStateWords;
+    unsigned* hb = hist + select_hist_at(b, pass);
+    unsigned* sb = state + select_state_at(b, pass);
     h[0][tid] = 0;
     h[1][tid] = 0;
+    unsigned prefix0 = 0, prefix1 = 0;
     if (pass > 0) {
-        select_resolve(hb - 512, sb - kStateWords, pass - 1, sc, st);
+        select_resolve(hb - kSelHistWords, sb - kStateWords, pass - 1, sc, st);
         if (blockIdx.x == 0 && tid < kStateWords) sb[tid] = st[tid];
+        prefix0 = st[0];
+        prefix1 = st[1];
     } else {
-        if (tid < kStateWords) st[tid] = 0;
         __syncthreads();
     }
-    const unsigned prefix0 = st[0], prefix1 = st[1];
-    const int shift = 24 - 8 * pass;
     const long begin = (long)blockIdx.x * kSelChunk, end = begin + kSelChunk < n ? begin + kSelChunk : n;
     const float* db = d + b * stride;
     for (long i = begin + tid; i < end; i += 256) {
-        const unsigned key = __float_as_uint(db[i]) & 0x7fffffffu;
+        const unsigned key = magnitude_key(db[i]);
         if (key == 0) continue;   // +0 and -0: skimage drops the exact zeros
-        const unsigned bin = (key >> shift) & 255u, high = pass ? key >> (shift + 8) : 0u;
-        if (high == prefix0) atomicAdd(&h[0][bin], 1u);
-        if (high == prefix1) atomicAdd(&h[1][bin], 1u);
+        if (pass == 0)
+            select_count_first(h, key);
+        else
+            select_count(h, key, pass, prefix0, prefix1);
     }
     __syncthreads();
-    if (h[0][tid]) atomicAdd(&hb[tid], h[0][tid]);
-    if (h[1][tid]) atomicAdd(&hb[256 + tid], h[1][tid]);
+    select_flush<2>(h, hb);
 }
 
 // ---- sigma and the thresholds: grid (B) -----------------------------------------------------------------------------------
@@ -325,8 +279,8 @@ __global__ __launch_bounds__(256) void wavelet_threshold_kernel(LevelSums ls, co
     __shared__ unsigned st[kStateWords];
     const long b = blockIdx.x;
     if (sigma < 0.f) {
-        select_resolve(hist + (b * 4 + 3) * 512, state + (b * 4 + 3) * kStateWords, 3, sc, st);
-        const float med = st[4] ? (__uint_as_float(st[0]) + __uint_as_float(st[1])) * 0.5f : 0.f;
+        select_resolve(hist + select_hist_at(b, 3), state + select_state_at(b, 3), 3, sc, st);
+        const float med = (__uint_as_float(st[0]) + __uint_as_float(st[1])) * 0.5f;   // nothing counted: the keys are 0, +0.0f
         sigma = (float)((double)med / kMadToSigma);
     }
     if (sigma_used && threadIdx.x == 0) sigma_used[b] = sigma;
@@ -344,14 +298,6 @@ __global__ __launch_bounds__(256) void wavelet_threshold_kernel(LevelSums ls, co
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-
-inline int tiles_of(int n, int t) { return (n + t - 1) / t; }
-inline size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return na && nb && pa < pb + nb && pb < pa + na;
-}
 
 bool taps_ok(int ntaps) { return ntaps >= 2 && ntaps <= kMaxTaps && ntaps % 2 == 0; }
 
@@ -397,21 +343,21 @@ bool geometry(int B, int H, int W, int L, int levels, Geometry* g) {
     size_t bytes = 0;
     for (int l = 1; l < levels; ++l) {
         g->scratch[l] = bytes;
-        bytes += round256((size_t)B * g->nH[l] * g->nW[l] * sizeof(float));
+        bytes += emd::round256((size_t)B * g->nH[l] * g->nW[l] * sizeof(float));
     }
     for (int l = 1; l <= levels; ++l) {
         g->part[l] = bytes;
-        bytes += round256((size_t)B * 3 * tiles_of(g->nH[l], kATH) * tiles_of(g->nW[l], kTW) * sizeof(double));
+        bytes += emd::round256((size_t)B * 3 * emd::tiles_of(g->nH[l], kATH) * emd::tiles_of(g->nW[l], kTW) * sizeof(double));
     }
     g->transform_bytes = bytes;
     g->pyr_off = bytes;
-    bytes += round256((size_t)B * g->pyramid * sizeof(float));
+    bytes += emd::round256((size_t)B * g->pyramid * sizeof(float));
     g->thr_off = bytes;
-    bytes += round256((size_t)B * levels * 3 * sizeof(float));
+    bytes += emd::round256((size_t)B * levels * 3 * sizeof(float));
     g->hist_off = bytes;
-    bytes += round256((size_t)B * 4 * 512 * sizeof(unsigned));
+    bytes += select_hist_bytes(B);
     g->state_off = bytes;
-    bytes += round256((size_t)B * 4 * kStateWords * sizeof(unsigned));
+    bytes += select_state_bytes(B);
     g->filter_bytes = bytes;
     return true;
 }
@@ -445,8 +391,8 @@ int run_forward(const Geometry& g, const float* x, float* pyr, char* ws, int B, 
         float* ca = l == g.levels ? pyr : reinterpret_cast<float*>(ws + g.scratch[l]);
         const long ca_stride = l == g.levels ? g.pyramid : (long)g.nH[l] * g.nW[l];
         double* part = sums ? reinterpret_cast<double*>(ws + g.part[l]) : nullptr;
-        const int tiles_x = tiles_of(g.nW[l], kTW);
-        const dim3 grid((unsigned)(tiles_x * tiles_of(g.nH[l], kATH)), (unsigned)B);
+        const int tiles_x = emd::tiles_of(g.nW[l], kTW);
+        const dim3 grid((unsigned)(tiles_x * emd::tiles_of(g.nH[l], kATH)), (unsigned)B);
 #define EMD_LAUNCH(LL)                                                                                                              \
     hipLaunchKernelGGL((wavelet_analysis_kernel<LL>), grid, dim3(256), 0, st, in, in_stride, g.nH[l - 1], g.nW[l - 1], ca, ca_stride, \
                        pyr + g.det[l], g.pyramid, g.nH[l], g.nW[l], tiles_x, taps, part);
@@ -466,8 +412,8 @@ int run_inverse(const Geometry& g, const float* pyr, float* out, char* ws, int B
         const long ca_stride = l == g.levels ? g.pyramid : (long)g.nH[l] * g.nW[l];
         float* o = l == 1 ? out : reinterpret_cast<float*>(ws + g.scratch[l - 1]);
         const int oH = g.nH[l - 1], oW = g.nW[l - 1];
-        const int tiles_x = tiles_of(oW, kTW);
-        const dim3 grid((unsigned)(tiles_x * tiles_of(oH, kSTH)), (unsigned)B);
+        const int tiles_x = emd::tiles_of(oW, kTW);
+        const dim3 grid((unsigned)(tiles_x * emd::tiles_of(oH, kSTH)), (unsigned)B);
         const float* t = thr ? thr + (l - 1) * 3 : nullptr;
 #define EMD_LAUNCH(LL)                                                                                                             \
     hipLaunchKernelGGL((wavelet_synthesis_kernel<LL>), grid, dim3(256), 0, st, ca, ca_stride, pyr + g.det[l], g.pyramid, g.nH[l],  \
@@ -566,8 +512,8 @@ extern "C" int emd_wavelet_forward_f32(const float* x, float* pyramid, int B, in
     rc = check_workspace(who, workspace, workspace_bytes, g.transform_bytes, B);
     if (rc != EMD_OK || B == 0) return rc;
     const size_t nx = (size_t)B * H * W * sizeof(float), np = (size_t)B * g.pyramid * sizeof(float);
-    EMD_REQUIRE(!overlap(x, nx, pyramid, np), EMD_E_INVALID, "emd_wavelet_forward_f32: pyramid may not alias x");
-    EMD_REQUIRE(!overlap(workspace, g.transform_bytes, x, nx) && !overlap(workspace, g.transform_bytes, pyramid, np), EMD_E_INVALID,
+    EMD_REQUIRE(!emd::overlap(x, nx, pyramid, np), EMD_E_INVALID, "emd_wavelet_forward_f32: pyramid may not alias x");
+    EMD_REQUIRE(!emd::overlap(workspace, g.transform_bytes, x, nx) && !emd::overlap(workspace, g.transform_bytes, pyramid, np), EMD_E_INVALID,
                 "emd_wavelet_forward_f32: the workspace may not alias x or pyramid");
     return run_forward(g, x, pyramid, static_cast<char*>(workspace), B, ntaps, make_taps(rec_lo_host, ntaps), false,
                        static_cast<hipStream_t>(stream));
@@ -582,8 +528,8 @@ extern "C" int emd_wavelet_inverse_f32(const float* pyramid, float* out, int B, 
     rc = check_workspace(who, workspace, workspace_bytes, g.transform_bytes, B);
     if (rc != EMD_OK || B == 0) return rc;
     const size_t nx = (size_t)B * H * W * sizeof(float), np = (size_t)B * g.pyramid * sizeof(float);
-    EMD_REQUIRE(!overlap(out, nx, pyramid, np), EMD_E_INVALID, "emd_wavelet_inverse_f32: out may not alias pyramid");
-    EMD_REQUIRE(!overlap(workspace, g.transform_bytes, out, nx) && !overlap(workspace, g.transform_bytes, pyramid, np), EMD_E_INVALID,
+    EMD_REQUIRE(!emd::overlap(out, nx, pyramid, np), EMD_E_INVALID, "emd_wavelet_inverse_f32: out may not alias pyramid");
+    EMD_REQUIRE(!emd::overlap(workspace, g.transform_bytes, out, nx) && !emd::overlap(workspace, g.transform_bytes, pyramid, np), EMD_E_INVALID,
                 "emd_wavelet_inverse_f32: the workspace may not alias pyramid or out");
     return run_inverse(g, pyramid, out, static_cast<char*>(workspace), B, ntaps, make_taps(rec_lo_host, ntaps), nullptr,
                        static_cast<hipStream_t>(stream));
@@ -602,11 +548,11 @@ extern "C" int emd_filter_wavelet_f32(const float* x, float* out, int B, int H, 
     rc = check_workspace(who, workspace, workspace_bytes, g.filter_bytes, B);
     if (rc != EMD_OK || B == 0) return rc;
     const size_t nx = (size_t)B * H * W * sizeof(float);
-    EMD_REQUIRE(!overlap(x, nx, out, nx), EMD_E_INVALID, "emd_filter_wavelet_f32: out may not alias x");
-    EMD_REQUIRE(!overlap(workspace, g.filter_bytes, x, nx) && !overlap(workspace, g.filter_bytes, out, nx), EMD_E_INVALID,
+    EMD_REQUIRE(!emd::overlap(x, nx, out, nx), EMD_E_INVALID, "emd_filter_wavelet_f32: out may not alias x");
+    EMD_REQUIRE(!emd::overlap(workspace, g.filter_bytes, x, nx) && !emd::overlap(workspace, g.filter_bytes, out, nx), EMD_E_INVALID,
                 "emd_filter_wavelet_f32: the workspace may not alias x or out");
-    EMD_REQUIRE(!sigma_used || (!overlap(sigma_used, (size_t)B * sizeof(float), workspace, g.filter_bytes) &&
-                                !overlap(sigma_used, (size_t)B * sizeof(float), out, nx)),
+    EMD_REQUIRE(!sigma_used || (!emd::overlap(sigma_used, (size_t)B * sizeof(float), workspace, g.filter_bytes) &&
+                                !emd::overlap(sigma_used, (size_t)B * sizeof(float), out, nx)),
                 EMD_E_INVALID, "emd_filter_wavelet_f32: sigma_used may not alias out or the workspace");
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
@@ -618,7 +564,7 @@ extern "C" int emd_filter_wavelet_f32(const float* x, float* out, int B, int H, 
     rc = run_forward(g, x, pyr, ws, B, ntaps, taps, true, st);
     if (rc != EMD_OK) return rc;
     if (sigma < 0.f) {
-        const hipError_t e = hipMemsetAsync(hist, 0, (size_t)B * 4 * 512 * sizeof(unsigned), st);
+        const hipError_t e = hipMemsetAsync(hist, 0, select_hist_bytes(B), st);
         if (e != hipSuccess) {
             emd::set_error("emd_filter_wavelet_f32: hipMemsetAsync: %s", hipGetErrorString(e));
             return EMD_E_LAUNCH;
@@ -634,7 +580,7 @@ extern "C" int emd_filter_wavelet_f32(const float* x, float* out, int B, int H, 
     LevelSums ls{};
     ls.levels = levels;
     for (int l = 1; l <= levels; ++l) {
-        ls.tiles[l - 1] = tiles_of(g.nH[l], kATH) * tiles_of(g.nW[l], kTW);
+        ls.tiles[l - 1] = emd::tiles_of(g.nH[l], kATH) * emd::tiles_of(g.nW[l], kTW);
         ls.off[l - 1] = (long)((g.part[l] - g.part[1]) / sizeof(double));
         ls.count[l - 1] = (double)g.nH[l] * (double)g.nW[l];
     }

@@ -134,6 +134,16 @@ def test_median_ties_signed_zero_and_parity():
     print(f"median with signed zeros / all negative: {got[:, col]} (numpy {want})")
     assert got[0, col] == 0.0 and np.array_equal(got[:, col], want)
     assert np.array_equal(got[:, 2], [np.count_nonzero(im) for im in x]) and np.array_equal(got[:, 3], [np.count_nonzero(im < 0) for im in x])
+    # an even count (66 x 70 = 4620: two chunks, the second ragged) whose lower middle value is negative and whose upper one is not:
+    # the two keys' top bytes lie on either side of 0x80, so the middle ranks part at the first pass
+    rng = np.random.default_rng(5)
+    z = rng.permutation(np.concatenate([-rng.uniform(0.5, 900.0, 2310), rng.uniform(0.5, 900.0, 2310)])).astype(np.float32)
+    lo, hi = np.sort(z)[2309:2311]
+    assert lo < 0.0 <= hi and int(lo.view(np.uint32)) >> 31 == 1 and int(hi.view(np.uint32)) >> 31 == 0
+    got = harvest.image_stats(up(z.reshape(1, 66, 70))).cpu().numpy()
+    want = np.median(z.astype(np.float64))
+    print(f"median with the middle values on either side of zero: {got[0, col]} (numpy {want})")
+    assert got[0, col] == want
 
 
 def test_estimate_noise_is_the_full_convolution_sum():

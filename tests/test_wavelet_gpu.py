@@ -215,6 +215,45 @@ def test_sigma_drops_exact_zeros():
             assert rel_l2(y0.cpu().numpy(), x) <= FACTOR * YARD_ROUNDTRIP
 
 
+def parted_image():
+    """[2, 130, 140]: one non-zero pixel in each 2 x 2 block, so that Haar's dd_1 (65 x 70 = 4550 coefficients: two chunks of the
+    selection, the second ragged) is half that pixel; as many magnitudes in [1, 3) as in [5, 7), ten blocks all zero.  The second
+    image is the first with one more block zeroed."""
+    rng = np.random.default_rng(41)
+    nb = 65 * 70
+    mag = np.concatenate([rng.uniform(1.0, 3.0, (nb - 10) // 2), rng.uniform(5.0, 7.0, (nb - 10) // 2), np.zeros(10)])
+    mag = rng.permutation(mag) * rng.choice([-1.0, 1.0], nb)
+    r, c = np.divmod(np.arange(nb), 70)
+    x = np.zeros((2, 130, 140), np.float32)
+    x[0, 2 * r + rng.integers(0, 2, nb), 2 * c + rng.integers(0, 2, nb)] = mag
+    x[1] = x[0]
+    k = int(np.flatnonzero(mag)[0])
+    x[1, 2 * r[k]:2 * r[k] + 2, 2 * c[k]:2 * c[k] + 2] = 0.0
+    return x
+
+
+def middle_values_part_at_the_top_byte(dd1):
+    """The precondition of the test below, on a [2, 65, 70] dd_1: an even count of non-zeros in the first image, whose two middle
+    magnitudes lie on either side of 2.0 (bit patterns 0x3f...... and 0x40......), and an odd count in the second."""
+    a = [np.sort(np.abs(d[d != 0])) for d in dd1]
+    lo, hi = a[0][a[0].size // 2 - 1:a[0].size // 2 + 1]
+    return (dd1.shape == (2, 65, 70) and a[0].size % 2 == 0 and a[0].size < dd1[0].size and a[1].size == a[0].size - 1
+            and lo < 2.0 <= hi and int(lo.view(np.uint32)) >> 24 != int(hi.view(np.uint32)) >> 24)
+
+
+def test_sigma_when_the_middle_ranks_part_at_the_first_pass():
+    x = up(parted_image())
+    _, sig = filters.denoise_wavelet(x, "db1", 1, return_sigma=True)
+    dd1 = filters.wavedec2(x, "db1", 1)[-1]["dd"].cpu().numpy()
+    assert middle_values_part_at_the_top_byte(dd1)
+    for b in range(2):
+        want = numpy_sigma(dd1[b])
+        e = abs(float(sig[b]) - want) / want
+        print(f"sigma, middle ranks in two bins of pass 0, image {b}: {float(sig[b]):.9e} (numpy {want:.9e}); relative {e:.2e}; "
+              f"bound {SIGMA_RTOL:.1e}")
+        assert e <= SIGMA_RTOL
+
+
 # ---- the denoiser against float64 -----------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("case", cases(), ids=cid)
