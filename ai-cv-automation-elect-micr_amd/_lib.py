@@ -443,6 +443,14 @@ SIGNATURES = {
     "emd_image_stats_f64": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # x y B n stats stream
     "emd_scale01_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]),
+    # ---- the 2-D FFT and the radial frequency profile (csrc/fft.hip)
+    "emd_radial_bins": (C.c_int, [C.c_int]),
+    "emd_rfft2_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    # x B S spec workspace ws_bytes stream
+    "emd_rfft2_f64": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_freq_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    # x B S profile freq_stats workspace ws_bytes stream
+    "emd_freq_stats_f64": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

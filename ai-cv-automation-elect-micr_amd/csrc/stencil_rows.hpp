@@ -1,8 +1,9 @@
 // What the single-channel image operations share, one definition of each:
 //   the window taps as a kernel argument, the vertical 1-D pass on a register ring    ssim.hip (the metrics), filters.hip (the
 //                                                                                     classical filters)
-//   wave_sum_lane0, block_sum_fixed: the fixed-order sums of doubles                  those two, wavelet.hip, harvest.hip
-//   block_sum_thread0: one double per thread, behind a barrier of its own             harvest.hip
+//   wave_sum_lane0, block_sum_fixed: the fixed-order sums of doubles                  those two, wavelet.hip, harvest.hip, fft.hip
+//   block_sum_thread0: one double per thread, behind a barrier of its own             harvest.hip, fft.hip
+//   block_tree_sum: block_sum_fixed's tree over one double per thread                 fft.hip
 // The host helpers they share (overlap, round256, tiles_of) are in emd_common.hpp, the median's selection in radix_select.hpp.
 #pragma once
 
@@ -62,11 +63,10 @@ __device__ __forceinline__ double block_sum_thread0(double v, double* sh) {
     return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
-// Sum of p[0], p[stride], ..., p[(n - 1) * stride] by the 256 threads of a workgroup, in a fixed order (every thread returns it).
-__device__ double block_sum_fixed(const double* __restrict__ p, int n, int stride, double* sh) {
+// Sum of one double per thread over the 256 threads of a workgroup as a binary tree in LDS, in a fixed order (every thread returns
+// it).  sh: 256 doubles.
+__device__ double block_tree_sum(double s, double* sh) {
     const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int i = tid; i < n; i += 256) s += p[(long)i * stride];
     __syncthreads();   // sh may still be read from the previous call
     sh[tid] = s;
     __syncthreads();
@@ -75,6 +75,13 @@ __device__ double block_sum_fixed(const double* __restrict__ p, int n, int strid
         __syncthreads();
     }
     return sh[0];
+}
+
+// Sum of p[0], p[stride], ..., p[(n - 1) * stride] by the 256 threads of a workgroup, in a fixed order (every thread returns it).
+__device__ double block_sum_fixed(const double* __restrict__ p, int n, int stride, double* sh) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += p[(long)i * stride];
+    return block_tree_sum(s, sh);
 }
 
 }  // namespace

@@ -1171,6 +1171,35 @@ int emd_image_stats_f64(const float* x, int B, int H, int W, double* stats, void
 int emd_scale01_f32(const float* x, float* y, int B, long n, const double* stats, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The 2-D FFT and the radial frequency profile (csrc/fft.hip): img_params.m:53-77, the four *Freq2048 fields.
+ * x is [B,S,S] float32, S a power of two, 8 <= S <= 4096 (one line of 4096 complex doubles is 64 KiB of LDS); finite values.
+ *
+ * Transform: F = fft2(double(x)), forward, unnormalised, in double.  spec is numpy.fft.rfft2's layout, [B][S][S/2 + 1] interleaved
+ * (re, im), unshifted: ky = 0..S-1, kx = 0..S/2.
+ *
+ * Profile: with the signed frequencies ky, kx in [-S/2, S/2 - 1] (fftshift, mid = S/2 + 1), n = ky^2 + kx^2 and
+ * R = ceil(sqrt(2 mid^2)) (1450 at 2048), a pixel's 0-based bin is ceil(sqrt(n)): the smallest integer t with t^2 >= n, in integer
+ * arithmetic.  radialProfile[t] = the sum of |F| over the bin; radialFreqs[t] = sqrt(n) / R of the bin's member with the largest kx,
+ * and among those the largest ky (the last one the reference's loop -- col outer, row inner -- visits; not a bin centre); a bin
+ * without a member has profile 0 and frequency 0 and still counts below.
+ *     p = radialProfile / sum(radialProfile) * radialFreqs          [R]
+ *     freq_stats[b] = { sum(p), std(p) with R - 1, skewness(p), kurtosis(p) }   (EMD_NFREQ doubles; m3 / m2^1.5 and m4 / m2^2 of the
+ *                      population central moments about sum(p) / R, two-pass; "mean" is the SUM, as in the reference)
+ * An all-zero image has sum(radialProfile) = 0: p and the four are NaN.  A constant non-zero image has all its energy at n = 0, whose
+ * frequency is 0: p = 0, mean = 0, std = 0, and skewness and kurtosis are 0/0 = NaN.  Both as in MATLAB.
+ * No floating-point atomics and fixed summation orders: bitwise reproducible, and an image's result does not depend on B.
+ * 0 <= B <= 65535 (B == 0 is a no-op); the workspace is the caller's, 16-byte aligned, as are spec and freq_stats; the twiddle
+ * table is written into it by a kernel on every call; launches only, on `stream`, no host synchronisation: capturable. */
+#define EMD_NFREQ 4
+int emd_radial_bins(int S); /* R; 0 for an invalid S */
+size_t emd_rfft2_workspace_bytes(int B, int S);
+int emd_rfft2_f64(const float* x, int B, int S, double* spec, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_freq_stats_workspace_bytes(int B, int S);
+/* profile [B][R] = p, may be NULL; freq_stats [B][EMD_NFREQ] (both DEVICE, doubles) */
+int emd_freq_stats_f64(const float* x, int B, int S, double* profile, double* freq_stats, void* workspace, size_t workspace_bytes,
+                       emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
