@@ -85,6 +85,13 @@ SIGNATURES = {
     "emd_sep3x3_fused_s2_genres_f32": (C.c_int, [_c_float_p, C.c_int, _c_float_p, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p,
                                                  _c_float_p, _c_float_p, _c_float_p, C.c_int, C.c_int, _c_float_p, _c_float_p, C.c_int,
                                                  _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "emd_sep3x3_fused_fold_supported": (C.c_int, [C.c_int] * 4),
+    # x ldx dw whi wlo scale1 shift1 scale2 shift2 res ldres wfin z B H W Cin Cout act stream
+    "emd_sep3x3_fused_fold_f32": (C.c_int, [_c_float_p, C.c_int, _c_float_p, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p,
+                                            _c_float_p, _c_float_p, _c_float_p, C.c_int, _c_float_p, _c_float_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # z scale shift y B H W act stream
+    "emd_cout1_gather9_f32": (C.c_int, [_c_float_p, C.c_float, C.c_float, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "emd_sep3x3_fused_s2_reflect_f32": (C.c_int, [_c_float_p, C.c_int, _c_float_p, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p,
                                           _c_float_p, _c_float_p, _c_float_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -62,6 +62,10 @@ __device__ __forceinline__ float load_s1(const void* sbase, unsigned voff) {
 __device__ __forceinline__ void store_nt_d(const void* sbase, unsigned voff, unsigned v) {
     asm volatile("global_store_dword %0, %1, %2 nt" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
 }
+// One dword per lane through a 64-bit lane address, cached (sep_pipe.hip's folded epilogue: the tap planes are read back by the next launch).
+__device__ __forceinline__ void store_d(void* dst, float v) {
+    asm volatile("global_store_dword %0, %1, off" ::"v"(dst), "v"(v) : "memory");
+}
 // The pointer form of the 16-byte non-temporal store.  Inline asm on purpose: behind a run-time flag, "if (nt) __builtin_nontemporal_store
 // else plain store" is merged into ONE plain store by the optimizer (the merged store keeps only the metadata both sides share).
 __device__ __forceinline__ void store_nt16(void* dst, f32x4 v) {

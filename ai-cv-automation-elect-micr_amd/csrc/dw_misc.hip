@@ -420,6 +420,57 @@ __global__ __launch_bounds__(256) void conv3x3_cout1_roll(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// The spatial half of a 3x3 conv to one channel whose channel sums exist as nine tap planes z [9][B][H][W] (sep_pipe.hip, FOLD):
+// out[b][y][x] = cout1_out(sum_t z_t[b][y + t / 3 - 1][x + t % 3 - 1]), taps outside the image contribute zero (TF SAME), added in the
+// order t = 0..8.  A thread owns four pixels of a row: per tap row one aligned 16-byte load of the three planes plus the pixel left of
+// them (dx = -1) and right of them (dx = +1); as in dw3x3_s1_roll every load is unconditional (indices clamped into the image) and a
+// padding value is replaced by zero where it is used.  Every plane element is read exactly once: there is nothing to roll.
+__global__ __launch_bounds__(256) void cout1_gather9_kernel(const float* __restrict__ z, float scale, float shift, float* __restrict__ y,
+                                                            int H, int W, long plane, long nthreads, int act) {
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (tid >= nthreads) return;
+    int x4, oy;
+    long t = emd::divmod(tid, W >> 2, x4);
+    const long b = emd::divmod(t, H, oy);
+    const int ox = x4 * 4;
+    const bool hasl = ox > 0, hasr = ox + 4 < W;
+    const int xl = hasl ? -1 : 0, xr = hasr ? 4 : 3;
+    float4 c[9];
+    float e[9];   // the edge pixel of the taps with dx != 0
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        int iy = oy - 1 + i;
+        iy = iy < 0 ? 0 : (iy >= H ? H - 1 : iy);
+        const float* row = z + ((b * H + iy) * (long)W + ox);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float* pr = row + (i * 3 + j) * plane;
+            c[i * 3 + j] = *reinterpret_cast<const float4*>(pr);
+            e[i * 3 + j] = j == 1 ? 0.f : pr[j == 0 ? xl : xr];
+        }
+    }
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int iy = oy - 1 + i;
+        const bool ok = iy >= 0 && iy < H;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float4 v = c[i * 3 + j];
+            float a0, a1, a2, a3;
+            if (j == 0) { a0 = hasl ? e[i * 3] : 0.f; a1 = v.x; a2 = v.y; a3 = v.z; }
+            else if (j == 1) { a0 = v.x; a1 = v.y; a2 = v.z; a3 = v.w; }
+            else { a0 = v.y; a1 = v.z; a2 = v.w; a3 = hasr ? e[i * 3 + 2] : 0.f; }
+            s[0] += ok ? a0 : 0.f; s[1] += ok ? a1 : 0.f; s[2] += ok ? a2 : 0.f; s[3] += ok ? a3 : 0.f;
+        }
+    }
+    float4 o;
+    o.x = cout1_out(s[0], 0.f, 0, scale, shift, act); o.y = cout1_out(s[1], 0.f, 0, scale, shift, act);
+    o.z = cout1_out(s[2], 0.f, 0, scale, shift, act); o.w = cout1_out(s[3], 0.f, 0, scale, shift, act);
+    *reinterpret_cast<float4*>(y + ((b * H + oy) * (long)W + ox)) = o;
+}
+
+// ------------------------------------------------------------------------------------------------
 // tf.image.resize_images: bilinear, align_corners=False, legacy sampling src = dst * (in/out).
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ x, int ldx,
                                                               float* __restrict__ y, int ldy, int Hi, int Wi,
@@ -988,6 +1039,24 @@ extern "C" int emd_conv3x3_cout1_f32(const float* x, int ldx, const float* w, fl
     hipLaunchKernelGGL(conv3x3_cout1_kernel, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), x, ldx, w, scale,
                        shift, y, H, W, LP, npix, act, pre_bias, pre_relu);
     return emd::check_launch("conv3x3_cout1_kernel");
+}
+
+// The nine-plane gather behind emd_sep3x3_fused_fold_f32 (the kernel above): same scalar scale / shift / act codes as emd_conv3x3_cout1_f32.
+// Shapes: the spatial part of emd_sep3x3_fused_fold_supported (H % 8 == 0, W % 16 == 0) -- the planes of any other shape have no producer.
+extern "C" int emd_cout1_gather9_f32(const float* z, float scale, float shift, float* y, int B, int H, int W, int act, emd_stream_t stream) {
+    EMD_REQUIRE(z && y, EMD_E_INVALID, "emd_cout1_gather9_f32: null pointer");
+    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_cout1_gather9_f32: bad shape");
+    EMD_REQUIRE(act >= 0 && act <= 2, EMD_E_INVALID, "emd_cout1_gather9_f32: act must be 0, 1 or 2");
+    EMD_REQUIRE(H % 8 == 0 && W % 16 == 0, EMD_E_UNSUPPORTED, "emd_cout1_gather9_f32: needs H%8==0, W%16==0 (emd_sep3x3_fused_fold_supported)");
+    EMD_REQUIRE(emd::aligned16(z) && emd::aligned16(y), EMD_E_ALIGN, "emd_cout1_gather9_f32: pointers must be 16-byte aligned");
+    if (B == 0) return EMD_OK;
+    const long plane = (long)B * H * W, nthreads = plane / 4;
+    unsigned nb;
+    int rc = grid_for(nthreads, &nb);
+    if (rc != EMD_OK) return rc;
+    hipLaunchKernelGGL(cout1_gather9_kernel, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), z, scale, shift, y, H, W, plane,
+                       nthreads, act);
+    return emd::check_launch("cout1_gather9_kernel");
 }
 
 extern "C" int emd_resize_bilinear_f32(const float* x, int ldx, float* y, int ldy, int B, int Hi, int Wi, int Ho,

@@ -600,12 +600,24 @@ struct Run {
         ar->release(deconv1_s);
         T4 d0a, residual0_d;
         sep_and_projection("deconv0_a", "residual0_d", deconv1to0, &d0a, &residual0_d);
+        const LayerParams& pf = P["deconv_final"];   // no output clip in D (:396); D' clips to [0, 1] in-graph (denoiser-multi-gpu.py:534-538)
+        if (emd::g_knobs.fold_final && emd_sep3x3_fused_supported(S, S, F0, F0, 1, 1) && emd_sep3x3_fused_fold_supported(S, S, F0, F0)) {
+            // deconv_final's channel sum in deconv0_b's epilogue, its spatial sum in the gather (the Python engine's _fold_final rule)
+            const LayerParams& pb = P["deconv0_b"];
+            float* z = static_cast<float*>(raw((size_t)9 * B * S * S * 4));
+            if (live()) {
+                call(emd_sep3x3_fused_fold_f32(d0a.ptr(), d0a.ld, pb.dw, pb.pw.hi, pb.pw.lo, pb.scale, pb.shift, pb.scale2, pb.shift2,
+                                               residual0_d.ptr(), residual0_d.ld, pf.wfin, z, B, S, S, F0, F0, EMD_ACT_RELU6, st));
+                call(emd_cout1_gather9_f32(z, pf.scale_f, pf.shift_f, yout, B, S, S, g->twin ? 2 : 1, st));
+            }
+            free(deconv1to0); free(d0a); free(residual0_d);
+            ar->release(z);
+            return;
+        }
         T4 deconv0 = sep("deconv0_b", d0a, nullptr, &residual0_d);
         free(deconv1to0); free(d0a); free(residual0_d);
-        if (live()) {
-            const LayerParams& pf = P["deconv_final"];   // no output clip in D (:396); D' clips to [0, 1] in-graph (denoiser-multi-gpu.py:534-538)
+        if (live())
             call(emd_conv3x3_cout1_f32(deconv0.ptr(), deconv0.ld, pf.wfin, pf.scale_f, pf.shift_f, yout, B, S, S, F0, g->twin ? 2 : 1, 0.f, 0, st));
-        }
         free(deconv0);
     }
 };

@@ -592,6 +592,44 @@ extern "C" int emd_sep3x3_fused_f32(const float* x, int ldx, const float* dw, co
                            precision, 0, stream);
 }
 
+// The stride-1 block whose output feeds only a 3x3 convolution to one channel (deconv0_b -> deconv_final, machine_learning/denoiser.py:
+// 383-387), with that convolution's CHANNEL sum folded into the epilogue: y = the block's output (affine, activation, second affine,
+// + res, the arithmetic of emd_sep3x3_fused_f32) is not stored; z[t][b][h][w] = sum_c wfin[t][c] * y[b][h][w][c], t = 0..8, is -- nine
+// planes of B*H*W floats.  emd_cout1_gather9_f32 adds the nine shifted planes.  csrc/sep_pipe.hip (FOLD) only: there is no other form.
+extern "C" int emd_sep3x3_fused_fold_supported(int H, int W, int Cin, int Cout) {
+    emd::SepParams q{};
+    q.H = H; q.W = W; q.Cin = Cin; q.N = Cout; q.stride = 1; q.fold = 1;
+    return H >= 1 && W >= 1 && emd::sep_pipe_covers(q, 3);
+}
+
+extern "C" int emd_sep3x3_fused_fold_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
+                                         const float* scale1, const float* shift1, const float* scale2, const float* shift2,
+                                         const float* res, int ldres, const float* wfin, float* z, int B, int H, int W, int Cin, int Cout,
+                                         int act, emd_stream_t stream) {
+    EMD_REQUIRE(x && dw && whi && wlo && scale1 && shift1 && wfin && z, EMD_E_INVALID, "emd_sep3x3_fused_fold_f32: null pointer");
+    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_fold_f32: scale2/shift2 pair");
+    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_sep3x3_fused_fold_f32: bad shape");
+    EMD_REQUIRE(emd_sep3x3_fused_fold_supported(H, W, Cin, Cout), EMD_E_UNSUPPORTED,
+                "emd_sep3x3_fused_fold_f32: needs H%8==0, W%16==0, Cin%32==0, Cout==64 (use emd_sep3x3_fused_f32 + emd_conv3x3_cout1_f32)");
+    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_fold_f32: B > 65535");
+    EMD_REQUIRE(9L * W * (ldx > ldres ? ldx : ldres) < (1L << 31), EMD_E_UNSUPPORTED,
+                "emd_sep3x3_fused_fold_f32: 9 image rows of the input must span fewer than 2^31 floats");
+    EMD_REQUIRE(ldx % 4 == 0 && ldx >= Cin && (!res || (ldres % 4 == 0 && ldres >= Cout)), EMD_E_ALIGN,
+                "emd_sep3x3_fused_fold_f32: pixel strides must be multiples of 4 and >= the channel count");
+    EMD_REQUIRE(emd::aligned16(x) && emd::aligned16(dw) && emd::aligned16(whi) && emd::aligned16(wlo) && emd::aligned16(z) &&
+                    (!res || emd::aligned16(res)) && emd::aligned16(scale1) && emd::aligned16(shift1) && emd::aligned16(wfin) &&
+                    (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))),
+                EMD_E_ALIGN, "emd_sep3x3_fused_fold_f32: pointers must be 16-byte aligned");
+    if (B == 0) return EMD_OK;
+    SepParams p{};
+    p.x = x; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = nullptr; p.res = res;
+    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
+    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
+    p.ldx = ldx; p.ldy = 0; p.ldres = ldres; p.act = act; p.stride = 1;
+    p.fold_w = wfin; p.fold_z = z; p.fold = 1;
+    return emd::sep_pipe_launch(p, B, static_cast<hipStream_t>(stream));
+}
+
 // The stride-2 separable block (strided_conv_block(stride=2), machine_learning/denoiser.py:258, :273, :288) in one launch: x [B,H,W,Cin]
 // (H, W even; TF SAME = no padding before, one pixel after) -> y [B,H/2,W/2,Cout].  Split-bf16.  Same arithmetic as emd_dw3x3_f32(stride 2)
 // followed by emd_conv1x1_f32; the depthwise result never exists in memory.

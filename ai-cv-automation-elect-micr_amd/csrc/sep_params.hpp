@@ -36,12 +36,16 @@ struct SepParams {
     // [ox * rg_stride].  That instance has one output: its three pointers share the second output's storage and its three ints sit in
     // what was alignment padding, so the block keeps its size and offsets -- a longer block changes the code the compiler makes for
     // EVERY instance (argument loads regroup, scratch sizes and VGPR counts move), which this one must not.
+    // Folded final conv (fold != 0; sep_pipe.hip, the 4-wave 64-column FOLD instance: emd_sep3x3_fused_fold_f32): y is not stored -- the
+    // epilogue forms z_t[pixel] = sum_c fold_w[t][c] * y[pixel][c], t = 0..8, and writes nine planes fold_z [9][B][H][W].  One output too:
+    // its two pointers and its flag share the second output's storage in the same way.
     union { const uint16_t* W2hi; const float* rg_x; };
-    const uint16_t* W2lo;
-    float* y2;
+    union { const uint16_t* W2lo; const float* fold_w; };   // [9][64]: the 3x3 conv's taps, channel innermost
+    union { float* y2; float* fold_z; };
     union { const float* scale_b; const float* rg_a; };
     union { const float* shift_b; const float* rg_t; };
-    int N2, ldy2;
+    int N2;
+    union { int ldy2; int fold; };   // (fold means something only where N2 == 0: folded())
     int out_split;        // y is a split32 tensor (pitch ldy 4-byte units; N % 32 == 0): the consumer is a split32 GEMM
     int rg_ld;
     long long* stamps;    // dev hook: per-workgroup phase cycle sums (NULL otherwise)
@@ -50,6 +54,7 @@ struct SepParams {
     int xcd;              // workgroup -> tile map that gives each XCD (workgroup id mod 8) one contiguous run of tiles
     int rg_act;
 };
+inline bool folded(const SepParams& p) { return p.N2 == 0 && p.fold != 0; }   // a two-output launch keeps its pitch in the same word
 static_assert(sizeof(SepParams) == 232, "SepParams: the rg_* fields fill padding and share storage; see above before adding a field");
 
 // sep_pipe.hip: true when the LDS-DMA pipelined kernel covers the launch (stride 1, split-bf16, no generated input, W % 32 == 0)

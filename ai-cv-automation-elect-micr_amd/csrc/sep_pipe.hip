@@ -31,6 +31,8 @@
 // 512^2 x 128 -> 64 layer, slower on every shape.  profiles/r03_experiments.txt.)
 // vmcnt bookkeeping is exact for full tiles (every wave issues the same number of DMA pieces per step and, per tile, a fixed number
 // of stores), conservative otherwise.
+#include <type_traits>
+
 #include "sep_params.hpp"
 
 namespace {
@@ -55,7 +57,20 @@ __device__ __attribute__((aligned(16))) float g_zero_pipe[4096];
 // dw_misc.hip without its depthwise stage, same fma and clamp: residual0 of graph D) -- where the other instances prefetch the tile's
 // residual values a lane fetches the sixteen d of its pixels instead (as many loads, so the vmcnt arithmetic is the same; a half wave
 // reads one address) and the epilogue evaluates the expression for its channel: no [B,H/2,W/2,N] tensor is written and read back.
-template <int BN, bool DUAL, int MODE, bool OSPLIT, int NW = 8, int STRIDE = 1, int EPI = 1, bool GEN = false, bool RGEN = false>     // EPI: dwords a lane stores at a time (epilogue)
+// FOLD: the layer's output feeds only a 3x3 convolution to ONE channel (deconv0_b -> deconv_final of graph D, machine_learning/
+// denoiser.py:383-387), which is linear in it: out[p] = act(scale * sum_t z_t[p + off_t] + shift), z_t[p] = sum_c w[t][c] y[p][c].  z_t[p]
+// needs only pixel p, so the epilogue forms the nine sums from the finished values and stores them -- nine floats per pixel instead of
+// 64; emd_cout1_gather9_f32 (dw_misc.hip) does the spatial sum.  The pointwise MFMAs are issued with their operands SWAPPED (the A and B
+// fragment layouts of the 32x32x16 MFMA are the same: same products, same K order, the transposed tile), so that a lane holds 32 of ITS
+// pixel's 64 channels: register e of acc[0][j] = y^T[channel 32 j + 8 (e >> 2) + 4 (lane >> 5) + (e & 3)][pixel lane & 31] -- which is the
+// B operand layout (K = 2: k = lane >> 5) of the fp32 matrix instruction v_mfma_f32_32x32x2_f32.  The channel sum is therefore 32 of those
+// per tile, z^T[t][pixel] += w^T[t][c | c + 4] * y^T[c | c + 4][pixel], fp32 products and fp32 accumulation in the fixed order j, e; rows
+// t >= 9 of the A operand are zero.  Rows 0..8 of the result leave lane = pixel again: no cross-lane step at all.  (The lane-local form,
+// 32 x 9 fmaf per lane from a 4 KiB LDS table of per-channel taps plus one exchange with lane ^ 32, was measured first: 96 table reads
+// per wave and tile and 150 live registers, graph D 0.24 ms SLOWER than the pair of launches; profiles/r06_experiments.txt.)
+// Per-channel constants cannot sit in registers in this layout: scale / shift come from a 1 KiB LDS table, the A operands from a
+// 2.5 KiB one ([step][k][t < 9 | zero]), both filled once per workgroup.
+template <int BN, bool DUAL, int MODE, bool OSPLIT, int NW = 8, int STRIDE = 1, int EPI = 1, bool GEN = false, bool RGEN = false, bool FOLD = false>     // EPI: dwords a lane stores at a time (epilogue)
 __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p) {
     constexpr int TW = STRIDE == 2 ? 16 : 4 * NW, TH = STRIDE == 2 ? 4 : 8, BM = TH * TW;
     constexpr int PW = STRIDE * TW + 3 - STRIDE, PH = STRIDE * TH + 3 - STRIDE, PWS = PW | 1;   // patch pixels per row; slot pitch odd (see above): 34 -> 35, 18 -> 19, 33
@@ -75,9 +90,13 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
     constexpr int WN = STRIDE == 2 ? 4 : BN / 64, WM = NW / WN, TM = BM / WM / 32, TN = BN / WN / 32;   // a wave owns 32 TM rows x 32 TN columns
     constexpr int A_OFF = 2 * STAGE, B_OFF = A_OFF + A_BYTES;
     constexpr int GW_OFF = B_OFF + B_ONE * (BDBL ? 2 : 1);    // GEN: depthwise weights [chunk][tap][32] fp32, two chunks at most
-    constexpr int SMEM = GW_OFF + (GEN ? 2 * 9 * 128 : 0);
+    constexpr int FT_OFF = GW_OFF + (GEN ? 2 * 9 * 128 : 0);  // FOLD: [64 channels][scale1, shift1, scale2, shift2], then [32 steps][2 k][10] A operands
+    constexpr int FW_OFF = FT_OFF + 1024;
+    constexpr int SMEM = FT_OFF + (FOLD ? 1024 + 32 * 80 : 0);
     constexpr bool SWZ = DUAL;                                // patch chunks XORed with (pixel >> 1) & 3: the projection's centre reads
-    constexpr int E = 16 / EPI * TM * TN;                     // stores per wave and tile (exact when no lane is masked: full tiles)
+    constexpr int E = FOLD ? 5 : 16 / EPI * TM * TN;          // stores per wave and tile (exact when no lane is masked: full tiles)
+    static_assert(!FOLD || (BN == 64 && NW == 4 && !DUAL && !OSPLIT && STRIDE == 1 && EPI == 1 && !GEN && !RGEN && TM == 1 && TN == 2),
+                  "folded final conv: the 4-wave 64-column one-output instance");
     static_assert(!(DUAL && MODE != 1), "the two-output instances read the patch in stage 2");
     static_assert(!(DUAL && OSPLIT), "split32 output: one-output instances only");
     static_assert(PP >= 2 && PB >= 1 && SMEM <= (NW == 8 ? 160 : 80) * 1024, "shape");
@@ -188,6 +207,19 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
                 *reinterpret_cast<const f32x4*>(p.dw + (long)(rem >> 3) * p.Cin + ch * 32 + (rem & 7) * 4);
         }
     }
+    if constexpr (FOLD) {   // the two tables (read in the epilogue, long after the first barrier)
+        if (tid < 64) {
+            const bool two_ = p.scale2 != nullptr;
+            *reinterpret_cast<f32x4*>(smem + FT_OFF + tid * 16) =
+                f32x4{p.scale1[tid], p.shift1[tid], two_ ? p.scale2[tid] : 1.f, two_ ? p.shift2[tid] : 0.f};
+        }
+        for (int i = tid; i < 32 * 20; i += NW * 64) {   // step s = 16 j + e, k, row m: tap m of channel 32 j + 8 (e >> 2) + 4 k + (e & 3); m = 9: zero
+            const int s = i / 20, rem = i - s * 20, k = rem / 10, m = rem - k * 10;
+            const int ch = 32 * (s >> 4) + 8 * ((s & 15) >> 2) + 4 * k + (s & 3);
+            *reinterpret_cast<float*>(smem + FW_OFF + i * 4) = m < 9 ? p.fold_w[m * 64 + ch] : 0.f;
+        }
+        wait_lgkm0();
+    }
     auto load_d = [&](float (&dst)[PP]) {
 #pragma unroll
         for (int j = 0; j < PP; ++j) dst[j] = *psrc[j];
@@ -244,7 +276,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
     for (int j = 0; j < TN; ++j) {
         const int n = wn * (TN * 32) + j * 32 + fr;
         const int nn = out2 ? n - BN / 2 : n;
-        const bool valid = nn < nlim;
+        const bool valid = !FOLD && nn < nlim;    // (FOLD: the constants come from the LDS table)
         es1[j] = valid ? (out2 ? p.scale_b : p.scale1)[nn] : 0.f;
         et1[j] = valid ? (out2 ? p.shift_b : p.shift1)[nn] : 0.f;
         es2[j] = (valid && two) ? p.scale2[nn] : 1.f;
@@ -356,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
     // Residual values of the tile, requested after stage 1 of the tile's last step (TM <= 2: 16 TM TN registers, free once stage 1's
     // are dead): they land under stage 2 instead of stalling the epilogue behind every older DMA piece (vmcnt is in order).
     constexpr bool RPRE = TM <= 2 && !DUAL;
-    constexpr int R = RPRE ? 16 / EPI * TM * TN : 0;         // residual loads per wave and tile
+    constexpr int R = RPRE ? (FOLD ? 4 * TM * TN : 16 / EPI * TM * TN) : 0;   // residual loads per wave and tile
     f32x4 rpre[RPRE ? TM : 1][TN][4];
     static_assert(!RGEN || (RPRE && STRIDE == 2 && EPI == 1 && TM == 1 && TN == 1 && MODE == 1), "generated residual: the stride-2 128-column instance");
     const bool res_on = (RGEN || p.res != nullptr) && !out2 && !(abl & 32);
@@ -378,6 +410,15 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
         }
         int ldr = p.ldres;
         asm volatile("" : "+s"(ldr));
+        if constexpr (FOLD) {   // lane = pixel fr of the wave's two tile rows: rpre[0][j][q] = its channels 32 j + 8 q + 4 fh .. + 3, 16 bytes
+            const float* rbase = p.res + (img_o + (long)(y0 + row0 / TW) * Wo + x0) * ldr;
+            const unsigned roff = (unsigned)(((fr >> 4) * Wo + (fr & 15)) * ldr + 4 * fh) * 4u;
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) rpre[0][j][q] = load_s(rbase + 32 * j + 8 * q, roff);
+            return;
+        }
         const int li = fr & 3, cq = fr >> 2;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -428,6 +469,12 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
+                        if constexpr (FOLD) {   // operands swapped: the same three products in the same order, the tile transposed
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[ks][j], al[ks][i], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[ks][j], ah[ks][i], acc[i][j], 0, 0, 0);
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[ks][j], ah[ks][i], acc[i][j], 0, 0, 0);
+                            continue;
+                        }
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks][i], bh[ks][j], acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][i], bl[ks][j], acc[i][j], 0, 0, 0);
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks][i], bh[ks][j], acc[i][j], 0, 0, 0);
@@ -490,7 +537,61 @@ __global__ __launch_bounds__(NW * 64, 2) void sep_pipe_kernel(const SepParams p)
         int ldo = out2 ? p.ldy2 : p.ldy, ldr = p.ldres;
         asm volatile("" : "+s"(ldo), "+s"(ldr));   // opaque: the per-pixel bases below are recomputed per tile, not hoisted out of the
                                                   // step loop into (spilled) SGPRs
-        if constexpr (EPI == 1) {
+        if constexpr (FOLD) {
+            // The accumulators hold the transposed tile: lane = pixel fr of the wave's 32 (tile row 2 wm + fr / 16, column fr % 16),
+            // register 4 q + k of acc[0][j] = channel 32 j + 8 q + 4 fh + k.  y as in the branch below (same affine, activation,
+            // "+ residual"), then one fp32 MFMA per register: A = the nine taps of the lane pair's two channels (lane = tap row), B = y.
+            // Result row t = 8 (e >> 2) + 4 fh + (e & 3): registers 0..3 are planes 0..3 (fh = 0) and 4..7 (fh = 1), register 4 of the
+            // half wave fh = 0 is plane 8 -- five dword stores per wave and tile, each 64-byte runs of a plane's rows (E = 5: the vmcnt
+            // arithmetic above stays exact; the fifth is issued by every wave, half its lanes masked).
+            const unsigned char* at = smem + FT_OFF + fh * 64;
+            const unsigned char* wt = smem + FW_OFF + (fh * 10 + (fr < 9 ? fr : 9)) * 4;
+            if constexpr (RPRE) {
+                if (has_res) {
+                    if constexpr (LEAD2) wait_vm<PP>();
+                    else wait_vm<0>();
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(rpre[0][j][q]));   // no use of a residual register moves above the wait
+                }
+            }
+            f32x16 zc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) zc[e] = 0.f;
+            // two copies, chosen once per tile (smp: conv + BN + relu6 alone): no branch inside the 32 steps
+            auto all = [&](auto smp) {
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int off = (32 * j + 8 * q + k) * 16;
+                            const float rv = has_res ? rpre[0][j][q][k] : -0.f;   // x + (-0) == x for every x
+                            float y;
+                            if constexpr (decltype(smp)::value) {
+                                const f32x2 a = *reinterpret_cast<const f32x2*>(at + off);
+                                y = __builtin_amdgcn_fmed3f(fmaf(acc[0][j][4 * q + k], a[0], a[1]), 0.f, 6.f) + rv;
+                            } else {
+                                const f32x4 a = *reinterpret_cast<const f32x4*>(at + off);
+                                float u = fmaf(acc[0][j][4 * q + k], a[0], a[1]);
+                                u = __builtin_amdgcn_fmed3f(fmaxf(u, slope * u), lo, hi);
+                                const float u2 = __builtin_amdgcn_fmed3f(fmaf(u, a[2], a[3]), 0.f, hi2);
+                                y = (two ? u2 : u) + rv;
+                            }
+                            const float wv = *reinterpret_cast<const float*>(wt + (16 * j + 4 * q + k) * 80);
+                            zc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv, y, zc, 0, 0, 0);
+                        }
+            };
+            if (simple) all(std::true_type{});
+            else all(std::false_type{});
+            const long plane = (long)gridDim.z * p.H * p.W;
+            float* zl = p.fold_z + (img_o + (long)(y0 + row0 / TW + (fr >> 4)) * Wo + x0 + (fr & 15)) + (fh ? 4 * plane : 0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) store_d(zl + i * plane, zc[i]);
+            if (fh == 0) store_d(zl + 8 * plane, zc[4]);
+        } else if constexpr (EPI == 1) {
             // a lane keeps its channel (nb + fr) and stores the sixteen pixels of an accumulator one dword each: the 32 lanes of a half
             // wave write a pixel's 128 contiguous bytes.  split32: two pixels are split together, the (even, odd) channel pair trades
             // halves, the even lane stores hi (c, c + 1), the odd lane lo (c - 1, c).
@@ -843,6 +944,9 @@ static bool use_nw4(const SepParams& p) {
 
 bool sep_pipe_covers(const SepParams& p, int precision) {
     if (!g_knobs.sep_pipe || precision != 3) return false;
+    if (folded(p))    // folded final conv: the 4-wave 64-column instance only -- deconv0_b of graph D and its likes
+        return p.stride == 1 && p.H % 8 == 0 && p.W % 16 == 0 && p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 4064 && p.N == 64 && p.N2 == 0 &&
+               !p.out_split && !p.gen_a && !p.rg_stride && !p.reflect && g_knobs.sep_nw != 8;
     if (p.gen_a)   // generated input (round 4, opt-in: dev knob sep_gen_pipe): the 4-wave 64-column instance only -- cnn0_last of graphs D / X and its likes
         return g_knobs.sep_gen_pipe && p.stride == 1 && p.H % 8 == 0 && p.W % 16 == 0 && (p.Cin == 32 || p.Cin == 64) && p.N <= 64 && p.N2 == 0 &&
                !p.out_split && !p.res && g_knobs.sep_nw != 8;
@@ -863,7 +967,7 @@ bool sep_pipe_covers(const SepParams& p, int precision) {
 // issues ~1.9 x the instructions per chunk -- and graph D 22.10 ms with 0, 22.26 with 1, 23.07 with 2 in one process.  A forced 4-wave
 // form (dev knob sep_nw = 4) always means this file's kernel.
 static bool use_pipe2(const SepParams& p) {
-    if (p.gen_a || p.rg_stride) return false;
+    if (p.gen_a || p.rg_stride || folded(p)) return false;
     if (!g_knobs.sep_pipe2 || g_knobs.sep_ablate || g_knobs.sep_nw == 4 || !sep_pipe2_covers(p)) return false;
     if (g_knobs.sep_pipe2 == 2) return true;
     return p.N2 > 0 && (p.N > 64 || p.N2 > 64);
@@ -873,7 +977,7 @@ int sep_pipe_launch(const SepParams& p, int B, hipStream_t st) {
     if (use_pipe2(p)) return sep_pipe2_launch(p, B, st);
     SepParams q = p;
     const bool s2 = p.stride == 2;
-    const int nw = (p.gen_a || (!s2 && use_nw4(p))) ? 4 : 8, tw = s2 ? 16 : 4 * nw, th = s2 ? 4 : 8;
+    const int nw = (p.gen_a || folded(p) || (!s2 && use_nw4(p))) ? 4 : 8, tw = s2 ? 16 : 4 * nw, th = s2 ? 4 : 8;
     const int Ho = p.H / (s2 ? 2 : 1), Wo = p.W / (s2 ? 2 : 1);
     const int tiles_w = Wo / tw;
     const long wgs1 = (long)tiles_w * (Ho / th) * B;
@@ -891,6 +995,11 @@ int sep_pipe_launch(const SepParams& p, int B, hipStream_t st) {
     const int mode = g_knobs.sep_mode >= 0 ? g_knobs.sep_mode : ((nw == 4 || p.res) ? 1 : 0);
     // epilogue (see the kernel): per-channel dword stores, 2.7 % over graph D's twelve shapes (tools/sep_epi_bench.py; the two-output
     // launches 5 %) -- except with a residual on more than 128 columns (cnn2_last: 445 against 430 us for the transposed 16-byte form)
+    if (folded(p)) {   // one epilogue form (the knob epi_width does not apply); both schedules
+        if (mode == 1) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 1, false, false, true>), grid, dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((sep_pipe_kernel<64, false, 0, false, 4, 1, 1, false, false, true>), grid, dim3(256), 0, st, q);
+        return emd::check_launch("sep_pipe_kernel<folded final conv>");
+    }
     if (p.gen_a) {
         if (g_knobs.epi_width == 4) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 4, true>), grid, dim3(256), 0, st, q);
         else hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 1, true>), grid, dim3(256), 0, st, q);

@@ -360,6 +360,14 @@ class DenoiserEngine:
                     and L.stride == 2 and L.rate == 1 and ops.sep_fused_supported(x, L.cout, L.stride, L.rate)
                     and ops.sep_fused_s2_genres_supported(x, L.cout))
 
+    def _fold_final(self, x):
+        """True where deconv0_b (input x) runs folded with deconv_final (emd_sep3x3_fused_fold_f32 + emd_cout1_gather9_f32): wherever _sep
+        would take the one-launch form and the FOLD instance covers the shape -- a rule of the shape alone, never of the batch size."""
+        L = self.layers["deconv0_b"]
+        return bool(self.fuse_sep and self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_FOLD_FINAL", "1") != "0"
+                    and L.stride == 1 and L.rate == 1 and self.layers["deconv_final"].cin == L.cout
+                    and ops.sep_fused_supported(x, L.cout, L.stride, L.rate) and ops.sep_fused_fold_supported(x, L.cout))
+
     def _sep_gemm_ok(self, x, L):
         return (self.fuse_sep and self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_SEPGEMM", "0") == "1"   # opt-in: measured slower than the two-kernel route (DESIGN.md 3.2c)
                 and ops.sep_gemm_supported(x, L.cout, L.stride, L.rate))
@@ -619,13 +627,22 @@ class DenoiserEngine:
         deconv1to0 = self._deconv("deconv1to0", deconv1, E(S, f1))
         del deconv1
         t, residual0_d = self._sep_and_projection("deconv0_a", "residual0_d", deconv1to0)
-        deconv0 = self._sep("deconv0_b", t, res=residual0_d)
-        del deconv1to0, residual0_d, t
         if out is None:
             out = torch.empty((B, S, S, 1), dtype=torch.float32, device=dev)
         pf = P["deconv_final"]
-        # the twin clips in-graph (denoiser-multi-gpu.py:534-538); D does not (denoiser.py:396)
-        ops.conv3x3_cout1(deconv0, pf["w"], pf["scale_f"], pf["shift_f"], out, act=2 if self.variant == "Dprime" else 1)
+        fact = 2 if self.variant == "Dprime" else 1   # the twin clips in-graph (denoiser-multi-gpu.py:534-538); D does not (denoiser.py:396)
+        if self._fold_final(t):
+            # deconv_final is linear in deconv0: its channel sum runs in deconv0_b's epilogue (nine floats per pixel leave instead of 64),
+            # the nine-tap spatial sum in a gather of its own -- a [B,S,S,64] write and its read less
+            pb = P["deconv0_b"]
+            z = torch.empty((9, B, S, S), dtype=torch.float32, device=dev)
+            ops.sep_fused(t, pb["dw"], pb["pw"], pb["scale"], pb["shift"], None, scale2=pb.get("scale2"), shift2=pb.get("shift2"),
+                          res=residual0_d, fold_final=(pf["w"], z))
+            del deconv1to0, residual0_d, t
+            return ops.cout1_gather9(z, pf["scale_f"], pf["shift_f"], out, B, S, S, act=fact)
+        deconv0 = self._sep("deconv0_b", t, res=residual0_d)
+        del deconv1to0, residual0_d, t
+        ops.conv3x3_cout1(deconv0, pf["w"], pf["scale_f"], pf["shift_f"], out, act=fact)
         return out
 
 

@@ -192,10 +192,23 @@ def sep_fused_supported(x: Act, cout: int, stride: int, rate: int) -> bool:
 
 
 def sep_fused(x: Act, dw_dev, w: PackedWeights, scale1, shift1, out: Act, act=True, scale2=None, shift2=None,
-              res: Act | None = None, precision=PREC_BF16X3, stream=None, reflect=False, stride=1, gen_res=None):
+              res: Act | None = None, precision=PREC_BF16X3, stream=None, reflect=False, stride=1, gen_res=None, fold_final=None):
     """Depthwise 3x3 + pointwise + epilogue in one launch (emd_sep3x3_fused_f32; reflect=True: the depthwise stage reads the
-    REFLECT-padded border, emd_sep3x3_fused_reflect_f32; stride=2: emd_sep3x3_fused_s2_f32, split-bf16 only)."""
+    REFLECT-padded border, emd_sep3x3_fused_reflect_f32; stride=2: emd_sep3x3_fused_s2_f32, split-bf16 only).
+    fold_final=(wfin, z): the output is not written -- the channel sums of the 3x3 conv to one channel that follows (taps wfin [9][cout])
+    are, as nine planes z [9,B,H,W] (emd_sep3x3_fused_fold_f32; `out` is ignored and z is returned; cout1_gather9 finishes the conv)."""
     lib = _lib.load()
+    if fold_final is not None:   # (through sep_fused: the launch stays in its kernel family)
+        wfin, z = fold_final
+        assert stride == 1 and not reflect and gen_res is None and precision == PREC_BF16X3 and w.cin == x.C and w.taps == 1
+        assert z.is_contiguous() and z.numel() == 9 * x.B * x.H * x.W and wfin.numel() == 9 * w.cout
+        if res is not None:
+            assert (res.B, res.H, res.W, res.C) == (x.B, x.H, x.W, w.cout)
+        rc = lib.emd_sep3x3_fused_fold_f32(x.ptr, x.ld, _p(dw_dev), _p(w.hi), _p(w.lo), _p(scale1), _p(shift1), _p(scale2), _p(shift2),
+                                           res.ptr if res is not None else C.c_void_p(0), res.ld if res is not None else 0,
+                                           _p(wfin), _p(z), x.B, x.H, x.W, x.C, w.cout, _act(act), _lib.stream_ptr(stream))
+        _lib.check(rc, "emd_sep3x3_fused_fold_f32")
+        return z
     assert (out.B, out.H, out.W, out.C) == (x.B, -(-x.H // stride), -(-x.W // stride), w.cout) and w.cin == x.C and w.taps == 1
     if res is not None:
         assert (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, out.C)
@@ -224,6 +237,20 @@ def sep_fused(x: Act, dw_dev, w: PackedWeights, scale1, shift1, out: Act, act=Tr
                                   _act(act), precision, _lib.stream_ptr(stream))
     _lib.check(rc, "emd_sep3x3_fused_f32")
     return out
+
+
+def sep_fused_fold_supported(x: Act, cout: int) -> bool:
+    return bool(_lib.load().emd_sep3x3_fused_fold_supported(x.H, x.W, x.C, cout))
+
+
+def cout1_gather9(z, scale: float, shift: float, out_img, B: int, H: int, W: int, act=True, stream=None):
+    """out[b,y,x] = act(scale * sum_t z[t,b,y+t//3-1,x+t%3-1] + shift) (emd_cout1_gather9_f32): the spatial half of the final 3x3 conv
+    behind sep_fused(..., fold_final=...).  act as conv3x3_cout1: False/0 none, True/1 relu6, 2 relu6 then clip to [0,1]."""
+    lib = _lib.load()
+    assert z.is_contiguous() and z.numel() == 9 * B * H * W and out_img.is_contiguous() and out_img.numel() == B * H * W
+    rc = lib.emd_cout1_gather9_f32(_p(z), C.c_float(scale), C.c_float(shift), _p(out_img), B, H, W, int(act), _lib.stream_ptr(stream))
+    _lib.check(rc, "emd_cout1_gather9_f32")
+    return out_img
 
 
 def sep_fused_s2_genres_supported(x: Act, cout: int) -> bool:

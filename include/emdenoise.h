@@ -327,6 +327,19 @@ int emd_sep3x3_fused_s2_genres_f32(const float* x, int ldx, const float* dw, con
                                    const float* scale1, const float* shift1, const float* scale2, const float* shift2,
                                    const float* img, int ldimg, int img_stride, const float* res_a, const float* res_t, int res_act,
                                    float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act, emd_stream_t stream);
+/* The stride-1 block followed by a 3x3 SAME convolution to ONE channel (deconv0_b -> deconv_final, machine_learning/denoiser.py:383-387),
+ * the convolution's channel sum folded into the block's epilogue.  With y the output emd_sep3x3_fused_f32 would have written (same
+ * arithmetic, never stored), emd_sep3x3_fused_fold_f32 writes z [9][B][H][W]: z[t][b][h][w] = sum_c wfin[t][c] * y[b][h][w][c] in fp32
+ * (fp32 matrix instruction, fixed order), wfin [3][3][Cout] as emd_conv3x3_cout1_f32 takes it.  emd_cout1_gather9_f32 finishes the convolution:
+ * out[b][h][w] = act(scale * sum_t z[t][b][h + t/3 - 1][w + t%3 - 1] + shift), taps outside the image zero, added in the order t = 0..8;
+ * scale / shift / act (0, 1, 2) as in emd_conv3x3_cout1_f32.  The pair computes emd_sep3x3_fused_f32 + emd_conv3x3_cout1_f32 up to the
+ * order of the 576-term sum.  emd_sep3x3_fused_fold_supported: stride 1, split-bf16, H%8==0, W%16==0, Cin%32==0, Cout==64. */
+int emd_sep3x3_fused_fold_supported(int H, int W, int Cin, int Cout);
+int emd_sep3x3_fused_fold_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
+                              const float* scale1, const float* shift1, const float* scale2, const float* shift2,
+                              const float* res, int ldres, const float* wfin, float* z, int B, int H, int W, int Cin, int Cout,
+                              int act, emd_stream_t stream);
+int emd_cout1_gather9_f32(const float* z, float scale, float shift, float* y, int B, int H, int W, int act, emd_stream_t stream);
 /* The same on the tf.pad(REFLECT, 1) image with VALID padding: graph G's down-sampling strided_conv_block(stride 2, pad_size = (1, 1))
  * (misc_py/gan-infilling-100.py:205-243, :345-352).  Same shape rules (emd_sep3x3_fused_supported(H, W, Cin, Cout, 2, 1)). */
 int emd_sep3x3_fused_s2_reflect_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
