@@ -463,6 +463,7 @@ SIGNATURES = {
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs
 DEV_SIGNATURES = {
     "emd_debug_knob": (C.c_int, [C.c_char_p, C.c_long]),
+    "emd_debug_reduce_final_cl": (C.c_int, [C.c_int]),
     "emd_debug_split_variant": (None, [C.c_int]),
     "emd_debug_split_stamps": (None, [C.c_void_p]),
     "emd_debug_sep_stamps": (None, [C.c_void_p]),

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void chan_reduce_partial_v4(const float* __res
 // do_prep: the per-channel step bn_bwd_prep_kernel would run next (K, m1, m2 and the parameter gradients) in the same launch.
 // CL channels x (256 / CL) slab lanes per workgroup (16 x 16 originally; 4 / 1 channels for the long partial lists of the large maps: the
 // fused depthwise-gradient reduction delivers 1 024 per 512^2 image and a 64-channel layer had four workgroups; see bn_stats_final).
-inline int reduce_final_cl(int nslab) { return nslab < 128 ? 16 : (nslab < 1024 ? 4 : 1); }
+// Launch rule: emd::reduce_final_cl (emd_common.hpp).
 template <int CL>
 __global__ __launch_bounds__(256) void chan_reduce_final(const double* __restrict__ part, int nslab, int C,
                                                          float* __restrict__ s1, float* __restrict__ s2, int accumulate,
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void chan_reduce_final(const double* __restric
 
 static void launch_final(const double* part, int nslab, int C, int B, float* s1, float* s2, int accumulate, const emd::BnPrepArgs* prep, float inv_n,
                          hipStream_t st) {
-    const int cl = reduce_final_cl(nslab);
+    const int cl = emd::reduce_final_cl(nslab);
     const emd::BnPrepArgs pa = prep ? *prep : emd::BnPrepArgs{};
     const int dp = prep ? 1 : 0;
     if (cl == 16)

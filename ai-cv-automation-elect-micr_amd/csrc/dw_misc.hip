@@ -674,11 +674,10 @@ __global__ __launch_bounds__(256) void bn_stats_partial_v4(const float* __restri
 // and the kernel that applies the norm (graph X has 63 such pairs on its critical path).
 // TRAIN (round 4): the training-mode fold of the whole BN chain (bn_train_fold_kernel's step, bn_chain_dev.hpp: scale, shift, rstd1,
 // rstd2 and the moving-average updates from image 0) in the same launch.
-inline int final_cl(int nslab) { return nslab < 128 ? 16 : (nslab < 1024 ? 4 : 1); }   // channels per workgroup of bn_stats_final
 // CL channels x (256 / CL) slab lanes per workgroup.  CL = 16 is the original geometry (<= 512 slabs of a channel summed by 16 lanes); the
 // statistics epilogues of the GEMMs deliver one partial per 128-row tile -- 2 048 per 512^2 image -- and with 16 channels per workgroup a
 // 64-channel layer had FOUR workgroups walking 128-256 dependent rounds: 87 us behind a 53 us GEMM (tools/small_gemm_bench.py, round 4).
-// CL = 4 / 1 (launch rule: final_cl) give those layers 16 / 64 workgroups of 64 / 256 lanes.  The order of the sum depends on CL, which
+// CL = 4 / 1 (launch rule: emd::reduce_final_cl, emd_common.hpp) give those layers 16 / 64 workgroups of 64 / 256 lanes.  The order of the sum depends on CL, which
 // depends on nslab only: an image alone and the same image in a batch still get the same bits.
 template <bool FOLD, bool TRAIN = false, int CL = 16>
 __global__ __launch_bounds__(256) void bn_stats_final(const double* __restrict__ part, int nslab, int C, long npix,
@@ -868,7 +867,7 @@ int emd::launch_bn_stats_final(const double* part, int nslab, int C, long npix, 
                                const float* gamma, const float* beta, float eps, float* scale, float* shift, int images,
                                const emd::BnFoldArgs* train_fold) {
     // images > 1: per-image statistics -- `nslab` partials and `npix` pixels PER IMAGE, part [image][nslab][2][C], mean / var [image][C]
-    const int cl = final_cl(nslab);
+    const int cl = emd::reduce_final_cl(nslab);
     const unsigned ni = images > 1 ? images : 1;
     const emd::BnFoldArgs fa = train_fold ? *train_fold : emd::BnFoldArgs{};
 #define EMD_FINAL(FOLD, TRAIN, CLV, GY) \

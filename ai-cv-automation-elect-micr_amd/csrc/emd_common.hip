@@ -22,6 +22,9 @@ extern "C" int emd_version(void) { return EMD_VERSION; }
 
 extern "C" const char* emd_last_error(void) { return emd::g_err; }
 
+// dev hook (include/emdenoise_dev.h), host only: the geometry the second stage of a per-channel reduction takes for `nslab` partials
+extern "C" int emd_debug_reduce_final_cl(int nslab) { return emd::reduce_final_cl(nslab); }
+
 // dev hook (include/emdenoise_dev.h): sets one of emd::Knobs by name; returns 0, or -1 for an unknown name
 extern "C" int emd_debug_knob(const char* name, long value) {
     using emd::g_knobs;

@@ -101,6 +101,10 @@ inline long reduce_slabs(long npix) {
     const long r = reduce_rows_per_slab(npix);
     return (npix + r - 1) / r;
 }
+// Channels per workgroup (CL) of the second stage, bn_stats_final (dw_misc.hip) and chan_reduce_final (bn_train.hip), from the number
+// of partials per channel: 16 channels x 16 slab lanes, 4 x 64 or 1 x 256.  The one copy of the rule; tests read it through
+// emd_debug_reduce_final_cl (include/emdenoise_dev.h).
+inline int reduce_final_cl(int nslab) { return nslab < 128 ? 16 : (nslab < 1024 ? 4 : 1); }
 
 }  // namespace emd
 

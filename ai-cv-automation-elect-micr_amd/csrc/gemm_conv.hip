@@ -489,7 +489,9 @@ extern "C" int emd_conv1x1_f32(const float* x, int ldx, const uint16_t* whi, con
 // otherwise -- call the conv and the statistics separately).  workspace: emd_conv_stats_workspace_bytes(B * Ho * Wo, Cout) bytes.
 extern "C" size_t emd_conv_stats_workspace_bytes(long M, int Cout) {
     if (M <= 0 || Cout <= 0) return 0;
-    return (size_t)((M + 127) / 128) * 2 * Cout * sizeof(double);
+    // + 3 rows: the transposed conv asks with M = 4 * B * H * W and its four phases write 4 * ceil(B * H * W / 128) rows of partials, up
+    // to three more than ceil(M / 128) when B * H * W is no multiple of 128 (without them the last phase wrote past the workspace)
+    return (size_t)((M + 127) / 128 + 3) * 2 * Cout * sizeof(double);
 }
 
 static int conv_stats_run(GemmParams& p, int B, long npix_img, int images, float* mean, float* var, void* workspace, int precision,

@@ -43,6 +43,10 @@ extern "C" {
 
 /* Set one of the knobs above by name.  Returns 0, or -1 for an unknown name. */
 int emd_debug_knob(const char* name, long value);
+/* Host only, no state: channels per workgroup (16, 4 or 1) of the second stage of a per-channel reduction (bn_stats_final,
+ * chan_reduce_final) for `nslab` partials per channel -- the launch rule itself (csrc/emd_common.hpp, emd::reduce_final_cl), so that
+ * tests/test_reduce_routes.py can prove which instance each of its shapes selects. */
+int emd_debug_reduce_final_cl(int nslab);
 /* Force the pipeline variant of emd_conv1x1_split32_f32 (csrc/gemm_split.hip); -1 restores the dispatch rule. */
 void emd_debug_split_variant(int v);
 /* Device buffer that the split32 GEMM writes s_memtime phase stamps into (NULL = off). */

@@ -221,61 +221,180 @@ def _t64(a):
     return torch.from_numpy(np.asarray(a, np.float64))
 
 
-@pytest.mark.parametrize("B,H,W,Cc,stride", [(2, 12, 16, 64, 1), (1, 9, 7, 128, 1), (2, 12, 16, 64, 2), (1, 7, 10, 768, 2), (1, 2, 2, 64, 1)])
-def test_dw3x3_reflect_backward(B, H, W, Cc, stride):
-    from emdenoise import train_ops as TO
-    from oracle import gan_graph as GG
-    from tests.test_ops_gpu import out_act, rnd, to_act
+# The reverse-pass kernels of the generator beyond toy sizes.  dw_reflect_wgrad_kernel (depthwise 3x3 and the 3x3 conv to one channel)
+# clamps to 512 slabs above 32 768 output pixels: more than 64 pixels per slab, slabs that straddle rows and images, a ragged or empty
+# tail; dw7_c1_wgrad_kernel runs a grid-stride loop over at most 1 024 workgroups.  The file's bars (TOL_WGRAD for weight gradients,
+# TOL_DATA for data gradients and the forward) were set at 384 - 768 pixels, so each case past them carries a yardstick: the relative
+# L2 distance of the float32 autograd restatement from the float64 one, computed on the CPU by ``python -m tests.test_gan_train_gpu``
+# and written below.  A case keeps the file's bar where 4 x its yardstick is below it; otherwise its bar is 4 x the yardstick.
+#
+#   case                                 float32 restatement (dW, dx) bar (dW, dx)         measured on an MI355X (dW, dx): no GPU run of these cases yet; each test prints its figures
+#   dw3x3_reflect (1, 181, 183, 8, 1)    1.25e-6, 5.4e-8              2e-5, 2e-6           not measured
+#   dw3x3_reflect (2, 130, 131, 8, 1)    1.22e-6, 5.4e-8              2e-5, 2e-6           not measured
+#   dw3x3_reflect (1, 363, 365, 8, 2)    1.22e-6, 3.5e-8              2e-5, 2e-6           not measured
+#   dw3x3_reflect (1, 512, 512, 32, 2)   1.66e-6, 3.4e-8              2e-5, 2e-6           not measured
+#   dw3x3_reflect (1, 128, 128, 4, 2)    4.1e-7, 3.7e-8               2e-5, 2e-6           not measured
+#   conv3x3_cout1 (1, 181, 183, 16)      1.16e-6, 5.9e-8              2e-5, 2e-6           not measured
+#   conv3x3_cout1 (2, 512, 512, 32)      5.10e-6, 5.7e-8              2.04e-5, 2e-6        not measured
+#   dw7_c1 (1, 47, 45)                   8.3e-7, 1.4e-7 (fwd)         2e-5, 2e-6           not measured
+#   dw7_c1 (2, 300, 301)                 4.65e-6, 1.3e-7 (fwd)        2e-5, 2e-6           not measured
+#   dw7_c1 (9, 512, 512)                 9.75e-6, 1.3e-7 (fwd)        3.90e-5, 2e-6        not measured
+TOL_WGRAD, TOL_DATA, FACTOR = 2e-5, 2e-6, 4.0
 
-    x = _t64(rnd((B, H, W, Cc), 1)).requires_grad_(True)
-    w = _t64(rnd((3, 3, Cc, 1), 2, 0.4)).requires_grad_(True)
+DW_REFLECT_SMALL = [(2, 12, 16, 64, 1), (1, 9, 7, 128, 1), (2, 12, 16, 64, 2), (1, 7, 10, 768, 2), (1, 2, 2, 64, 1)]
+DW_REFLECT_LARGE = [
+    (1, 181, 183, 8, 1),      # 33 123 pixels: 512 slabs of 65; slab 509 is ragged, slabs 510 and 511 are empty
+    (2, 130, 131, 8, 1),      # 34 060 pixels: 67 per slab, a slab straddles the image boundary
+    (1, 363, 365, 8, 2),      # stride 2: 182 x 183 outputs
+    (1, 512, 512, 32, 2),     # the generator's enc1 at 512^2 (gan.py: sep("enc1", 32, 64, stride=2))
+    (1, 128, 128, 4, 2),      # a small stride-2 case with one channel quad (64 slabs of 64 pixels, below the clamp)
+]
+COUT1_SMALL, COUT1_LARGE = [(1, 20, 24, 32)], [(1, 181, 183, 16), (2, 512, 512, 32)]
+DW7_SMALL = [(1, 20, 24)]
+DW7_LARGE = [(1, 47, 45),     # 2 115 pixels: one workgroup, two rounds of its 8-pixel-per-thread budget
+             (2, 300, 301),   # 89 workgroups
+             (9, 512, 512)]   # 1 152 workgroups' worth of pixels on the 1 024 the launch is capped at: several rounds per thread
+
+# (dW, dx) -- for dw7: (dW, forward) -- of the float32 restatement, by case
+YARD = {
+    (1, 181, 183, 8, 1): (1.253e-06, 5.425e-08),
+    (2, 130, 131, 8, 1): (1.216e-06, 5.415e-08),
+    (1, 363, 365, 8, 2): (1.217e-06, 3.509e-08),
+    (1, 512, 512, 32, 2): (1.656e-06, 3.447e-08),
+    (1, 128, 128, 4, 2): (4.090e-07, 3.702e-08),
+    (1, 181, 183, 16): (1.160e-06, 5.927e-08),
+    (2, 512, 512, 32): (5.100e-06, 5.746e-08),
+    (1, 47, 45): (8.341e-07, 1.361e-07),
+    (2, 300, 301): (4.651e-06, 1.280e-07),
+    (9, 512, 512): (9.750e-06, 1.271e-07),
+}
+
+
+def bar(case, which):
+    """The file's bar, or 4 x the case's yardstick where that is larger (which: 0 weight gradient, 1 data gradient / forward)."""
+    tol = (TOL_WGRAD, TOL_DATA)[which]
+    return max(tol, FACTOR * YARD[case][which]) if case in YARD else tol
+
+
+def dw_reflect_reference(B, H, W, Cc, stride, dtype=torch.float64):
+    """-> x, w, dy (float32 numpy) and autograd's (dx, dW) in `dtype` of the reflect-padded depthwise 3x3."""
+    from oracle import gan_graph as GG
+    from tests.test_ops_gpu import rnd
+
+    x32, w32 = rnd((B, H, W, Cc), 1), rnd((3, 3, Cc, 1), 2, 0.4)
+    x, w = torch.from_numpy(x32).to(dtype).requires_grad_(True), torch.from_numpy(w32).to(dtype).requires_grad_(True)
     y = GG.depthwise_valid_t(GG.reflect_pad_t(x, 1), w, stride)
     dy = rnd(tuple(y.shape), 3)
-    gx, gw = torch.autograd.grad(y, (x, w), _t64(dy))
-    xa, dya = to_act(x.detach().numpy().astype(np.float32), ld=Cc + 8, c0=4), to_act(dy)
+    gx, gw = torch.autograd.grad(y, (x, w), torch.from_numpy(dy).to(dtype))
+    return x32, w32, dy, gx.numpy(), gw.numpy()
+
+
+@pytest.mark.parametrize("B,H,W,Cc,stride", DW_REFLECT_SMALL + DW_REFLECT_LARGE)
+def test_dw3x3_reflect_backward(B, H, W, Cc, stride):
+    from emdenoise import train_ops as TO
+    from tests.test_ops_gpu import out_act, to_act
+
+    case = (B, H, W, Cc, stride)
+    x, w, dy, gx, gw = dw_reflect_reference(*case)
+    xa, dya = to_act(x, ld=Cc + 8, c0=4), to_act(dy)
     dw = torch.zeros((9, Cc), dtype=torch.float32, device=dev())
     TO.dw3x3_reflect_wgrad(xa, dya, dw, stride=stride)
-    wdev = torch.from_numpy(w.detach().numpy().reshape(9, Cc).astype(np.float32)).to(dev())
+    wdev = torch.from_numpy(w.reshape(9, Cc)).to(dev())
     dx = TO.dw3x3_reflect_bwd_data(dya, wdev, out_act(B, H, W, Cc), stride=stride)
     torch.cuda.synchronize()
-    assert rel_l2(dw.cpu().numpy().reshape(3, 3, Cc, 1), gw.numpy()) < 2e-5
-    assert rel_l2(dx.torch().cpu().numpy(), gx.numpy()) < 2e-6
+    e_w, e_x = rel_l2(dw.cpu().numpy().reshape(3, 3, Cc, 1), gw), rel_l2(dx.torch().cpu().numpy(), gx)
+    print(f"dw3x3_reflect {case}: dW {e_w:.2e} (bar {bar(case, 0):.2e}), dx {e_x:.2e} (bar {bar(case, 1):.2e})")
+    assert e_w < bar(case, 0)
+    assert e_x < bar(case, 1)
 
 
-def test_first_and_last_layer_backward():
-    from emdenoise import train_ops as TO
+def dw7_reference(B, H, W, dtype=torch.float64):
     from oracle import gan_graph as GG
-    from tests.test_ops_gpu import out_act, rnd, to_act
+    from tests.test_ops_gpu import rnd
 
-    B, H, W = 1, 20, 24
-    d32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev())
-    # 7x7 reflect depthwise on the 1-channel image: forward into channel 0 of a 4-channel tensor, and dW
-    x = rnd((B, H, W, 1), 4)
-    w = _t64(rnd((7, 7, 1, 1), 5, 0.2)).requires_grad_(True)
-    y = GG.depthwise_valid_t(GG.reflect_pad_t(_t64(x), 3), w, 1)
+    x, w32 = rnd((B, H, W, 1), 4), rnd((7, 7, 1, 1), 5, 0.2)
+    w = torch.from_numpy(w32).to(dtype).requires_grad_(True)
+    y = GG.depthwise_valid_t(GG.reflect_pad_t(torch.from_numpy(x).to(dtype), 3), w, 1)
     dd = rnd((B, H, W, 1), 6)
-    (gw,) = torch.autograd.grad(y, w, _t64(dd))
-    d4 = TO.dw7_c1_reflect(d32(x), d32(w.detach().numpy().reshape(49)), out_act(B, H, W, 4))
+    (gw,) = torch.autograd.grad(y, w, torch.from_numpy(dd).to(dtype))
+    return x, w32, dd, y.detach().numpy(), gw.numpy()
+
+
+def first_layer_backward(B, H, W):
+    """7x7 reflect depthwise on the 1-channel image: forward into channel 0 of a 4-channel tensor, and dW."""
+    from emdenoise import train_ops as TO
+    from tests.test_ops_gpu import out_act, to_act
+
+    case = (B, H, W)
+    d32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev())
+    x, w, dd, y, gw = dw7_reference(*case)
+    d4 = TO.dw7_c1_reflect(d32(x), d32(w.reshape(49)), out_act(B, H, W, 4))
     dd4 = np.zeros((B, H, W, 4), np.float32)
     dd4[..., 0:1] = dd
     dw49 = torch.zeros(49, dtype=torch.float32, device=dev())
     TO.dw7_c1_reflect_wgrad(d32(x), to_act(dd4), dw49)
     torch.cuda.synchronize()
     got = d4.torch().cpu().numpy()
-    assert rel_l2(got[..., 0:1], y.detach().numpy()) < 2e-6 and np.all(got[..., 1:] == 0)
-    assert rel_l2(dw49.cpu().numpy().reshape(7, 7, 1, 1), gw.numpy()) < 2e-5
-    # last conv (reflect pad + 3x3 -> 1 channel): dW and dx
-    xin = _t64(rnd((B, H, W, 32), 7)).requires_grad_(True)
-    wl = _t64(rnd((3, 3, 32, 1), 8, 0.2)).requires_grad_(True)
+    e_y, e_w = rel_l2(got[..., 0:1], y), rel_l2(dw49.cpu().numpy().reshape(7, 7, 1, 1), gw)
+    print(f"dw7_c1_reflect {case}: forward {e_y:.2e} (bar {bar(case, 1):.2e}), dW {e_w:.2e} (bar {bar(case, 0):.2e})")
+    assert e_y < bar(case, 1) and np.all(got[..., 1:] == 0)
+    assert e_w < bar(case, 0)
+
+
+def cout1_reference(B, H, W, Cc, dtype=torch.float64):
+    from oracle import gan_graph as GG
+    from tests.test_ops_gpu import rnd
+
+    x32, w32 = rnd((B, H, W, Cc), 7), rnd((3, 3, Cc, 1), 8, 0.2)
+    xin, wl = torch.from_numpy(x32).to(dtype).requires_grad_(True), torch.from_numpy(w32).to(dtype).requires_grad_(True)
     yl = GG.depthwise_valid_t(GG.reflect_pad_t(xin, 1), wl, 1).sum(-1, keepdim=True)
     dyl = rnd((B, H, W, 1), 9)
-    gx, gwl = torch.autograd.grad(yl, (xin, wl), _t64(dyl))
-    dwl = torch.zeros((9, 32), dtype=torch.float32, device=dev())
-    TO.conv3x3_cout1_reflect_wgrad(to_act(xin.detach().numpy().astype(np.float32)), d32(dyl), dwl)
-    dx = TO.conv3x3_cout1_reflect_bwd_data(d32(dyl), d32(wl.detach().numpy().reshape(9, 32)), out_act(B, H, W, 32))
+    gx, gwl = torch.autograd.grad(yl, (xin, wl), torch.from_numpy(dyl).to(dtype))
+    return x32, w32, dyl, gx.numpy(), gwl.numpy()
+
+
+def last_layer_backward(B, H, W, Cc):
+    """The last conv (reflect pad + 3x3 -> 1 channel): dW and dx."""
+    from emdenoise import train_ops as TO
+    from tests.test_ops_gpu import out_act, to_act
+
+    case = (B, H, W, Cc)
+    d32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev())
+    x, w, dyl, gx, gwl = cout1_reference(*case)
+    dwl = torch.zeros((9, Cc), dtype=torch.float32, device=dev())
+    TO.conv3x3_cout1_reflect_wgrad(to_act(x), d32(dyl), dwl)
+    dx = TO.conv3x3_cout1_reflect_bwd_data(d32(dyl), d32(w.reshape(9, Cc)), out_act(B, H, W, Cc))
     torch.cuda.synchronize()
-    assert rel_l2(dwl.cpu().numpy().reshape(3, 3, 32, 1), gwl.numpy()) < 2e-5
-    assert rel_l2(dx.torch().cpu().numpy(), gx.numpy()) < 2e-6
+    e_w, e_x = rel_l2(dwl.cpu().numpy().reshape(3, 3, Cc, 1), gwl), rel_l2(dx.torch().cpu().numpy(), gx)
+    print(f"conv3x3_cout1_reflect {case}: dW {e_w:.2e} (bar {bar(case, 0):.2e}), dx {e_x:.2e} (bar {bar(case, 1):.2e})")
+    assert e_w < bar(case, 0)
+    assert e_x < bar(case, 1)
+
+
+def test_first_and_last_layer_backward():
+    first_layer_backward(*DW7_SMALL[0])
+    last_layer_backward(*COUT1_SMALL[0])
+
+
+@pytest.mark.parametrize("B,H,W", DW7_LARGE)
+def test_first_layer_backward_beyond_toy_sizes(B, H, W):
+    first_layer_backward(B, H, W)
+
+
+@pytest.mark.parametrize("B,H,W,Cc", COUT1_LARGE)
+def test_last_layer_backward_beyond_toy_sizes(B, H, W, Cc):
+    last_layer_backward(B, H, W, Cc)
+
+
+def yardsticks():
+    """(dW, dx / forward) of the float32 autograd restatement against the float64 one for every case past the toy sizes (CPU only)."""
+    out = {}
+    for cases, ref, pick in ((DW_REFLECT_LARGE, dw_reflect_reference, (4, 3)), (COUT1_LARGE, cout1_reference, (4, 3)),
+                             (DW7_LARGE, dw7_reference, (4, 3))):
+        for case in cases:
+            a, b = ref(*case, dtype=torch.float32), ref(*case, dtype=torch.float64)
+            out[case] = tuple(rel_l2(a[i], b[i]) for i in pick)
+    return out
 
 
 def test_feature_loss_crop_scatter_and_tanh():
@@ -457,3 +576,8 @@ def test_policy_driven_iterations():
     G2 = GT.GeneratorTrainer(G.state_dict(), D2, dev())
     b = GT.gan_iteration(G2, D2, x, t, offs, labels=[0.95, 1e-8, 0.95, 0.95], adapts=[1.0, 3.0, 1.0, 1.0], train="discr")[1].cpu().numpy()
     assert not np.isclose(a[0, 1], b[0, 1])
+
+
+if __name__ == "__main__":
+    for case, (yw, yx) in yardsticks().items():
+        print(f"    {case}: ({yw:.3e}, {yx:.3e}),   # bars {max(TOL_WGRAD, FACTOR * yw):.2e}, {max(TOL_DATA, FACTOR * yx):.2e}")
