@@ -458,6 +458,20 @@ SIGNATURES = {
     "emd_freq_stats_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
     # x B S profile freq_stats workspace ws_bytes stream
     "emd_freq_stats_f64": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- exit-wave reconstruction from a focal series (csrc/exitwave.hip)
+    # S n defocus wavelength px cs H stream
+    "emd_transfer_function_f64": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "emd_cfft2_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    # x B S inverse out workspace ws_bytes stream
+    "emd_cfft2_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_propagate_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # psi psi_is_real_f32 B s pad_periods defocus wavelength px cs out workspace ws_bytes stream
+    "emd_propagate_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_exitwave_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # images N s pad_periods defocus wavelength px cs iterations flags E stack losses workspace ws_bytes stream
+    "emd_exitwave_reconstruct_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

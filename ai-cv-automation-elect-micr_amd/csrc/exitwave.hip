@@ -1,0 +1,592 @@
+// Exit-wave reconstruction from a through-focus series (ewrec_class.py:100-110, :272-380), in double: the Fresnel
+// transfer function, the complex 2-D FFT, propagation between two 2-D FFTs, and the iteration that averages the back-propagated
+// images into an exit wave, propagates it to every focus and restores the measured amplitudes.  Square images of side s, padded
+// side S = s (1 + pad_periods), a power of two, 8..4096.  The 1-D transform is fft_line.hpp's (one line of S complex doubles in
+// LDS); the inverse is by conjugation.
+//
+//   ew_twiddle_kernel      exp(-2 pi i k / S), written into the workspace on every call
+//   ew_transfer_kernel     H [n][S][S] for the public transfer_function; the other kernels compute H on the fly and never read it
+//   ew_pass_kernel<OP>     a workgroup owns 8 consecutive lines of one image, one after the other: load a contiguous line (complex, or
+//                          float32 as the real part; elements >= n_in are zeros that are never read), transform, store n_out elements
+//                          with strides of the caller's choice: straight, or TRANSPOSED, where the 8 lines of a workgroup make the
+//                          eight 16-byte pieces of every 128-byte run.  OP: FWD; INV; PROP (forward, times H, inverse, without leaving
+//                          LDS); MOD (inverse, psi = a b / |b|, forward: the fused reconstruction's row launch)
+//   ew_recon_cols_kernel   the fused reconstruction's column launch: a workgroup owns one kx; for k = 0..N-1 it transforms the line of
+//                          image k, multiplies by H(-df_k) and accumulates in registers; then for every k it forms E^ H(+df_k) in LDS,
+//                          transforms back and stores transposed
+//   ew_mean_kernel, ew_modulus_kernel, ew_loss_*  the composed path's mean and modulus constraint, and the loss's two passes
+//
+// No floating-point atomics, every sum in a fixed order: bitwise reproducible.  Launches only; the defocuses are read on the device.
+#include <cmath>
+
+#include "fft_line.hpp"
+#include "stencil_rows.hpp"
+
+namespace {
+
+constexpr int kMinS = 8, kMaxS = 4096, kMaxN = 64, kMaxIter = 1000000;
+constexpr int kLines = 8;   // lines per workgroup of ew_pass_kernel: 8 x 16 bytes = one 128-byte run of a transposed store
+
+enum { OP_FWD = 0, OP_INV = 1, OP_PROP = 2, OP_MOD = 3 };
+
+bool size_ok(int S) { return S >= kMinS && S <= kMaxS && (S & (S - 1)) == 0; }
+// the padded side, or 0
+int padded_side(int s, int pad) {
+    if (s < 1 || pad < 0 || pad > kMaxS) return 0;
+    const long S = (long)s * (1 + pad);
+    return S <= kMaxS && size_ok((int)S) ? (int)S : 0;
+}
+
+struct Optics {
+    double lam, span, c4;   // wavelength; S px; 0.5 lam^3 Cs
+};
+
+Optics optics(double wavelength, double px, double cs, int S) {
+    Optics o;
+    o.lam = wavelength;
+    o.span = (double)S * px;
+    o.c4 = 0.5 * (wavelength * wavelength * wavelength) * cs;
+    return o;
+}
+
+// H at the unshifted indices (iy, ix): j = i below S / 2, else i - S; q = j / (S px); t = lam df q2 + 0.5 lam^3 Cs q2 q2, every
+// operation rounded on its own (as the float64 restatement); H = cospi(t) + i sinpi(t)
+__device__ __forceinline__ cplx transfer_h(int iy, int ix, int S, double df, Optics o) {
+#pragma clang fp contract(off)
+    const int jy = iy < (S >> 1) ? iy : iy - S, jx = ix < (S >> 1) ? ix : ix - S;
+    const double qy = (double)jy / o.span, qx = (double)jx / o.span;
+    const double q2 = qy * qy + qx * qx;
+    const double t = o.lam * df * q2 + o.c4 * q2 * q2;
+    double s, c;
+    sincospi(t, &s, &c);
+    return make_double2(c, s);
+}
+
+// a_k from the float32 image: |x|, or sqrt(max(x, 0)) of an intensity
+__device__ __forceinline__ double amplitude(float x, int from_intensity) {
+    const double v = (double)x;
+    return from_intensity ? sqrt(fmax(v, 0.0)) : fabs(v);
+}
+
+// psi = a b / |b|; a where |b| = 0 (the reference gives NaN there)
+__device__ __forceinline__ cplx restore_amplitude(double a, cplx b) {
+    const double m = sqrt(b.x * b.x + b.y * b.y);
+    return m > 0.0 ? make_double2(a * b.x / m, a * b.y / m) : make_double2(a, 0.0);
+}
+
+__global__ __launch_bounds__(256) void ew_twiddle_kernel(cplx* __restrict__ tw, int S) {
+    twiddle_entry(tw, S);
+}
+
+// grid (S * S / 256, n)
+__global__ __launch_bounds__(256) void ew_transfer_kernel(cplx* __restrict__ H, int S, const double* __restrict__ defocus, Optics o) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (long)S * S) return;
+    H[(long)blockIdx.y * S * S + j] = transfer_h((int)(j / S), (int)(j % S), S, defocus[blockIdx.y], o);
+}
+
+struct PassArgs {
+    const void* src;   // lines of complex doubles, or of float32 (src_real; 2: an intensity, sqrt(max(x, 0)) is loaded)
+    long src_batch, src_line;
+    int n_in, src_real;
+    cplx* dst;         // element i of line l of image b: dst[b dst_batch + l dst_line + i dst_elem], i < n_out
+    long dst_batch, dst_line, dst_elem;
+    int n_out, nlines, S;
+    const cplx* tw;
+    const double* defocus;   // PROP: df = sign defocus[b]
+    double sign;
+    Optics o;
+    const float* amp;        // MOD: the image, [B][nlines][S]
+    int from_intensity;
+};
+
+// grid (ceil(nlines / 8), B), S * 16 bytes of LDS.  A thread reads and rewrites only the elements tid + 256 u of the line outside
+// fft_line, whose first and last statements are barriers: no other barrier is needed between the lines of a workgroup.
+template <int OP>
+__global__ __launch_bounds__(256) void ew_pass_kernel(PassArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    cplx* line = reinterpret_cast<cplx*>(smem);
+    const int tid = threadIdx.x, S = a.S;
+    const long b = blockIdx.y;
+    const double inv = 1.0 / (double)S;
+    const int l0 = blockIdx.x * kLines, l1 = min(l0 + kLines, a.nlines);
+    for (int l = l0; l < l1; ++l) {
+        if (a.src_real) {
+            const float* p = static_cast<const float*>(a.src) + b * a.src_batch + (long)l * a.src_line;
+            for (int i = tid; i < S; i += 256) line[swz(i)] = make_double2(i < a.n_in ? (a.src_real == 2 ? amplitude(p[i], 1) : (double)p[i]) : 0.0, 0.0);
+        } else {
+            const cplx* p = static_cast<const cplx*>(a.src) + b * a.src_batch + (long)l * a.src_line;
+            for (int i = tid; i < S; i += 256) {
+                cplx v = i < a.n_in ? p[i] : make_double2(0.0, 0.0);
+                if (OP == OP_INV || OP == OP_MOD) v.y = -v.y;
+                line[swz(i)] = v;
+            }
+        }
+        fft_line(line, S, a.tw);
+        if (OP == OP_PROP) {
+            const double df = a.sign * a.defocus[b];
+            for (int i = tid; i < S; i += 256) {
+                const cplx v = cmul(line[swz(i)], transfer_h(i, l, S, df, a.o));
+                line[swz(i)] = make_double2(v.x, -v.y);
+            }
+            fft_line(line, S, a.tw);
+        }
+        if (OP == OP_MOD) {
+            const float* am = a.amp + (b * a.nlines + l) * S;
+            for (int i = tid; i < S; i += 256) {
+                const cplx v = line[swz(i)];
+                line[swz(i)] = restore_amplitude(amplitude(am[i], a.from_intensity), make_double2(v.x * inv, -v.y * inv));
+            }
+            fft_line(line, S, a.tw);
+        }
+        cplx* d = a.dst + b * a.dst_batch + (long)l * a.dst_line;
+        for (int i = tid; i < a.n_out; i += 256) {
+            cplx v = line[swz(i)];
+            if (OP == OP_INV || OP == OP_PROP) v = make_double2(v.x * inv, -v.y * inv);
+            d[(long)i * a.dst_elem] = v;
+        }
+    }
+}
+
+// grid (S), S * 16 bytes of LDS; NU = max(S / 256, 1) elements of the line per thread.  Wt: [N][kx][y] (the rows' transforms,
+// transposed); G: [N][y][kx] (b_k, inverse-transformed along y only); Eh: [y][kx] (the exit wave, likewise), or NULL.
+template <int NU>
+__global__ __launch_bounds__(256) void ew_recon_cols_kernel(const cplx* __restrict__ Wt, cplx* __restrict__ G, cplx* __restrict__ Eh, int N,
+                                                            int S, const cplx* __restrict__ tw, const double* __restrict__ defocus,
+                                                            Optics o) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    cplx* line = reinterpret_cast<cplx*>(smem);
+    const int tid = threadIdx.x, kx = blockIdx.x;
+    const double inv = 1.0 / (double)S, n = (double)N;
+    cplx acc[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) acc[u] = make_double2(0.0, 0.0);
+    for (int k = 0; k < N; ++k) {   // E^ = sum_k psi^_k H(-df_k), ascending k
+        const cplx* src = Wt + ((long)k * S + kx) * S;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) line[swz(i)] = src[i];
+        }
+        fft_line(line, S, tw);
+        const double df = -defocus[k];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) acc[u] = cadd(acc[u], cmul(line[swz(i)], transfer_h(i, kx, S, df, o)));
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) acc[u] = make_double2(acc[u].x / n, acc[u].y / n);
+    if (Eh) {
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) line[swz(i)] = make_double2(acc[u].x, -acc[u].y);
+        }
+        fft_line(line, S, tw);
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) {
+                const cplx v = line[swz(i)];
+                Eh[(long)i * S + kx] = make_double2(v.x * inv, -v.y * inv);
+            }
+        }
+    }
+    for (int k = 0; k < N; ++k) {   // b^_k = E^ H(+df_k), back along y
+        const double df = defocus[k];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) {
+                const cplx v = cmul(acc[u], transfer_h(i, kx, S, df, o));
+                line[swz(i)] = make_double2(v.x, -v.y);
+            }
+        }
+        fft_line(line, S, tw);
+        cplx* dst = G + (long)k * S * S + kx;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) {
+                const cplx v = line[swz(i)];
+                dst[(long)i * S] = make_double2(v.x * inv, -v.y * inv);
+            }
+        }
+    }
+}
+
+// grid (ceil(n / 256)): E[j] = (sum_k P[k][j]) / N, ascending k
+__global__ __launch_bounds__(256) void ew_mean_kernel(const cplx* __restrict__ P, int N, long n, cplx* __restrict__ E) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    cplx s = make_double2(0.0, 0.0);
+    for (int k = 0; k < N; ++k) s = cadd(s, P[k * n + j]);
+    E[j] = make_double2(s.x / (double)N, s.y / (double)N);
+}
+
+// grid (ceil(n / 256), N): psi = a b / |b|
+__global__ __launch_bounds__(256) void ew_modulus_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, long n, int from_intensity,
+                                                         cplx* __restrict__ psi) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const long e = blockIdx.y * n + j;
+    psi[e] = restore_amplitude(amplitude(img[e], from_intensity), Bw[e]);
+}
+
+#pragma clang fp contract(off)   // the loss: every operation rounds on its own, as in the host restatement
+
+// grid (s, N): part[k][y] = (sum of the image's row, sum of I = |b|^2 over the row)
+__global__ __launch_bounds__(256) void ew_loss_rows_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s,
+                                                           double* __restrict__ part) {
+    __shared__ double sh[4];
+    const long row = (long)blockIdx.y * s + blockIdx.x;
+    double si = 0.0, sI = 0.0;
+    for (int i = threadIdx.x; i < s; i += 256) {
+        const cplx v = Bw[row * s + i];
+        si += (double)img[row * s + i];
+        sI += v.x * v.x + v.y * v.y;
+    }
+    si = block_sum_thread0(si, sh);
+    sI = block_sum_thread0(sI, sh);
+    if (threadIdx.x == 0) {
+        part[2 * row] = si;
+        part[2 * row + 1] = sI;
+    }
+}
+
+// grid (s, N): c = mean(image) / mean(I) from the rows' sums, then resid[k][y] = sum over the row of (image - c I)^2
+__global__ __launch_bounds__(256) void ew_loss_resid_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s,
+                                                            const double* __restrict__ part, double* __restrict__ resid) {
+    __shared__ double sh[256];
+    const long k = blockIdx.y, row = k * s + blockIdx.x;
+    const double npx = (double)s * (double)s;
+    const double si = block_sum_fixed(part + 2 * k * s, s, 2, sh), sI = block_sum_fixed(part + 2 * k * s + 1, s, 2, sh);
+    const double c = (si / npx) / (sI / npx);
+    double r = 0.0;
+    for (int i = threadIdx.x; i < s; i += 256) {
+        const cplx v = Bw[row * s + i];
+        const double d = (double)img[row * s + i] - c * (v.x * v.x + v.y * v.y);
+        r += d * d;
+    }
+    r = block_tree_sum(r, sh);
+    if (threadIdx.x == 0) resid[row] = r;
+}
+
+// grid (N)
+__global__ __launch_bounds__(256) void ew_loss_final_kernel(const double* __restrict__ resid, int s, double* __restrict__ losses) {
+    __shared__ double sh[256];
+    const double r = block_sum_fixed(resid + (long)blockIdx.x * s, s, 1, sh);
+    if (threadIdx.x == 0) losses[blockIdx.x] = r / ((double)s * (double)s);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------
+
+struct Range {
+    const void* p;
+    size_t n;
+};
+
+bool any_overlap(const Range* r, int n) {
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (r[i].p && r[j].p && emd::overlap(r[i].p, r[i].n, r[j].p, r[j].n)) return true;
+    return false;
+}
+
+// The checks the entry points share, behind their shape checks: null pointers, the workspace's size, alignment, overlap.
+// all[0] is the workspace; the first nalign of all hold 16-byte elements, the others doubles (8-byte alignment); a range with
+// p == NULL is an optional argument that is absent.
+int common_check(const char* who, const Range* required, int nreq, size_t workspace_bytes, const Range* all, int nall, int nalign) {
+    for (int i = 0; i < nreq; ++i)
+        if (!required[i].p) {
+            emd::set_error("%s: null pointer", who);
+            return EMD_E_INVALID;
+        }
+    if (workspace_bytes < all[0].n) {
+        emd::set_error("%s: workspace too small (%zu bytes, needs %zu)", who, workspace_bytes, all[0].n);
+        return EMD_E_INVALID;
+    }
+    for (int i = 0; i < nall; ++i)
+        if (all[i].p && (reinterpret_cast<uintptr_t>(all[i].p) & (i < nalign ? 15u : 7u))) {
+            emd::set_error("%s: the inputs, the outputs and the workspace must be 16-byte aligned (arrays of doubles: 8-byte)", who);
+            return EMD_E_ALIGN;
+        }
+    if (any_overlap(all, nall)) {
+        emd::set_error("%s: the inputs, the outputs and the workspace may not overlap", who);
+        return EMD_E_INVALID;
+    }
+    return EMD_OK;
+}
+
+template <int OP>
+void launch_pass(const PassArgs& a, int B, hipStream_t st) {
+    hipLaunchKernelGGL(ew_pass_kernel<OP>, dim3((unsigned)emd::tiles_of(a.nlines, kLines), (unsigned)B), dim3(256), (size_t)a.S * sizeof(cplx),
+                       st, a);
+}
+
+void launch_twiddle(cplx* tw, int S, hipStream_t st) {
+    hipLaunchKernelGGL(ew_twiddle_kernel, dim3((unsigned)emd::tiles_of(S, 256)), dim3(256), 0, st, tw, S);
+}
+
+PassArgs pass_args(const void* src, int src_real, long src_batch, long src_line, int n_in, cplx* dst, long dst_batch, long dst_line,
+                   long dst_elem, int n_out, int nlines, int S, const cplx* tw) {
+    PassArgs a{};
+    a.src = src;
+    a.src_real = src_real;
+    a.src_batch = src_batch;
+    a.src_line = src_line;
+    a.n_in = n_in;
+    a.dst = dst;
+    a.dst_batch = dst_batch;
+    a.dst_line = dst_line;
+    a.dst_elem = dst_elem;
+    a.n_out = n_out;
+    a.nlines = nlines;
+    a.S = S;
+    a.tw = tw;
+    return a;
+}
+
+// out[b] = ifft2(fft2(pad(src[b])) H(sign defocus[b]))[:s, :s], three launches.  src: [.][s][s], images src_batch apart (0: one
+// wave to every focus); T: [B][S][s] (kx, then the s rows that are not zero); U: [B][s][S] (the s rows that are kept, then kx).
+void launch_propagate(const void* src, int src_real, long src_batch, int B, int s, int S, const double* defocus, double sign, Optics o,
+                      const cplx* tw, cplx* T, cplx* U, cplx* out, hipStream_t st) {
+    launch_pass<OP_FWD>(pass_args(src, src_real, src_batch, s, s, T, (long)S * s, 1, s, S, s, S, tw), B, st);
+    PassArgs c = pass_args(T, 0, (long)S * s, s, s, U, (long)s * S, 1, S, s, S, S, tw);
+    c.defocus = defocus;
+    c.sign = sign;
+    c.o = o;
+    launch_pass<OP_PROP>(c, B, st);
+    launch_pass<OP_INV>(pass_args(U, 0, (long)s * S, S, S, out, (long)s * s, s, 1, s, s, S, tw), B, st);
+}
+
+void launch_recon_cols(const cplx* Wt, cplx* G, cplx* Eh, int N, int S, const cplx* tw, const double* defocus, Optics o, hipStream_t st) {
+    const size_t lds = (size_t)S * sizeof(cplx);
+#define EW_COLS(NU) hipLaunchKernelGGL(ew_recon_cols_kernel<NU>, dim3((unsigned)S), dim3(256), lds, st, Wt, G, Eh, N, S, tw, defocus, o)
+    switch (S / 256) {
+        case 0:
+        case 1: EW_COLS(1); break;
+        case 2: EW_COLS(2); break;
+        case 4: EW_COLS(4); break;
+        case 8: EW_COLS(8); break;
+        default: EW_COLS(16); break;
+    }
+#undef EW_COLS
+}
+
+void launch_losses(const cplx* Bw, const float* images, int N, int s, double* part, double* resid, double* losses, hipStream_t st) {
+    hipLaunchKernelGGL(ew_loss_rows_kernel, dim3((unsigned)s, (unsigned)N), dim3(256), 0, st, Bw, images, s, part);
+    hipLaunchKernelGGL(ew_loss_resid_kernel, dim3((unsigned)s, (unsigned)N), dim3(256), 0, st, Bw, images, s, part, resid);
+    hipLaunchKernelGGL(ew_loss_final_kernel, dim3((unsigned)N), dim3(256), 0, st, resid, s, losses);
+}
+
+struct PropLayout {
+    size_t tw, T, U, bytes;
+};
+
+PropLayout prop_layout(int B, int s, int S) {
+    PropLayout l{};
+    size_t bytes = 0;
+    l.tw = bytes;
+    bytes += emd::round256((size_t)S * sizeof(cplx));
+    l.T = bytes;
+    bytes += emd::round256((size_t)B * S * s * sizeof(cplx));
+    l.U = bytes;
+    bytes += emd::round256((size_t)B * s * S * sizeof(cplx));
+    l.bytes = bytes;
+    return l;
+}
+
+// Fused (pad_periods == 0): W (the rows' transforms, transposed; b_k at the end), G, Eh.  Composed: psi, P (the propagated stack),
+// and the propagation's T and U.  Both: the loss's partial sums.
+struct ReconLayout {
+    bool fused;
+    size_t tw, A, Bf, Eh, T, U, part, resid, bytes;
+};
+
+ReconLayout recon_layout(int N, int s, int S) {
+    ReconLayout l{};
+    l.fused = S == s && !emd::g_knobs.exitwave_composed;
+    const size_t stack = emd::round256((size_t)N * s * s * sizeof(cplx));
+    size_t bytes = 0;
+    l.tw = bytes;
+    bytes += emd::round256((size_t)S * sizeof(cplx));
+    l.A = bytes;    // fused: W; composed: psi
+    bytes += stack;
+    l.Bf = bytes;   // fused: G; composed: P
+    bytes += stack;
+    if (l.fused) {
+        l.Eh = bytes;
+        bytes += emd::round256((size_t)S * S * sizeof(cplx));
+    } else {
+        l.T = bytes;
+        bytes += emd::round256((size_t)N * S * s * sizeof(cplx));
+        l.U = bytes;
+        bytes += emd::round256((size_t)N * s * S * sizeof(cplx));
+    }
+    l.part = bytes;
+    bytes += emd::round256((size_t)N * s * 2 * sizeof(double));
+    l.resid = bytes;
+    bytes += emd::round256((size_t)N * s * sizeof(double));
+    l.bytes = bytes;
+    return l;
+}
+
+bool batch_ok(int B) { return B >= 0 && B <= 65535; }
+
+}  // namespace
+
+extern "C" int emd_transfer_function_f64(int S, int n, const double* defocus, double wavelength, double px, double cs, double* H,
+                                         emd_stream_t stream) {
+    if (!size_ok(S) || !batch_ok(n) || !(px > 0.0)) {
+        emd::set_error("emd_transfer_function_f64: bad shape (S a power of two in %d..%d, 0..65535 defocuses, px > 0; got S = %d, n = %d)",
+                       kMinS, kMaxS, S, n);
+        return EMD_E_INVALID;
+    }
+    if (n == 0) return EMD_OK;
+    const Range req[] = {{defocus, (size_t)n * sizeof(double)}, {H, (size_t)n * S * S * sizeof(cplx)}};
+    const Range all[] = {{nullptr, 0}, req[1], req[0]};
+    const int rc = common_check("emd_transfer_function_f64", req, 2, 0, all, 3, 2);
+    if (rc != EMD_OK) return rc;
+    hipLaunchKernelGGL(ew_transfer_kernel, dim3((unsigned)emd::tiles_of(S * S, 256), (unsigned)n), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<cplx*>(H), S, defocus, optics(wavelength, px, cs, S));
+    return emd::check_launch("emd_transfer_function_f64");
+}
+
+extern "C" size_t emd_cfft2_workspace_bytes(int B, int S) {
+    if (B < 1 || !batch_ok(B) || !size_ok(S)) return 0;
+    return emd::round256((size_t)S * sizeof(cplx)) + emd::round256((size_t)B * S * S * sizeof(cplx));
+}
+
+extern "C" int emd_cfft2_f64(const double* x, int B, int S, int inverse, double* out, void* workspace, size_t workspace_bytes,
+                             emd_stream_t stream) {
+    if (!batch_ok(B) || !size_ok(S)) {
+        emd::set_error("emd_cfft2_f64: bad shape (batch 0..65535, S a power of two in %d..%d; got %d x %d x %d)", kMinS, kMaxS, B, S, S);
+        return EMD_E_INVALID;
+    }
+    if (B == 0) return EMD_OK;
+    const size_t nx = (size_t)B * S * S * sizeof(cplx);
+    const Range all[] = {{workspace, emd_cfft2_workspace_bytes(B, S)}, {x, nx}, {out, nx}};
+    const int rc = common_check("emd_cfft2_f64", all, 3, workspace_bytes, all, 3, 3);
+    if (rc != EMD_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    cplx* tw = static_cast<cplx*>(workspace);
+    cplx* T = reinterpret_cast<cplx*>(static_cast<char*>(workspace) + emd::round256((size_t)S * sizeof(cplx)));
+    launch_twiddle(tw, S, st);
+    const long SS = (long)S * S;
+    // rows, written transposed; then the columns, written transposed again
+    const PassArgs r = pass_args(x, 0, SS, S, S, T, SS, 1, S, S, S, S, tw);
+    const PassArgs c = pass_args(T, 0, SS, S, S, reinterpret_cast<cplx*>(out), SS, 1, S, S, S, S, tw);
+    if (inverse) {
+        launch_pass<OP_INV>(r, B, st);
+        launch_pass<OP_INV>(c, B, st);
+    } else {
+        launch_pass<OP_FWD>(r, B, st);
+        launch_pass<OP_FWD>(c, B, st);
+    }
+    return emd::check_launch("emd_cfft2_f64");
+}
+
+extern "C" size_t emd_propagate_workspace_bytes(int B, int s, int pad_periods) {
+    const int S = padded_side(s, pad_periods);
+    if (B < 1 || !batch_ok(B) || !S) return 0;
+    return prop_layout(B, s, S).bytes;
+}
+
+extern "C" int emd_propagate_f64(const void* psi, int psi_is_real_f32, int B, int s, int pad_periods, const double* defocus,
+                                 double wavelength, double px, double cs, double* out, void* workspace, size_t workspace_bytes,
+                                 emd_stream_t stream) {
+    const int S = padded_side(s, pad_periods);
+    if (!batch_ok(B) || !S || !(px > 0.0)) {
+        emd::set_error("emd_propagate_f64: bad shape (batch 0..65535, s (1 + pad_periods) a power of two in %d..%d, px > 0; got %d x %d x %d, "
+                       "pad_periods %d)", kMinS, kMaxS, B, s, s, pad_periods);
+        return EMD_E_INVALID;
+    }
+    if (B == 0) return EMD_OK;
+    const PropLayout l = prop_layout(B, s, S);
+    const size_t ne = (size_t)B * s * s;
+    const Range all[] = {{workspace, l.bytes}, {psi, ne * (psi_is_real_f32 ? sizeof(float) : sizeof(cplx))}, {out, ne * sizeof(cplx)},
+                         {defocus, (size_t)B * sizeof(double)}};
+    const int rc = common_check("emd_propagate_f64", all, 4, workspace_bytes, all, 4, 3);   // the defocuses are doubles
+    if (rc != EMD_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    cplx* tw = reinterpret_cast<cplx*>(ws + l.tw);
+    launch_twiddle(tw, S, st);
+    launch_propagate(psi, psi_is_real_f32 ? 1 : 0, (long)s * s, B, s, S, defocus, 1.0, optics(wavelength, px, cs, S), tw,
+                     reinterpret_cast<cplx*>(ws + l.T), reinterpret_cast<cplx*>(ws + l.U), reinterpret_cast<cplx*>(out), st);
+    return emd::check_launch("emd_propagate_f64");
+}
+
+extern "C" size_t emd_exitwave_workspace_bytes(int N, int s, int pad_periods) {
+    const int S = padded_side(s, pad_periods);
+    if (N < 1 || N > kMaxN || !S) return 0;
+    return recon_layout(N, s, S).bytes;
+}
+
+extern "C" int emd_exitwave_reconstruct_f64(const float* images, int N, int s, int pad_periods, const double* defocus, double wavelength,
+                                            double px, double cs, int iterations, int flags, double* E, double* stack, double* losses,
+                                            void* workspace, size_t workspace_bytes, emd_stream_t stream) {
+    const int S = padded_side(s, pad_periods);
+    if (N < 1 || N > kMaxN || !S || !(px > 0.0) || iterations < 1 || iterations > kMaxIter) {
+        emd::set_error("emd_exitwave_reconstruct_f64: bad shape (1..%d images, s (1 + pad_periods) a power of two in %d..%d, px > 0, "
+                       "1..%d iterations; got %d x %d x %d, pad_periods %d, %d iterations)", kMaxN, kMinS, kMaxS, kMaxIter, N, s, s,
+                       pad_periods, iterations);
+        return EMD_E_INVALID;
+    }
+    const ReconLayout l = recon_layout(N, s, S);
+    const size_t ne = (size_t)N * s * s;
+    const Range all[] = {{workspace, l.bytes},          {images, ne * sizeof(float)},        {E, (size_t)s * s * sizeof(cplx)},
+                         {stack, ne * sizeof(cplx)},    {losses, (size_t)N * sizeof(double)}, {defocus, (size_t)N * sizeof(double)}};
+    const Range req[] = {all[0], all[1], all[2], all[5]};
+    const int rc = common_check("emd_exitwave_reconstruct_f64", req, 4, workspace_bytes, all, 6, 4);   // losses, defocus: doubles
+    if (rc != EMD_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    cplx* tw = reinterpret_cast<cplx*>(ws + l.tw);
+    cplx* A = reinterpret_cast<cplx*>(ws + l.A);
+    cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
+    cplx* Ew = reinterpret_cast<cplx*>(E);
+    cplx* stk = reinterpret_cast<cplx*>(stack);
+    const Optics o = optics(wavelength, px, cs, S);
+    const int fi = (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0;
+    const long ss = (long)s * s;
+    const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
+    const cplx* bwave;   // b_k of the last iteration, [N][s][s]
+    launch_twiddle(tw, S, st);
+    if (l.fused) {
+        cplx* Eh = reinterpret_cast<cplx*>(ws + l.Eh);
+        // the rows of the images, transformed and written transposed: W[k][kx][y]
+        launch_pass<OP_FWD>(pass_args(images, fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), N, st);
+        for (int it = 0; it < iterations; ++it) {
+            const bool last = it == iterations - 1;
+            launch_recon_cols(A, Bf, last ? Eh : nullptr, N, S, tw, defocus, o, st);
+            if (!last) {
+                PassArgs m = pass_args(Bf, 0, ss, S, S, A, ss, 1, S, S, S, S, tw);
+                m.amp = images;
+                m.from_intensity = fi;
+                launch_pass<OP_MOD>(m, N, st);
+            }
+        }
+        launch_pass<OP_INV>(pass_args(Eh, 0, 0, S, S, Ew, 0, S, 1, S, S, S, tw), 1, st);
+        if (stack || losses) launch_pass<OP_INV>(pass_args(Bf, 0, ss, S, S, A, ss, S, 1, S, S, S, tw), N, st);
+        bwave = A;
+    } else {
+        cplx* T = reinterpret_cast<cplx*>(ws + l.T);
+        cplx* U = reinterpret_cast<cplx*>(ws + l.U);
+        for (int it = 0; it < iterations; ++it) {
+            const bool last = it == iterations - 1;
+            launch_propagate(it == 0 ? static_cast<const void*>(images) : A, it == 0 ? (fi ? 2 : 1) : 0, ss, N, s, S, defocus, -1.0, o, tw, T, U, Bf, st);
+            hipLaunchKernelGGL(ew_mean_kernel, dim3(tiles), dim3(256), 0, st, Bf, N, ss, Ew);
+            launch_propagate(Ew, 0, 0, N, s, S, defocus, 1.0, o, tw, T, U, Bf, st);
+            if (!last) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, images, ss, fi, A);
+        }
+        bwave = Bf;
+    }
+    if (stack) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, bwave, images, ss, fi, stk);
+    if (losses)
+        launch_losses(bwave, images, N, s, reinterpret_cast<double*>(ws + l.part), reinterpret_cast<double*>(ws + l.resid), losses, st);
+    return emd::check_launch("emd_exitwave_reconstruct_f64");
+}

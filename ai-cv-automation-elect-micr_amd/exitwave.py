@@ -1,0 +1,289 @@
+"""Exit-wave reconstruction from a through-focus series on the device (csrc/exitwave.hip): the reference's
+``ewrec.py`` / ``ewrec_class.py``.  Every image is propagated with a Fresnel transfer function between two 2-D FFTs, the results are
+averaged into an exit wave, the exit wave is propagated back to every focus, the measured amplitudes are restored, and so on.  The
+reference runs it on ArrayFire (and does not run as committed); here the formulas of include/emdenoise.h are the specification.
+
+Everything is double precision (complex128).  Images are square, of side s; the padded side ``S = s * (1 + pad_periods)`` is a power
+of two, 8..4096.  numpy in -> numpy out; torch CUDA tensor in -> device tensor out, on the current stream, with no host
+synchronisation; arguments are checked on the shape before anything moves to the device.  A defocus argument that is a float64 CUDA
+tensor is used where it is: such calls can be captured in a ``torch.cuda.graph`` and replayed after the tensor is overwritten.
+Anything else (a number, a list, a numpy array) is uploaded before the call, which a capture does not allow.
+
+Deviations from the reference: ``px`` (the pixel size) replaces its ``px_dim = 1 + pad_periods`` in the transfer function; where
+``|b_k| = 0`` the modulus constraint gives ``a_k`` (the reference: NaN); with ``from_intensity`` the amplitude is
+``sqrt(max(image_k, 0))`` and ``psi_k`` starts as that amplitude, not as the image; with ``cs != 0`` the back-propagation multiplies
+by ``H(-df)`` as the reference does, which is not ``conj H(df)`` (the Cs term keeps its sign; at ``cs == 0`` the two are equal bit
+for bit); ``aperture_mask``, the bisection after the defocus sweep,
+registration, ``refine_params``, TIFF reading and the display helpers are not here."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .metrics import _p, _ws
+
+MIN_SIDE, MAX_SIDE, MAX_IMAGES = 8, 4096, 64
+FROM_INTENSITY = 1               # EMD_EXITWAVE_FROM_INTENSITY
+COMPOSED_KNOB = "exitwave_composed"   # include/emdenoise_dev.h: the composed path at pad_periods == 0, for measurements and tests
+
+
+def _padded_side(name, s, pad_periods=0):
+    """S = s (1 + pad_periods), checked."""
+    if int(pad_periods) != pad_periods or pad_periods < 0:
+        raise ValueError(f"{name}: pad_periods must be a non-negative integer (got {pad_periods!r})")
+    if int(s) != s or s < 1:
+        raise ValueError(f"{name}: the side must be a positive integer (got {s!r})")
+    S = int(s) * (1 + int(pad_periods))
+    if not MIN_SIDE <= S <= MAX_SIDE or S & (S - 1):
+        raise ValueError(f"{name}: the padded side s (1 + pad_periods) must be a power of two, {MIN_SIDE}..{MAX_SIDE} "
+                         f"(got {s} x {1 + int(pad_periods)} = {S})")
+    return S
+
+
+def _shape3(name, a):
+    """(B, s, ndim) of a [B,s,s] or [s,s] argument, before anything is moved to the device."""
+    shp = tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+    if len(shp) == 2:
+        shp = (1,) + shp
+    if len(shp) != 3:
+        raise ValueError(f"{name}: [B,s,s] or [s,s] (got a shape of {len(shp)} dimensions)")
+    if shp[1] != shp[2]:
+        raise ValueError(f"{name}: square images, the padded side a power of two (got {shp[1]} x {shp[2]})")
+    return int(shp[0]), int(shp[1])
+
+
+def _positive(name, **kw):
+    for k, v in kw.items():
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name}: {k} must be positive and finite (got {v!r})")
+
+
+def _device(a):
+    import torch
+
+    return a.device if isinstance(a, torch.Tensor) and a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def _wave(a, device, real_ok):
+    """-> (contiguous CUDA tensor [B,s,s], complex128 -- or float32 where real_ok and a is real --, was_numpy)."""
+    import torch
+
+    is_np = not isinstance(a, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(a)) if is_np else a
+    if t.dim() == 2:
+        t = t.reshape(1, *t.shape)
+    if not t.is_cuda:
+        t = t.to(device)
+    if t.is_complex() or not real_ok:
+        t = t.to(torch.complex128)
+    else:
+        t = t.to(torch.float32)
+    return t.contiguous(), is_np
+
+
+def _defocus(name, defocus, B, device):
+    """-> float64 CUDA tensor [B].  A float64 CUDA tensor of B entries is used where it is."""
+    import torch
+
+    if isinstance(defocus, torch.Tensor) and defocus.is_cuda:
+        if defocus.dtype != torch.float64 or defocus.numel() != B or not defocus.is_contiguous():
+            raise ValueError(f"{name}: a device defocus must be a contiguous float64 tensor of {B} entries")
+        return defocus.reshape(B)
+    d = np.asarray(defocus.cpu() if isinstance(defocus, torch.Tensor) else defocus, np.float64)
+    if d.ndim == 0:
+        d = np.full(B, float(d))
+    if d.shape != (B,):
+        raise ValueError(f"{name}: one defocus, or one per image ({B}); got a shape of {d.shape}")
+    if not np.isfinite(d).all():
+        raise ValueError(f"{name}: the defocuses must be finite")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{name}: the defocuses are not on the device; pass a float64 CUDA tensor when capturing")
+    return torch.from_numpy(np.ascontiguousarray(d)).to(device)
+
+
+def _ret(t, ndim, as_np):
+    if ndim == 2:
+        t = t.reshape(t.shape[-2], t.shape[-1])
+    return t.cpu().numpy() if as_np else t
+
+
+def transfer_function(S, wavelength, defocus, px=1.0, cs=0.0):
+    """The Fresnel transfer function ``H = exp(i pi (lam df q^2 + 0.5 lam^3 Cs q^4))`` on the S x S grid of ``numpy.fft.fftfreq(S, px)``
+    (FFT order), complex128 ``[S,S]``; a sequence of N defocuses gives ``[N,S,S]``.  The phase is evaluated as include/emdenoise.h
+    writes it, operation by operation, and goes through ``sincospi``.  numpy out, unless ``defocus`` is a CUDA tensor."""
+    import torch
+
+    S = _padded_side("transfer_function", S)
+    _positive("transfer_function", wavelength=wavelength, px=px)
+    as_np = not (isinstance(defocus, torch.Tensor) and defocus.is_cuda)
+    scalar = (defocus.dim() if isinstance(defocus, torch.Tensor) else np.ndim(defocus)) == 0
+    n = 1 if scalar else len(defocus)
+    if not 1 <= n <= 65535:
+        raise ValueError(f"transfer_function: 1..65535 defocuses (got {n})")
+    device = _device(defocus)
+    d = _defocus("transfer_function", defocus, n, device)
+    H = torch.empty((n, S, S), dtype=torch.complex128, device=device)
+    _lib.check(_lib.load().emd_transfer_function_f64(S, n, _p(d), float(wavelength), float(px), float(cs), _p(H), _lib.stream_ptr()),
+               "emd_transfer_function_f64")
+    return _ret(H, 2 if scalar else 3, as_np)
+
+
+def _cfft2(name, z, inverse):
+    import torch
+
+    B, S = _shape3(name, z)
+    _padded_side(name, S)
+    ndim = len(np.shape(z)) if not hasattr(z, "dim") else z.dim()
+    x, as_np = _wave(z, _device(z), False)
+    lib = _lib.load()
+    out = torch.empty_like(x)
+    nbytes = lib.emd_cfft2_workspace_bytes(B, S)
+    ws = _ws(nbytes, x.device)
+    _lib.check(lib.emd_cfft2_f64(_p(x), B, S, int(inverse), _p(out), _p(ws), nbytes, _lib.stream_ptr()), "emd_cfft2_f64")
+    return _ret(out, ndim, as_np)
+
+
+def fft2(z):
+    """``numpy.fft.fft2`` over the last two axes of ``[B,S,S]`` (or ``[S,S]``), complex128; real input is cast."""
+    return _cfft2("fft2", z, False)
+
+
+def ifft2(z):
+    """``numpy.fft.ifft2`` (normalised by 1 / S^2), by conjugation around the forward transform."""
+    return _cfft2("ifft2", z, True)
+
+
+def propagate(psi, defocus, wavelength, px=1.0, cs=0.0, pad_periods=0):
+    """``ifft2(fft2(zero-pad psi to S x S, image at the top-left) * H(defocus_b))[:s, :s]`` of every wave of ``[B,s,s]`` (complex128, or
+    float32: a real image), complex128.  ``defocus``: one number, or one per wave.  Three launches after the twiddle table."""
+    import torch
+
+    B, s = _shape3("propagate", psi)
+    _padded_side("propagate", s, pad_periods)
+    _positive("propagate", wavelength=wavelength, px=px)
+    ndim = len(np.shape(psi)) if not hasattr(psi, "dim") else psi.dim()
+    device = _device(psi)
+    d = _defocus("propagate", defocus, B, device)
+    x, as_np = _wave(psi, device, True)
+    lib = _lib.load()
+    out = torch.empty((B, s, s), dtype=torch.complex128, device=device)
+    nbytes = lib.emd_propagate_workspace_bytes(B, s, int(pad_periods))
+    ws = _ws(nbytes, device)
+    _lib.check(lib.emd_propagate_f64(_p(x), int(x.dtype == torch.float32), B, s, int(pad_periods), _p(d), float(wavelength), float(px),
+                                     float(cs), _p(out), _p(ws), nbytes, _lib.stream_ptr()), "emd_propagate_f64")
+    return _ret(out, ndim, as_np)
+
+
+def _reconstruct(name, images, defocuses, wavelength, px, cs, iterations, pad_periods, from_intensity, want_stack, want_losses, composed):
+    """-> (E [s,s], stack [N,s,s] or None, losses [N] or None) on the device, and was_numpy."""
+    import torch
+
+    shp = tuple(images.shape) if hasattr(images, "shape") else np.shape(images)
+    if len(shp) != 3 or shp[1] != shp[2]:
+        raise ValueError(f"{name}: images are [N,s,s], square (got a shape of {shp})")
+    N, s = int(shp[0]), int(shp[1])
+    if not 1 <= N <= MAX_IMAGES:
+        raise ValueError(f"{name}: 1..{MAX_IMAGES} images (got {N})")
+    _padded_side(name, s, pad_periods)
+    _positive(name, wavelength=wavelength, px=px)
+    if int(iterations) != iterations or iterations < 1:
+        raise ValueError(f"{name}: iterations must be a positive integer (got {iterations!r})")
+    if isinstance(images, torch.Tensor) and images.is_complex() or not isinstance(images, torch.Tensor) and np.iscomplexobj(images):
+        raise ValueError(f"{name}: the images are real (float32)")
+    device = _device(images)
+    d = _defocus(name, defocuses, N, device)
+    x, as_np = _wave(images, device, True)
+    lib = _lib.load()
+    flags = FROM_INTENSITY if from_intensity else 0
+    E = torch.empty((s, s), dtype=torch.complex128, device=device)
+    stack = torch.empty((N, s, s), dtype=torch.complex128, device=device) if want_stack else None
+    losses = torch.empty((N,), dtype=torch.float64, device=device) if want_losses else None
+    if composed:
+        _lib.knob(COMPOSED_KNOB, 1)
+    try:   # the knob is read by the size query and by the call (host side, at launch time), and is back at its default afterwards
+        nbytes = lib.emd_exitwave_workspace_bytes(N, s, int(pad_periods))
+        ws = _ws(nbytes, device)
+        rc = lib.emd_exitwave_reconstruct_f64(_p(x), N, s, int(pad_periods), _p(d), float(wavelength), float(px), float(cs),
+                                              int(iterations), flags, _p(E), _p(stack), _p(losses), _p(ws), nbytes, _lib.stream_ptr())
+    finally:
+        if composed:
+            _lib.knob(COMPOSED_KNOB, 0)
+    _lib.check(rc, "emd_exitwave_reconstruct_f64")
+    return (E, stack, losses), as_np
+
+
+def reconstruct(images, defocuses, wavelength, px=1.0, cs=0.0, iterations=50, pad_periods=0, from_intensity=False, return_stack=False,
+                return_losses=False, _composed=False):
+    """The exit wave of a focal series ``images`` ``[N,s,s]`` float32 (1 <= N <= 64) taken at ``defocuses``.  The amplitudes are
+    ``|image_k|`` and ``psi_k`` starts as the image (``from_intensity``: ``sqrt(max(image_k, 0))``, and ``psi_k`` starts as that); every iteration
+    ``E = mean_k P(psi_k, -df_k)``, ``b_k = P(E, +df_k)``, ``psi_k = a_k b_k / |b_k|``.  Returns E of the last iteration, complex128
+    ``[s,s]``; with ``return_stack`` / ``return_losses`` a tuple that also holds the last psi ``[N,s,s]`` and the losses ``[N]`` (see
+    ``reconstruction_loss``).  With ``pad_periods == 0`` an iteration is two launches for the whole stack (the iteration restated in
+    the frequency domain); ``_composed`` (the library's development knob ``exitwave_composed``, for measurements and tests) runs it
+    through the launches of ``propagate`` instead, as ``pad_periods > 0`` does."""
+    outs, as_np = _reconstruct("reconstruct", images, defocuses, wavelength, px, cs, iterations, pad_periods, from_intensity, return_stack,
+                               return_losses, _composed)
+    outs = [o.cpu().numpy() if as_np else o for o in outs if o is not None]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def reconstruction_loss(images, defocuses, wavelength, per_image=False, **kw):
+    """``reconstruction_loss`` (ewrec_class.py:364-380): with E the reconstruction, ``I = |P(E, df_k)|^2`` and
+    ``c = mean(image_k) / mean(I)``, ``loss_k = mean((image_k - c I)^2)`` (two-pass, in double); the largest over the images, as the
+    reference returns it, or all of them (``per_image``: ``[N]``).  Keywords: ``px``, ``cs``, ``iterations``, ``pad_periods``,
+    ``from_intensity``, as ``reconstruct`` has them."""
+    kw = dict(kw)
+    composed = kw.pop("_composed", False)
+    args = {"px": 1.0, "cs": 0.0, "iterations": 50, "pad_periods": 0, "from_intensity": False}
+    unknown = sorted(set(kw) - set(args))
+    if unknown:
+        raise TypeError(f"reconstruction_loss: unexpected keyword(s) {unknown}; it takes {sorted(args)}")
+    args.update(kw)
+    (_, _, losses), as_np = _reconstruct("reconstruction_loss", images, defocuses, wavelength, args["px"], args["cs"], args["iterations"],
+                                         args["pad_periods"], args["from_intensity"], False, True, composed)
+    if not per_image:
+        losses = losses.max()
+    return (losses.cpu().numpy() if per_image else float(losses)) if as_np else losses
+
+
+def focal_ramp(n, series_type="cubic", middle=None, alternating=True, increasing=True):
+    """The relative defocuses of a series of n images (ewrec_class.py:387-404): ``dir * sign(x - mid) * gen(x - mid)``, gen the
+    identity ("linear"), the square ("quadratic") or the cube ("cubic"); mid = ``middle`` or n // 2 when ``alternating``, else 0.
+    float64 ``[n]``, on the host."""
+    gens = {"linear": lambda x: x, "quadratic": lambda x: x ** 2, "cubic": lambda x: x ** 3}
+    if series_type not in gens:
+        raise ValueError(f"focal_ramp: series_type is one of {sorted(gens)} (got {series_type!r})")
+    if int(n) != n or n < 1:
+        raise ValueError(f"focal_ramp: n must be a positive integer (got {n!r})")
+    mid = (middle if middle else int(n) // 2) if alternating else 0
+    direction = 1.0 if increasing else -1.0
+    x = np.arange(int(n), dtype=np.float64) - mid
+    return direction * np.sign(x) * gens[series_type](x)
+
+
+def defocus_sweep(images, wavelength, increments, ramp, **kw):
+    """``reconstruction_loss`` for every increment, the defocuses being ``increment * ramp``: float64 ``[len(increments)]``.  The
+    defocuses of all increments are uploaded once, the reconstructions run one after the other on the device, and the losses are
+    read back once at the end (numpy out for numpy images, else a device tensor).  Keywords: ``px``, ``cs``, ``iterations``,
+    ``pad_periods``, ``from_intensity``; always the largest loss over the images, so ``per_image`` is refused."""
+    import torch
+
+    unknown = sorted(set(kw) - {"px", "cs", "iterations", "pad_periods", "from_intensity", "_composed"})
+    if unknown:
+        raise TypeError(f"defocus_sweep: unexpected keyword(s) {unknown}")
+
+    inc = np.asarray(increments, np.float64).reshape(-1)
+    ramp = np.asarray(ramp, np.float64).reshape(-1)
+    shp = tuple(images.shape) if hasattr(images, "shape") else np.shape(images)
+    if len(shp) != 3 or ramp.shape[0] != shp[0]:
+        raise ValueError(f"defocus_sweep: images are [N,s,s] and the ramp has N entries (got {shp} and {ramp.shape[0]})")
+    if inc.size < 1 or not np.isfinite(inc).all() or not np.isfinite(ramp).all():
+        raise ValueError("defocus_sweep: at least one increment; increments and ramp finite")
+    _padded_side("defocus_sweep", shp[1], kw.get("pad_periods", 0))
+    device = _device(images)
+    x, as_np = _wave(images, device, True)
+    table = torch.from_numpy(inc[:, None] * ramp[None, :]).to(device)
+    out = torch.stack([reconstruction_loss(x, table[i], wavelength, **kw) for i in range(inc.size)])
+    return out.cpu().numpy() if as_np else out

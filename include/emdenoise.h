@@ -1213,6 +1213,44 @@ int emd_freq_stats_f64(const float* x, int B, int S, double* profile, double* fr
                        emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exit-wave reconstruction from a through-focus series (csrc/exitwave.hip): ewrec_class.py:100-110, :272-380.
+ * Everything is double precision; complex arrays are interleaved (re, im) doubles.  Square images of side s; the padded side is
+ * S = s (1 + pad_periods), a power of two, 8 <= S <= 4096 (pad_periods = 0, 1, 3, ...): the image sits at the top-left of an S x S
+ * array of zeros.  `defocus` is always a DEVICE pointer to one double per image: a search loop changes it without an upload inside
+ * the call, and a captured graph reads the new values on replay.
+ *
+ * Transfer function, at the unshifted (FFT-order) indices: j = i for i < S/2, else i - S; q = (double)j / ((double)S * px);
+ *     q2 = qy qy + qx qx;   t = lam df q2 + 0.5 lam^3 Cs q2 q2   (left to right, lam^3 = lam lam lam, every operation rounded on
+ *     its own);   H = cospi(t) + i sinpi(t).
+ * px (the pixel size) replaces the reference's `px_dim = 1 + pad_periods`.  H is [n][S][S].
+ *
+ * cfft2: numpy.fft.fft2 / ifft2 of x [B][S][S] (inverse != 0: normalised by 1 / S^2).
+ * propagate: out[b] = ifft2(fft2(pad(psi[b])) H(defocus[b]))[:s, :s], [B][s][s]; psi is complex, or float32 (the real part) when
+ *     psi_is_real_f32 != 0.  Rows and columns of the padding are never read or transformed on the way in, and only the s rows that
+ *     are kept are transformed on the way out.
+ * reconstruct: images [N][s][s] float32, 1 <= N <= 64; a_k = |image_k| (EMD_EXITWAVE_FROM_INTENSITY: sqrt(max(image_k, 0)));
+ *     psi_k starts as image_k + 0i (FROM_INTENSITY: as a_k); `iterations` times:  E = (sum_k P(psi_k, -df_k)) / N in ascending k;  b_k = P(E, +df_k);
+ *     psi_k = a_k b_k / |b_k|  (a_k where |b_k| = 0: the reference gives NaN).  E [s][s] is the last iteration's; stack (may be
+ *     NULL) [N][s][s] the last psi; losses (may be NULL) [N]: with I = |b_k|^2 of the last iteration and c = mean(image_k) / mean(I),
+ *     mean((image_k - c I)^2), two-pass in double.  With pad_periods == 0 the iteration runs in the frequency domain, two launches
+ *     per iteration for the whole stack; with pad_periods > 0 it is composed from the launches of emd_propagate_f64.
+ *     With Cs != 0, P(psi, -df) multiplies by H(-df), as the reference does, which is not conj H(df): the Cs term keeps its sign.
+ * No floating-point atomics, fixed summation orders: bitwise reproducible.  The workspace is the caller's; it, the inputs and the
+ * outputs are 16-byte aligned (defocus and losses: 8-byte, checked too) and may not overlap.  Launches only, on `stream`: capturable. */
+#define EMD_EXITWAVE_FROM_INTENSITY 1 /* the only bit of `flags` */
+int emd_transfer_function_f64(int S, int n, const double* defocus, double wavelength, double px, double cs, double* H,
+                              emd_stream_t stream);
+size_t emd_cfft2_workspace_bytes(int B, int S);
+int emd_cfft2_f64(const double* x, int B, int S, int inverse, double* out, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_propagate_workspace_bytes(int B, int s, int pad_periods);
+int emd_propagate_f64(const void* psi, int psi_is_real_f32, int B, int s, int pad_periods, const double* defocus, double wavelength,
+                      double px, double cs, double* out, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_exitwave_workspace_bytes(int N, int s, int pad_periods);
+int emd_exitwave_reconstruct_f64(const float* images, int N, int s, int pad_periods, const double* defocus, double wavelength, double px,
+                                 double cs, int iterations, int flags, double* E, double* stack, double* losses, void* workspace,
+                                 size_t workspace_bytes, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */

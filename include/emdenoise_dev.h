@@ -34,6 +34,9 @@
  *   split_variant (-1)  pointwise split32 GEMM pipeline variant (-1 = dispatch rule)
  *   split_lead (2)      pointwise split32 GEMM, 16x16x32 form: the DMA of tile kt + 3 issued in step kt into the stage of tile kt (whose fragments
  *                       are in registers): two tiles in flight on three stages; 1 = one step ahead (round 2's schedule; same bits)
+ *   exitwave_composed (0)  emd_exitwave_reconstruct_f64 at pad_periods == 0: 1 = the iteration composed from the launches of
+ *                       emd_propagate_f64 (the path of pad_periods > 0) instead of the two-launch frequency-domain iteration; differences
+ *                       at rounding level.  emd_exitwave_workspace_bytes follows it: set it before asking for the size
  */
 #ifndef EMDENOISE_DEV_H
 #define EMDENOISE_DEV_H
