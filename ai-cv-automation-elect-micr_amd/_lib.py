@@ -472,6 +472,17 @@ SIGNATURES = {
     # images N s pad_periods defocus wavelength px cs iterations flags E stack losses workspace ws_bytes stream
     "emd_exitwave_reconstruct_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                                C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- registration of a focal series (csrc/register.hip)
+    # S w1 w2 stream
+    "emd_hanning_window_f64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "emd_phase_correlate_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # a b P S flags shifts surface workspace ws_bytes stream
+    "emd_phase_correlate_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
+    # shifts N S centres stream
+    "emd_stack_centres_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # images N S centres side pad_val out stream
+    "emd_crop_stack_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

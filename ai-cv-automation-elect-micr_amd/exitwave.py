@@ -13,8 +13,15 @@ Deviations from the reference: ``px`` (the pixel size) replaces its ``px_dim = 1
 ``|b_k| = 0`` the modulus constraint gives ``a_k`` (the reference: NaN); with ``from_intensity`` the amplitude is
 ``sqrt(max(image_k, 0))`` and ``psi_k`` starts as that amplitude, not as the image; with ``cs != 0`` the back-propagation multiplies
 by ``H(-df)`` as the reference does, which is not ``conj H(df)`` (the Cs term keeps its sign; at ``cs == 0`` the two are equal bit
-for bit); ``aperture_mask``, the bisection after the defocus sweep,
-registration, ``refine_params``, TIFF reading and the display helpers are not here."""
+for bit); ``aperture_mask``, the bisection after the defocus sweep, ``cv2.resize`` of the crops, ``refine_params``, TIFF reading and
+the display helpers are not here.
+
+Registration (csrc/register.hip) is what the reference's ``EWREC.__init__`` does before it reconstructs:
+``phase_correlate`` / ``rel_pos_estimate`` (``cv2.phaseCorrelate`` restated in include/emdenoise.h; OpenCV is not run), the cropping
+centres, ``crop_stack`` (a bilinear sub-pixel crop), and ``align`` / ``reconstruct_series`` that chain them on the device.  Deviations:
+``R = P / |P|`` is 0 where ``|P| = 0`` (OpenCV adds an epsilon); images of zeros give shift (0, 0) and response 0 (cv2: NaN); the
+centres are ``S/2 + pos - mean(pos)`` (the reference's loop does not run and its sign moves the crop against the drift); the crop is
+bilinear (the reference weights the wrong tap and returns the integer crop)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,6 +34,8 @@ from .metrics import _p, _ws
 MIN_SIDE, MAX_SIDE, MAX_IMAGES = 8, 4096, 64
 FROM_INTENSITY = 1               # EMD_EXITWAVE_FROM_INTENSITY
 COMPOSED_KNOB = "exitwave_composed"   # include/emdenoise_dev.h: the composed path at pad_periods == 0, for measurements and tests
+PC_WINDOW, PC_CHAIN = 1, 2       # EMD_PC_WINDOW, EMD_PC_CHAIN
+MAX_PAIRS, MAX_CROPS = 64, 65535
 
 
 def _padded_side(name, s, pad_periods=0):
@@ -287,3 +296,187 @@ def defocus_sweep(images, wavelength, increments, ramp, **kw):
     table = torch.from_numpy(inc[:, None] * ramp[None, :]).to(device)
     out = torch.stack([reconstruction_loss(x, table[i], wavelength, **kw) for i in range(inc.size)])
     return out.cpu().numpy() if as_np else out
+
+
+# ---- registration and cropping (csrc/register.hip) -----------------------------------------------------------------
+
+def _stack(name, a, min_images=1, max_images=MAX_CROPS, power_of_two=True):
+    """(N, S) of an [N,S,S] argument, checked before anything moves."""
+    import torch
+
+    shp = tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+    if len(shp) != 3 or shp[1] != shp[2]:
+        raise ValueError(f"{name}: images are [N,S,S], square (got a shape of {shp})")
+    N, S = int(shp[0]), int(shp[1])
+    if not min_images <= N <= max_images:
+        raise ValueError(f"{name}: {min_images}..{max_images} images (got {N})")
+    if power_of_two:
+        _padded_side(name, S)
+    elif not 1 <= S <= MAX_SIDE:
+        raise ValueError(f"{name}: the side of the images must be 1..{MAX_SIDE} (got {S})")
+    if isinstance(a, torch.Tensor) and a.is_complex() or not isinstance(a, torch.Tensor) and np.iscomplexobj(a):
+        raise ValueError(f"{name}: the images are real (float32)")
+    return N, S
+
+
+def _real(a, device):
+    """-> (contiguous float32 CUDA tensor, was_numpy)."""
+    import torch
+
+    is_np = not isinstance(a, torch.Tensor)
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) if is_np else a
+    return t.to(device=device, dtype=torch.float32).contiguous(), is_np
+
+
+def hanning_window(S, one_d=False):
+    """``cv2.createHanningWindow((S, S), CV_64F)``: ``sqrt(w[y] w[x])`` with ``w[i] = 0.5 (1 - cos(2 pi i / (S - 1)))``, float64
+    ``[S,S]`` on the host -- the bits that ``phase_correlate(window=True)`` multiplies the images by, computed by the same device
+    function.  ``one_d``: the table ``w`` ``[S]`` instead."""
+    import torch
+
+    S = _padded_side("hanning_window", S)
+    device = torch.device("cuda", torch.cuda.current_device())
+    w = torch.empty((S,) if one_d else (S, S), dtype=torch.float64, device=device)
+    _lib.check(_lib.load().emd_hanning_window_f64(S, _p(w if one_d else None), _p(None if one_d else w), _lib.stream_ptr()),
+               "emd_hanning_window_f64")
+    return w.cpu().numpy()
+
+
+def _correlate(name, a, b, P, S, flags, want_surface):
+    """-> (shifts [P,3], surface [P,S,S] or None) on the device of ``a`` (a contiguous float32 CUDA tensor, as ``b`` or None)."""
+    import torch
+
+    lib = _lib.load()
+    shifts = torch.empty((P, 3), dtype=torch.float64, device=a.device)
+    surface = torch.empty((P, S, S), dtype=torch.float64, device=a.device) if want_surface else None
+    nbytes = lib.emd_phase_correlate_workspace_bytes(P, S, flags)
+    ws = _ws(nbytes, a.device)
+    _lib.check(lib.emd_phase_correlate_f64(_p(a), _p(b), P, S, flags, _p(shifts), _p(surface), _p(ws), nbytes, _lib.stream_ptr()), name)
+    return shifts, surface
+
+
+def phase_correlate(a, b, window=False, return_response=False, return_surface=False):
+    """``cv2.phaseCorrelate(a, b[, hanning window])`` of every pair of ``a``, ``b`` ``[B,S,S]`` (1 <= B <= 64; or ``[S,S]``: one pair),
+    float32, S a power of two, 8..4096, as include/emdenoise.h restates it: float64 ``[B,2]`` = (dx, dy) (``[2]`` for one ``[S,S]`` pair);
+    if b is a displaced by +d the shift is +d; a and b may be the same tensor (an autocorrelation) or overlapping views.  ``return_response`` adds the responses ``[B]`` (the sum of the 5 x 5 window around the
+    peak), ``return_surface`` the correlation surfaces ``[B,S,S]`` in ``fftshift`` order; then a tuple is returned."""
+    B, S = _shape3("phase_correlate", a)
+    if _shape3("phase_correlate", b) != (B, S):
+        raise ValueError(f"phase_correlate: a and b must have the same shape (got {tuple(np.shape(a))} and {tuple(np.shape(b))})")
+    _padded_side("phase_correlate", S)
+    if not 1 <= B <= MAX_PAIRS:
+        raise ValueError(f"phase_correlate: 1..{MAX_PAIRS} pairs (got {B})")
+    ndim = len(np.shape(a)) if not hasattr(a, "dim") else a.dim()
+    device = _device(a)
+    x, as_np = _real(a, device)
+    y, _ = _real(b, device)
+    shifts, surface = _correlate("emd_phase_correlate_f64", x.reshape(B, S, S), y.reshape(B, S, S), B, S, PC_WINDOW if window else 0,
+                                 return_surface)
+    outs = [shifts[:, :2]] + ([shifts[:, 2]] if return_response else []) + ([surface] if return_surface else [])
+    if ndim == 2:
+        outs = [o[0] for o in outs]
+    outs = [o.cpu().numpy() if as_np else o for o in outs]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def _stack_centres(shifts, N, S):
+    import torch
+
+    centres = torch.empty((N, 2), dtype=torch.float64, device=shifts.device)
+    _lib.check(_lib.load().emd_stack_centres_f64(_p(shifts), N, S, _p(centres), _lib.stream_ptr()), "emd_stack_centres_f64")
+    return centres
+
+
+def rel_pos_estimate(stack, window=False, as_cropping_centres=True):
+    """``rel_pos_estimate`` (ewrec_class.py:240-269): the shifts between consecutive images of ``stack`` ``[N,S,S]`` (2 <= N <= 65) by
+    phase correlation, every image transformed once; float64 ``[N-1,2]`` = (dx, dy) of the pairs (k, k+1), or, with
+    ``as_cropping_centres``, ``[N,2]`` = (x, y): ``S/2 + pos_k - mean(pos)`` with ``pos_0 = 0``, ``pos_k = pos_{k-1} + shift_{k-1}``."""
+    N, S = _stack("rel_pos_estimate", stack, 2, MAX_PAIRS + 1)
+    x, as_np = _real(stack, _device(stack))
+    shifts, _ = _correlate("emd_phase_correlate_f64", x, None, N - 1, S, PC_CHAIN | (PC_WINDOW if window else 0), False)
+    out = _stack_centres(shifts, N, S) if as_cropping_centres else shifts[:, :2]
+    return out.cpu().numpy() if as_np else out
+
+
+def largest_crop_side(centres, S, power_of_two=True):
+    """The largest side a crop around every one of ``centres`` ``[N,2]`` can have inside images of side S (ewrec_class.py:193-200, with
+    ``min`` where the reference has a comparison that never fires): ``int(2 min(x, y, S - x, S - y))`` over all centres, floored to a
+    power of two unless ``power_of_two`` is false.  On the host (a device tensor is read back)."""
+    c = np.asarray(centres.detach().cpu() if hasattr(centres, "detach") else centres, np.float64)
+    if c.ndim != 2 or c.shape[1] != 2 or c.shape[0] < 1 or not np.isfinite(c).all():
+        raise ValueError(f"largest_crop_side: centres are [N,2], finite (got a shape of {c.shape})")
+    side = int(2.0 * min(c.min(), (float(S) - c).min()))
+    if side < 1:
+        raise ValueError(f"largest_crop_side: a centre lies outside the images (side {S})")
+    return 1 << (side.bit_length() - 1) if power_of_two else side
+
+
+def _crop(x, centres, side, pad_val):
+    import torch
+
+    N, S = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty((N, side, side), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().emd_crop_stack_f32(_p(x), N, S, _p(centres), side, float(pad_val), _p(out), _lib.stream_ptr()),
+               "emd_crop_stack_f32")
+    return out
+
+
+def _side(name, side, S):
+    if int(side) != side or not 1 <= side <= S:
+        raise ValueError(f"{name}: side must be an integer, 1..{S} (got {side!r})")
+    return int(side)
+
+
+def crop_stack(stack, centres, side, pad_val=0.0):
+    """``crop_stack`` (ewrec_class.py:190-229) as a bilinear sub-pixel crop: ``side x side`` pixels around ``centres[k]`` = (x, y) from
+    image k of ``stack`` ``[N,S,S]`` float32 (S 1..4096, 1 <= side <= S): float32 ``[N,side,side]``.  The window starts at
+    ``centre - side / 2``; a tap outside the image reads ``pad_val``.  ``centres``: ``[N,2]``; a contiguous float64 CUDA tensor is used
+    where it is (capturable), anything else is uploaded."""
+    import torch
+
+    N, S = _stack("crop_stack", stack, 1, MAX_CROPS, power_of_two=False)
+    side = _side("crop_stack", side, S)
+    if tuple(centres.shape if hasattr(centres, "shape") else np.shape(centres)) != (N, 2):
+        raise ValueError(f"crop_stack: centres are [N,2] = [{N},2]")
+    if not np.isfinite(pad_val):
+        raise ValueError(f"crop_stack: pad_val must be finite (got {pad_val!r})")
+    device = _device(stack)
+    if isinstance(centres, torch.Tensor) and centres.is_cuda:
+        if centres.dtype != torch.float64 or not centres.is_contiguous():
+            raise ValueError("crop_stack: device centres must be a contiguous float64 tensor")
+        c = centres
+    else:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("crop_stack: the centres are not on the device; pass a float64 CUDA tensor when capturing")
+        c = torch.from_numpy(np.ascontiguousarray(centres.cpu() if isinstance(centres, torch.Tensor) else centres, dtype=np.float64)).to(device)
+    x, as_np = _real(stack, device)
+    out = _crop(x, c, side, pad_val)
+    return out.cpu().numpy() if as_np else out
+
+
+def align(stack, side=None, window=False, pad_val=0.0):
+    """Registers ``stack`` ``[N,S,S]`` (2 <= N <= 65) and cuts the aligned crops: ``(crops [N,side,side] float32, centres [N,2]
+    float64)``.  With ``side`` given and a CUDA tensor in, it is three C calls on the current stream (correlation in chain mode,
+    centres, crop) with no read-back; ``side=None`` reads the centres back for ``largest_crop_side``."""
+    N, S = _stack("align", stack, 2, MAX_PAIRS + 1)
+    if side is not None:
+        side = _side("align", side, S)
+    x, as_np = _real(stack, _device(stack))
+    shifts, _ = _correlate("emd_phase_correlate_f64", x, None, N - 1, S, PC_CHAIN | (PC_WINDOW if window else 0), False)
+    centres = _stack_centres(shifts, N, S)
+    if side is None:
+        side = largest_crop_side(centres, S)
+    crops = _crop(x, centres, side, pad_val)
+    return (crops.cpu().numpy(), centres.cpu().numpy()) if as_np else (crops, centres)
+
+
+def reconstruct_series(stack, defocuses, wavelength, side, window=False, **reconstruct_kw):
+    """``align(stack, side, window)``, then ``reconstruct`` of the crops with ``reconstruct_kw``: what ``EWREC.__init__`` does with a
+    recorded series.  2 <= N <= 64 images (``reconstruct``'s limit; ``align`` and ``rel_pos_estimate`` alone take 65);
+    ``side (1 + pad_periods)`` is a power of two, 8..4096.  With a CUDA stack and float64 CUDA defocuses the whole
+    call is launches on the current stream and can be captured in one ``torch.cuda.graph``."""
+    N, S = _stack("reconstruct_series", stack, 2, MAX_PAIRS)
+    side = _side("reconstruct_series", side, S)
+    _padded_side("reconstruct_series", side, reconstruct_kw.get("pad_periods", 0))
+    crops, _ = align(stack, side, window)
+    return reconstruct(crops, defocuses, wavelength, **reconstruct_kw)

@@ -1251,6 +1251,52 @@ int emd_exitwave_reconstruct_f64(const float* images, int N, int s, int pad_peri
                                  size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Registration of a focal series (csrc/register.hip): what ewrec_class.py:140-177 does before it reconstructs --
+ * the drift between consecutive images by phase correlation (:240-269), the chain of the shifts into one cropping centre per image,
+ * the sub-pixel crop around each centre (:190-229).  cv2 is not available: the formulas below are the specification.  Every pointer
+ * but the workspace sizes' is a DEVICE pointer; launches only, on `stream`, no host synchronisation, no upload: capturable; no
+ * floating-point atomics, fixed orders: bitwise reproducible.
+ *
+ * Phase correlation, cv2.phaseCorrelate(a, b[, window]) restated.  Images float32 [S][S], S a power of two, 8 <= S <= 4096; all
+ * arithmetic in double.
+ *   window (EMD_PC_WINDOW), cv2.createHanningWindow's: w[i] = 0.5 (1 - cos(2 pi i / (S - 1))), evaluated as numpy's
+ *       0.5 * (1 - cos(2 * pi * i / (S - 1))); the image is multiplied by sqrt(w[y] w[x]).  emd_hanning_window_f64 writes the same
+ *       bits: w1 [S] and w2 [S][S] = sqrt(w[y] w[x]) (either may be NULL).
+ *   P = F(a) conj F(b);  R = P / |P| where |P| > 0, else 0 (OpenCV adds an epsilon to the denominator instead);
+ *   c = Re ifft2(R), normalised by 1 / S^2, viewed in fftshift order: c_s[y][x] = c[(y + S/2) mod S][(x + S/2) mod S].
+ *   peak: the largest c_s; on a tie the first in row-major order of c_s.
+ *   centroid: over rows and columns peak - 2 .. peak + 2 clipped to [0, S - 1] (not wrapped), in row-major order, in double:
+ *       sv += v; sx += x v; sy += y v (every operation rounded on its own);  (cx, cy) = (sx / sv, sy / sv).
+ *   shift = (S/2 - cx, S/2 - cy): if b is a displaced by +d, the shift is +d.  response = sv.  Where sv = 0 (images of zeros):
+ *       shift = (0, 0), response = 0 (cv2: NaN).
+ *   shifts [P][3] = (dx, dy, response), 1 <= P <= 64 pairs; surface: NULL, or [P][S][S] = c_s.  Pair p is (a[p], b[p]); with
+ *   EMD_PC_CHAIN `a` holds P + 1 images, b is NULL, pair p is (a[p], a[p + 1]) and every image is transformed once.  Chain and pair
+ *   mode give the same bits on the same pairs.  Four launches after the tables' (rows; columns with R formed in LDS between the forward
+ *   and the inverse transform; rows back with the peak's partials; one wave per pair for the peak and the centroid).
+ *   The workspace is 16-byte aligned, doubles 8-byte, images 4-byte.  The outputs and the workspace may overlap neither one another
+ *   nor the inputs; a and b are only read and may share bytes (a == b is an autocorrelation).
+ *
+ * Centres: shifts [N - 1][3] of the pairs (k, k + 1) (the response is not read), 2 <= N <= 65, images of side S (1..4096):
+ *   pos_0 = 0; pos_k = pos_{k-1} + shift_{k-1}; m = (sum_k pos_k, ascending from pos_0) / N; centre_k = (S / 2 + pos_k) - m, as
+ *   (x, y) in centres [N][2].  (The reference's loop does not run as written, has one entry too few and returns S/2 + m - pos, which
+ *   under the sign convention above moves the crop against the drift.)
+ *
+ * Crop: images [N][S][S] float32 (1 <= N <= 65535, 1 <= S <= 4096), 1 <= side <= S, out [N][side][side] float32.  Per image and axis
+ *   x0 = cx - (double)side / 2; ix = floor(x0); fx = x0 - ix; then, every operation rounded on its own in double,
+ *   out[r][c] = (float)((1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11)),  p_jk = image[iy + r + j][ix + c + k], or
+ *   pad_val where that tap is outside the image.  (The reference weights the left tap with the fraction, which is not bilinear, and
+ *   then returns the integer crop.) */
+#define EMD_PC_WINDOW 1
+#define EMD_PC_CHAIN 2
+int emd_hanning_window_f64(int S, double* w1, double* w2, emd_stream_t stream);
+size_t emd_phase_correlate_workspace_bytes(int P, int S, int flags);
+int emd_phase_correlate_f64(const float* a, const float* b, int P, int S, int flags, double* shifts, double* surface, void* workspace,
+                            size_t workspace_bytes, emd_stream_t stream);
+int emd_stack_centres_f64(const double* shifts, int N, int S, double* centres, emd_stream_t stream);
+int emd_crop_stack_f32(const float* images, int N, int S, const double* centres, int side, float pad_val, float* out,
+                       emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
