@@ -483,6 +483,26 @@ SIGNATURES = {
     "emd_stack_centres_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # images N S centres side pad_val out stream
     "emd_crop_stack_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    # ---- affine registration by mutual information, and warping (csrc/affine.hip)
+    # images N H W T shared_T fill out stream
+    "emd_warp_affine_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    # n H W seed samples stream
+    "emd_mi_samples_u32": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "emd_mattes_mi_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # fixed moving P H W T samples n bins mi status hist workspace ws_bytes stream
+    "emd_mattes_mi_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # iterations P first_iteration seed normals stream
+    "emd_affine_normals_f64": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
+    # fixed moving P H W samples n bins initial_radius growth epsilon seed variates variates_rows flags T0 first_iteration iterations
+    # state workspace ws_bytes stream
+    "emd_affine_register_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                          C.c_double, C.c_double, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # T_pairs N middle C stream
+    "emd_affine_chain_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # C N H W limits stream
+    "emd_affine_limits_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

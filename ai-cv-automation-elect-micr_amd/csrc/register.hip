@@ -286,39 +286,8 @@ __global__ __launch_bounds__(256) void reg_crop_kernel(const float* __restrict__
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-struct Range {
-    const void* p;
-    size_t n;
-    unsigned align;   // bytes
-    bool optional;    // may be NULL
-    bool input;       // read only: two inputs may share bytes (a == b is an autocorrelation)
-};
-
-// Null pointers, then the workspace's size (r[0] where workspace_bytes != NULL), alignment (`aligned`: the caller's sentence), and
-// overlap of every output and the workspace with everything else.
-int check_ranges(const char* who, const Range* r, int n, const char* aligned, const size_t* workspace_bytes = nullptr) {
-    for (int i = 0; i < n; ++i)
-        if (!r[i].p && !r[i].optional) {
-            emd::set_error("%s: null pointer", who);
-            return EMD_E_INVALID;
-        }
-    if (workspace_bytes && *workspace_bytes < r[0].n) {
-        emd::set_error("%s: workspace too small (%zu bytes, needs %zu)", who, *workspace_bytes, r[0].n);
-        return EMD_E_INVALID;
-    }
-    for (int i = 0; i < n; ++i)
-        if (r[i].p && (reinterpret_cast<uintptr_t>(r[i].p) & (r[i].align - 1))) {
-            emd::set_error("%s: %s", who, aligned);
-            return EMD_E_ALIGN;
-        }
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (r[i].p && r[j].p && !(r[i].input && r[j].input) && emd::overlap(r[i].p, r[i].n, r[j].p, r[j].n)) {
-                emd::set_error("%s: the outputs and the workspace may overlap neither one another nor the inputs", who);
-                return EMD_E_INVALID;
-            }
-    return EMD_OK;
-}
+using emd::check_ranges;
+using emd::Range;
 
 struct PcLayout {
     size_t tw, win, T, G, surf, pval, pidx, bytes;

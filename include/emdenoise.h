@@ -1297,6 +1297,111 @@ int emd_crop_stack_f32(const float* images, int N, int S, const double* centres,
                        emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Affine registration of a focal series by mutual information, and warping (csrc/affine.hip): what
+ * misc_py/evolutionary_align.m (imregtform with imregconfig('multimodal'): Mattes mutual information on random samples under a (1+1)
+ * evolutionary optimizer) and misc_py/warp_stack.m (the transforms chained onto the middle image, imwarp, the common rectangle) do.
+ * MATLAB is not available: the formulas below are the specification.  Every pointer is a DEVICE pointer; launches only, on `stream`, no
+ * host synchronisation, no upload: capturable; no floating-point atomics: two runs give the same bits.  Images are float32 [N][H][W],
+ * 8 <= H, W <= 4096, not necessarily equal or powers of two.  All arithmetic is in double, every operation rounded on its own, every
+ * expression evaluated left to right as written.
+ *
+ * Conventions.  Pixel coordinates are zero-based (x, y); c = ((W - 1) / 2, (H - 1) / 2); h = max(H, W) / 2; the normalised
+ *   coordinates are u = (x - cx) / h, v = (y - cy) / h.  A transform T is 2 x 3 doubles, row-major, in normalised coordinates, and a PULL
+ *   map: it takes a point of the fixed (output) frame to the point of the moving (input) frame that is sampled there,
+ *       u' = (T00 u + T01 v) + T02;  v' = (T10 u + T11 v) + T12;  x' = u' h + cx;  y' = v' h + cy.
+ *   The optimizer's six parameters are p = T - [I | 0].  In pixel coordinates the same map is the 3 x 3 matrix
+ *   [T00 T01 (T02 h + cx - T00 cx - T01 cy); T10 T11 (T12 h + cy - T10 cx - T11 cy); 0 0 1] on column vectors.  MATLAB's tform.T (row
+ *   vectors, the forward map from moving to fixed) is the transpose of the inverse of that matrix (one-based coordinates aside).
+ *   MATLAB's optimizer scales its parameters internally; here the normalised coordinates do that: all six have the magnitude of a
+ *   displacement in units of half the image.
+ *
+ * Warp: imwarp(img, T, 'OutputView', imref2d(size(img))) with linear interpolation.  T is [N][6], or [6] shared by all images
+ *   (shared_T != 0).  ix = floor(x'), fx = x' - ix, likewise y;
+ *       out = (float)((1 - fy) ((1 - fx) p00 + fx p01) + fy ((1 - fx) p10 + fx p11)),  p_jk = image[iy + j][ix + k]
+ *   (emd_crop_stack_f32's arithmetic); a tap outside the image reads `fill`; where no tap is inside the output is `fill` itself; a
+ *   coordinate that is not finite puts every tap outside.
+ *
+ * Samples: samples[i] = mulhi32(r_i, H W), r_i the word i % 4 of philox4x32_10 with counter (i / 4, 0, 0, 7) and key (seed lo, seed hi):
+ *   pixel indices y W + x, drawn with replacement.
+ *
+ * Metric: Mattes mutual information of P pairs (fixed[p], moving[p]) under one candidate T[p] each.  fmin, fmax are the extrema of the
+ *   whole fixed image, mmin, mmax of the whole moving image (exact, found on the device; NaN pixels are passed over).  samples == NULL
+ *   and n == 0: every fixed pixel in row-major order; else n indices (an index >= H W is passed over).  Per sample at (x, y): f the
+ *   fixed pixel; (x', y') as above; the sample counts iff 0 <= x' <= W - 1 and 0 <= y' <= H - 1 (false for a value that is not
+ *   finite); m is the bilinear value of the moving image as in the warp, in double, with outside taps read as 0.  With pad = 2:
+ *       bf = (fmax - fmin) / (bins - 2 pad);  tf = (f - fmin) / bf + pad;  jf = clip(floor(tf), pad, bins - pad - 1);  bm, tm, jm likewise from m;
+ *       for d = -1, 0, 1, 2:  w = B3((jm + d) - tm);  hist[jf][jm + d] += rint(w 2^32)       (64-bit integers)
+ *       B3(u), a = |u|:  a < 1: a2 = a a, a3 = a2 a, ((4 - 6 a2) + 3 a3) / 6;   a < 2: t = 2 - a, ((t t) t) / 6;   else 0.
+ *   The histogram is a sum of integers: it does not depend on the order of the samples and is exact.  Value: n = sum hist; pf[j], pm[k]
+ *   the row and column sums (integers); P = hist / n, pf / n, pm / n (each integer converted to double, then one division);
+ *       MI = sum over the bins in row-major order of P log(P / (pf pm)), an empty bin adding 0, by one accumulator.
+ *   MI = 0 and status EMD_MI_EMPTY if n = 0; MI = 0, a histogram of zeros and status EMD_MI_CONSTANT if fmax <= fmin or mmax <= mmin
+ *   (or an extremum is infinite).  8 <= bins <= 64; 1 <= P <= 64.  hist (may be NULL) receives [P][bins][bins].
+ *   Launches: two for the extrema, one for the histogram (a workgroup owns a run of samples and keeps the histogram in LDS,
+ *   bins^2 x 8 bytes, with integer LDS atomics; G = min(ceil(n / 1024), 64) workgroups per pair store their histograms as partials in
+ *   the workspace), one that sums the partials and forms the value, one workgroup per pair.
+ *
+ * Optimizer: the (1+1) evolution strategy of imregconfig('multimodal') on p, all P pairs in the same launches.  The state of a pair is
+ *   EMD_AFFINE_STATE_DOUBLES doubles: x[6] at 0, A[6][6] at 6, the normal vector n[6] that made the child at 42, the child at 48, the
+ *   parent's value f at 54, the last value at 55, and as 64-bit integers in the same array the number of evaluations done at 56, the
+ *   number accepted at 57, the status at 58 (0, EMD_AFFINE_CONVERGED, EMD_AFFINE_DEGENERATE: an image is constant, f = 0;
+ *   EMD_AFFINE_EXHAUSTED: the caller's variates have run out), sum hist of the last evaluation at 59; the rest is internal.
+ *   flags: EMD_AFFINE_RESET starts from T0 [P][6] (NULL: the identity): x = T0 - [I | 0], A = initial_radius I, the counters at
+ *   first_iteration and 0; EMD_AFFINE_NEXT_LEVEL keeps x and the counters and resets A and the status (the next level of a pyramid);
+ *   0 continues.  Then `iterations` times two launches: the histogram launch evaluates the child (T = [I | 0] + child), and a step
+ *   launch, one workgroup per pair, sums the partials, forms MI, and one thread does the rest.  The first evaluation after a reset is
+ *   the parent itself and only sets f.  Otherwise, with t the number of evaluations done before:
+ *       accept iff MI > f: then x = child, f = MI;  factor = growth on acceptance, else sqrt(sqrt(1 / growth)) (growth^(-1/4) in
+ *       correctly rounded operations);  nn = sum n_j n_j;  d_i = sum_j A_ij n_j;  c = (factor - 1) / nn;  A_ij = A_ij + (c d_i) n_j
+ *       (no update if nn = 0);  if sqrt(sum A_ij A_ij, row-major) < epsilon: status = EMD_AFFINE_CONVERGED, stop;
+ *   then the next normals: n = variates[t][p][0..5] where variates != NULL ([variates_rows][P][6]; t >= variates_rows: status =
+ *   EMD_AFFINE_EXHAUSTED), else by Box-Muller from Philox: for draw = 0, 1, 2 the words r0, r1 of philox4x32_10 with counter
+ *   (t, p, draw, 8) and key (seed lo, seed hi); u1 = (r0 + 0.5) 2^-32, u2 = (r1 + 0.5) 2^-32; rad = sqrt(-2 log u1);
+ *   n[2 draw] = rad cospi(2 u2), n[2 draw + 1] = rad sinpi(2 u2) (emd_affine_normals_f64 writes the same bits, [iterations][P][6] from
+ *   iteration first_iteration on);  child_i = x_i + sum_j A_ij n_j.  Sums run j = 0..5 from the first product.
+ *   A pair whose status is not 0 makes both launches return at once by a uniform branch: further iterations leave its state untouched.
+ *   The extrema are found again by every call (two launches), so a captured block of iterations may be replayed on other images.
+ *   The workspace is emd_mattes_mi_workspace_bytes(P, H, W, n, bins) for both the metric and the optimizer.
+ *
+ * Chain: T_pairs [N - 1][6], pair k being (fixed k, moving k + 1); M_k its 3 x 3 homogeneous form; C_middle = I;
+ *   C_j = M_{j-1} C_{j-1} above the middle, C_j = inv(M_j) C_{j+1} below; (A B)_ik = (A_i0 B_0k + A_i1 B_1k) + A_i2 B_2k; the inverse of
+ *   [a b c; d e f; 0 0 1] is, with det = a e - b d, [e/det, -b/det, (b f - c e)/det; -d/det, a/det, (c d - a f)/det; 0 0 1].  A pair
+ *   transform that is singular (det = 0) or not finite gives NaNs from there outwards on either side of the middle, so the warp writes `fill`.  C is [N][6]: the pull
+ *   map of image j onto the middle image's frame.  1 <= N <= 65.
+ * Limits: warp_stack.m:112-150 applied to every image and intersected.  With D = inv(C_j) as above, the corners (0, 0), (W - 1, 0),
+ *   (W - 1, H - 1), (0, H - 1) of image j land at  X = (D00 (x - cx) + D01 (y - cy)) + (D02 h + cx),  Y likewise; left = ceil(max(X1, X4)),
+ *   right = floor(min(X2, X3)), top = ceil(max(Y1, Y2)), bottom = floor(min(Y3, Y4)); over all images the largest left and top and
+ *   the smallest right and bottom, clamped to the image; limits = int32 (x0, y0, w, h) = (left, top, right - left + 1, bottom - top + 1),
+ *   w and h not below 0; (0, 0, 0, 0) if a C_j is singular or not finite.  The identity gives (0, 0, W, H).
+ *
+ * Deviations from the reference: the pull-map convention and the normalised parameters (above); the fixed-point histogram (ITK adds
+ *   doubles); warp_stack.m as committed does not run (its loop (mid-2):1 is empty, the right-hand images use left_trans, crop_limits
+ *   reads an undefined image), and int32(L/2)+1 is not the middle for odd L: here middle is an argument (Python: N // 2); the corner
+ *   box is the reference's heuristic, not the exact inscribed rectangle of a rotated image, and it intersects edges where the reference
+ *   compares a width with an edge; imregtform's moment-based initialisation and its pyramid smoothing are not restated. */
+#define EMD_MI_CONSTANT 1
+#define EMD_MI_EMPTY 2
+#define EMD_AFFINE_STATE_DOUBLES 64
+#define EMD_AFFINE_CONVERGED 1
+#define EMD_AFFINE_DEGENERATE 2
+#define EMD_AFFINE_EXHAUSTED 4
+#define EMD_AFFINE_RESET 1
+#define EMD_AFFINE_NEXT_LEVEL 2
+int emd_warp_affine_f32(const float* images, int N, int H, int W, const double* T, int shared_T, float fill, float* out,
+                        emd_stream_t stream);
+int emd_mi_samples_u32(int n, int H, int W, uint64_t seed, uint32_t* samples, emd_stream_t stream);
+size_t emd_mattes_mi_workspace_bytes(int P, int H, int W, int n, int bins);
+int emd_mattes_mi_f64(const float* fixed, const float* moving, int P, int H, int W, const double* T, const uint32_t* samples, int n,
+                      int bins, double* mi, int* status, uint64_t* hist, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+int emd_affine_normals_f64(int iterations, int P, int first_iteration, uint64_t seed, double* normals, emd_stream_t stream);
+int emd_affine_register_f64(const float* fixed, const float* moving, int P, int H, int W, const uint32_t* samples, int n, int bins,
+                            double initial_radius, double growth, double epsilon, uint64_t seed, const double* variates,
+                            int variates_rows, int flags, const double* T0, int first_iteration, int iterations, double* state,
+                            void* workspace, size_t workspace_bytes, emd_stream_t stream);
+int emd_affine_chain_f64(const double* T_pairs, int N, int middle, double* C, emd_stream_t stream);
+int emd_affine_limits_i32(const double* C, int N, int H, int W, int* limits, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
