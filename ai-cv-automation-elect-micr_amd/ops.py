@@ -60,6 +60,18 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def workspace(nbytes, device):
+    """The workspace of an entry point that takes a workspace pointer and no size (the statistics epilogues, the reverse reductions, the
+    loss): float64, exactly the ``nbytes`` the library's size function advertises, never rounded up (one element where it advertises
+    none).  Every wrapper here and in train_ops allocates through this one function, so a test can substitute it and hand out
+    guard-banded memory: what training runs with is what the tests run with."""
+    import torch
+
+    nbytes = int(nbytes)
+    assert nbytes >= 0 and nbytes % 8 == 0, nbytes
+    return torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+
+
 class PackedWeights:
     """bf16 hi/lo planes of one conv's weights on the device (emd_pack_weights_bf16 layout)."""
 
@@ -136,7 +148,7 @@ def conv_stats(x: Act, w: PackedWeights, ones, zeros, out: Act, stride=1, rate=1
     n = x.B * w.cout if images else w.cout
     mean = torch.empty(n, dtype=torch.float32, device=x.buf.device)
     var = torch.empty_like(mean)
-    ws = torch.empty(max(lib.emd_conv_stats_workspace_bytes(x.B * Ho * Wo, w.cout) // 8, 1), dtype=torch.float64, device=x.buf.device)
+    ws = workspace(lib.emd_conv_stats_workspace_bytes(x.B * Ho * Wo, w.cout), x.buf.device)
     # fold: a train_ops.FoldRequest -- the training-mode fold of the norm behind the conv runs in the statistics' final kernel too
     if w.taps == 1:
         args = (x.ptr, x.ld, _p(w.hi), _p(w.lo), _p(ones), _p(zeros), out.ptr, out.ld, x.B, x.H, x.W, x.C, w.cout, stride, precision,
@@ -169,7 +181,7 @@ def deconv_stats(x: Act, w_phases, ones, zeros, out: Act, images=False, precisio
     n = x.B * cout if images else cout
     mean = torch.empty(n, dtype=torch.float32, device=x.buf.device)
     var = torch.empty_like(mean)
-    ws = torch.empty(max(lib.emd_conv_stats_workspace_bytes(4 * x.B * x.H * x.W, cout) // 8, 1), dtype=torch.float64, device=x.buf.device)
+    ws = workspace(lib.emd_conv_stats_workspace_bytes(4 * x.B * x.H * x.W, cout), x.buf.device)
     args = (x.ptr, x.ld, hi, lo, _p(ones), _p(zeros), out.ptr, out.ld, x.B, x.H, x.W, x.C, cout, precision, 1 if images else 0, _p(mean), _p(var),
             _p(ws))
     if fold is not None:
@@ -528,8 +540,7 @@ def conv1x1_split32(x: SplitAct, w: PackedWeights, scale1, shift1, out: Act, act
         M = x.B * x.H * x.W
         mean = torch.empty(w.cout, dtype=torch.float32, device=x.buf.device)
         var = torch.empty_like(mean)
-        ws = torch.empty(lib.emd_conv1x1_split32_stats_workspace_bytes(C.c_long(M), w.cout) // 8, dtype=torch.float64,
-                         device=x.buf.device)
+        ws = workspace(lib.emd_conv1x1_split32_stats_workspace_bytes(C.c_long(M), w.cout), x.buf.device)
         if fold is not None:
             scale, shift = torch.empty_like(mean), torch.empty_like(mean)
             rc = lib.emd_conv1x1_split32_stats_fold_f32(x.ptr, x.ld, _p(w.hi), _p(w.lo), _p(scale1), _p(shift1), out.ptr, out.ld,
@@ -631,7 +642,7 @@ def bn_batch_stats(x: Act, stream=None):
     npix = x.B * x.H * x.W
     mean = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
     var = torch.empty_like(mean)
-    ws = torch.empty(lib.emd_bn_stats_workspace_bytes(npix, x.C) // 8, dtype=torch.float64, device=x.buf.device)
+    ws = workspace(lib.emd_bn_stats_workspace_bytes(npix, x.C), x.buf.device)
     _lib.check(lib.emd_bn_stats_f32(x.ptr, x.ld, C.c_long(npix), x.C, _p(mean), _p(var), _p(ws),
                                     _lib.stream_ptr(stream)), "emd_bn_stats_f32")
     return mean, var
@@ -645,7 +656,7 @@ def bn_batch_stats_images(x: Act, stream=None):
     npix = x.H * x.W
     mean = torch.empty(x.B * x.C, dtype=torch.float32, device=x.buf.device)
     var = torch.empty_like(mean)
-    ws = torch.empty(x.B * (lib.emd_bn_stats_workspace_bytes(npix, x.C) // 8), dtype=torch.float64, device=x.buf.device)
+    ws = workspace(x.B * lib.emd_bn_stats_workspace_bytes(npix, x.C), x.buf.device)
     _lib.check(lib.emd_bn_stats_images_f32(x.ptr, x.ld, x.B, C.c_long(npix), x.C, _p(mean), _p(var), _p(ws),
                                            _lib.stream_ptr(stream)), "emd_bn_stats_images_f32")
     return mean, var
@@ -734,7 +745,7 @@ def instnorm_tanh(x_img, out_img, eps=1e-3, stream=None):
     mean = torch.empty(B, dtype=torch.float32, device=x_img.device)
     var = torch.empty_like(mean)
     # the statistics of all B images in one pair of launches (each image reduced exactly as it would be alone)
-    ws = torch.empty(B * max(lib.emd_bn_stats_workspace_bytes(npix, 1) // 8, 1), dtype=torch.float64, device=x_img.device)
+    ws = workspace(B * lib.emd_bn_stats_workspace_bytes(npix, 1), x_img.device)
     _lib.check(lib.emd_bn_stats_images_f32(_p(x_img), 1, B, C.c_long(npix), 1, _p(mean), _p(var), _p(ws),
                                            _lib.stream_ptr(stream)), "emd_bn_stats_images_f32")
     _lib.check(lib.emd_instnorm_tanh_f32(_p(x_img), _p(mean), _p(var), _p(out_img), B, C.c_long(npix), C.c_float(eps),

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from . import _lib
+from . import _lib, ops as _ops
 from .ops import PREC_BF16X3, Act, _act, _p
 
 MASK_NONE, MASK_RELU6, MASK_RELU6_CLIP, MASK_LEAKY, MASK_RELU = 0, 1, 2, 3, 4
@@ -106,9 +106,7 @@ def conv1x1_s2_bwd_data(dy: Act, w: DevPackedWeights, ones, zeros, dx: Act, accu
 
 
 def _reduce_ws(npix, Cc, device):
-    import torch
-
-    return torch.empty(max(_lib.load().emd_chan_reduce_workspace_bytes(npix, Cc) // 8, 1), dtype=torch.float64, device=device)
+    return _ops.workspace(_lib.load().emd_chan_reduce_workspace_bytes(npix, Cc), device)
 
 
 def bn_train_fold(mean, var, gamma2, beta2, npix, gamma1=None, beta1=None, bias=None, moving=None, eps=BN_EPS,
@@ -257,7 +255,7 @@ def bn_backward(dy: Act, r: Act, fold, gamma2, dgamma2, dbeta2, dr: Act, mask=MA
     s1, t = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
     ms, mh = (fold["scale"], fold["shift"]) if mask else (None, None)
     K, m1, m2 = torch.empty_like(s1), torch.empty_like(s1), torch.empty_like(s1)
-    ws = torch.empty(max((images or 1) * (lib.emd_chan_reduce_workspace_bytes(npix, Cc) // 8), 1), dtype=torch.float64, device=dev)
+    ws = _ops.workspace((images or 1) * lib.emd_chan_reduce_workspace_bytes(npix, Cc), dev)
     if isinstance(dy, Cout1Grad):
         prep = _prep_struct(fold, gamma1, gamma2, eps, K, m1, m2, dgamma1, dgamma2, dbeta2)
         _lib.check(lib.emd_bn_bwd_reduce_prep_cout1_f32(_p(dy.g1), _p(dy.w9), dy.B, dy.H, dy.W, r.ptr, r.ld, _p(fold["mean"]), _p(fold["rstd1"]),
@@ -342,7 +340,7 @@ def bn_backward_dw(dy: DwGrad, r: Act, fold, gamma2, dgamma2, dbeta2, dr: Act, m
     npix = dy.H * dy.W if images else dy.B * dy.H * dy.W
     s1, t = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
     ms, mh = (fold["scale"], fold["shift"]) if mask else (None, None)
-    ws = torch.empty(max(lib.emd_dw3x3_bn_bwd_workspace_bytes(dy.B, dy.H, dy.W, Cc) // 8, 1), dtype=torch.float64, device=dev)
+    ws = _ops.workspace(lib.emd_dw3x3_bn_bwd_workspace_bytes(dy.B, dy.H, dy.W, Cc), dev)
     K, m1, m2 = torch.empty_like(s1), torch.empty_like(s1), torch.empty_like(s1)
     prep = _prep_struct(fold, gamma1, gamma2, eps, K, m1, m2, dgamma1, dgamma2, dbeta2) if FUSE_PREP else None
     _lib.check(lib.emd_dw3x3_bn_bwd_reduce_f32(dd.ptr, dd.ld, _p(dy.w), r.ptr, r.ld, _p(fold["mean"]), _p(fold["rstd1"]), _p(ms), _p(mh), mask,
@@ -440,7 +438,7 @@ def denoise_loss(out, truth, dout=None, grad_scale=1.0, stream=None):
     lib = _lib.load()
     assert out.is_contiguous() and truth.is_contiguous() and out.numel() == truth.numel()
     res = torch.empty(3, dtype=torch.float32, device=out.device)
-    ws = torch.empty(lib.emd_denoise_loss_workspace_bytes() // 8, dtype=torch.float64, device=out.device)
+    ws = _ops.workspace(lib.emd_denoise_loss_workspace_bytes(), out.device)
     _lib.check(lib.emd_denoise_loss_f32(_p(out), _p(truth), C.c_long(out.numel()), C.c_float(grad_scale), _p(res), _p(dout),
                                         _p(ws), _lib.stream_ptr(stream)), "emd_denoise_loss_f32")
     return res
@@ -486,7 +484,7 @@ def sumsq(x, scale=1.0, stream=None):
 
     lib = _lib.load()
     out = torch.empty(1, dtype=torch.float32, device=x.device)
-    ws = torch.empty(lib.emd_sumsq_workspace_bytes() // 8, dtype=torch.float64, device=x.device)
+    ws = _ops.workspace(lib.emd_sumsq_workspace_bytes(), x.device)
     _lib.check(lib.emd_sumsq_f32(_p(x), C.c_long(x.numel()), C.c_float(scale), _p(out), _p(ws), _lib.stream_ptr(stream)),
                "emd_sumsq_f32")
     return out

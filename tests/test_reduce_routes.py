@@ -104,3 +104,39 @@ def test_every_instance_is_launched():
     for cl in (16, 4, 1):
         assert {("prep", cl, 1), ("prep", cl, 2), ("plain", cl, 1), ("plain", cl, 2)} <= got, (cl, sorted(got))
     assert {("accumulate", 16, 1), ("accumulate", 4, 1)} <= got     # (the accumulating entry takes at most 512 slabs: no CL = 1)
+
+
+SWEEP = sorted(set(range(1, 41)) | {63, 64, 65, 127, 128, 129})
+
+
+def test_size_functions_hold_every_partial_over_a_sweep_of_shapes():
+    """The three size functions whose callers pass a workspace pointer and no size, against the producers' partial counts, for B in 1..4
+    and H, W in 1..40 and around 64 and 128, stride 1 / 2 and rate 1 / 2 where the producer takes them (the listed cases above are 52
+    points of this grid).  The transposed conv's four phases write 4 * ceil(m / 128) rows against the ceil(4 * m / 128) its M suggests:
+    at most three more, which emd_conv_stats_workspace_bytes adds -- held here for every m of the grid, not only on paper."""
+    lib = _lib.load()
+    row = 2 * R.CO * 8
+    n = 0
+    for B in range(1, 5):
+        for H in SWEEP:
+            for W in SWEEP:
+                for stride in (1, 2):       # conv_stats (1x1 at either stride; the dense 3x3 is the stride-1 count at any rate)
+                    Ho, Wo = R.cdiv(H, stride), R.cdiv(W, stride)
+                    have = lib.emd_conv_stats_workspace_bytes(B * Ho * Wo, R.CO)
+                    assert have >= R.nslab_conv(B, H, W, stride, False) * row, (B, H, W, stride)
+                    if (Ho * Wo) % 128 == 0:
+                        assert have >= B * R.nslab_conv(B, H, W, stride, True) * row, (B, H, W, stride)
+                m = B * H * W                # deconv_stats (H, W: the input grid)
+                have = lib.emd_conv_stats_workspace_bytes(4 * m, R.CO)
+                need = R.nslab_deconv(B, H, W, False)
+                assert 0 <= need - R.cdiv(4 * m, 128) <= 3 and need * row <= have <= (need + 3) * row, (B, H, W)
+                if (H * W) % 128 == 0:
+                    assert have >= B * R.nslab_deconv(B, H, W, True) * row, (B, H, W)
+                assert lib.emd_conv1x1_split32_stats_workspace_bytes(m, R.CO) == R.nslab_split32(B, H, W) * row, (B, H, W)
+                have = lib.emd_dw3x3_bn_bwd_workspace_bytes(B, H, W, R.CO)
+                for stride, rate in ((1, 1), (2, 1), (1, 2)):     # bn_backward_dw: rolling, strided gather, dilated gather
+                    for images in (False, True):
+                        rows = R.nslab_dw(B, H, W, stride, rate, images) * (B if images else 1)
+                        assert have >= rows * row, (B, H, W, stride, rate, images)
+                n += 1
+    assert n == 4 * 46 * 46

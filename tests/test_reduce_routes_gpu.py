@@ -231,12 +231,12 @@ def _p(t):
 
 def dw_reduce(dd, wf, r, fold, mask, images, c, gdw=None):
     """emd_dw3x3_bn_bwd_reduce_f32 alone, no per-channel step: the plain chan_reduce_final -> (s1, s2)."""
-    from emdenoise import _lib
+    from emdenoise import _lib, ops
 
     lib = _lib.load()
     n = (c.B if images else 1) * c.C
     s1, s2 = torch.empty(n, device=dev()), torch.empty(n, device=dev())
-    ws = torch.empty(max(lib.emd_dw3x3_bn_bwd_workspace_bytes(c.B, c.H, c.W, c.C) // 8, 1), dtype=torch.float64, device=dev())
+    ws = ops.workspace(lib.emd_dw3x3_bn_bwd_workspace_bytes(c.B, c.H, c.W, c.C), dev())
     ms, mh = (fold["scale"], fold["shift"]) if mask else (None, None)
     _lib.check(lib.emd_dw3x3_bn_bwd_reduce_f32(dd.ptr, dd.ld, _p(wf), r.ptr, r.ld, _p(fold["mean"]), _p(fold["rstd1"]), _p(ms), _p(mh), mask,
                                                1 if images else 0, c.B, c.H, c.W, c.C, c.stride, c.rate, _p(s1), _p(s2), _p(gdw), _p(ws), None,
@@ -246,7 +246,7 @@ def dw_reduce(dd, wf, r, fold, mask, images, c, gdw=None):
 
 def slab_reduce(dy, r, fold, images, c):
     """emd_bn_bwd_reduce[_images]_f32 alone, mask 0 -> (s1, s2)."""
-    from emdenoise import _lib, train_ops as TO
+    from emdenoise import _lib, ops, train_ops as TO
 
     lib = _lib.load()
     n = (c.B if images else 1) * c.C
@@ -255,7 +255,7 @@ def slab_reduce(dy, r, fold, images, c):
         TO.chan_reduce(dy, s1, r, fold["mean"], fold["rstd1"], s2)
         return s1, s2
     npix = c.H * c.W
-    ws = torch.empty(max(c.B * (lib.emd_chan_reduce_workspace_bytes(npix, c.C) // 8), 1), dtype=torch.float64, device=dev())
+    ws = ops.workspace(c.B * lib.emd_chan_reduce_workspace_bytes(npix, c.C), dev())
     _lib.check(lib.emd_bn_bwd_reduce_images_f32(dy.ptr, dy.ld, r.ptr, r.ld, _p(fold["mean"]), _p(fold["rstd1"]), None, None, 0, c.B,
                                                 C.c_long(npix), c.C, _p(s1), _p(s2), _p(ws), _lib.stream_ptr(None)),
                "emd_bn_bwd_reduce_images_f32")
@@ -414,7 +414,7 @@ def test_cout1_backward_route(c):
     dg1 = torch.zeros(Cc, device=dev()) if c.double_bn else None
     prep = TO._prep_struct(fold, gamma1, gamma2, TO.BN_EPS, K, m1, m2, dg1, dg2, db2)
     npix = H * W if images else B * H * W
-    ws = torch.empty(max(nl * (lib.emd_chan_reduce_workspace_bytes(npix, Cc) // 8), 1), dtype=torch.float64, device=dev())
+    ws = ops.workspace(nl * lib.emd_chan_reduce_workspace_bytes(npix, Cc), dev())
     r = ops.Act(r0)
     _lib.check(lib.emd_bn_bwd_reduce_prep_cout1_f32(_p(g1), _p(w9), B, H, W, r.ptr, r.ld, _p(fold["mean"]), _p(fold["rstd1"]), None, None, 0,
                                                     1 if images else 0, Cc, _p(s1), _p(s2), _p(ws), C.byref(prep), _lib.stream_ptr(None)),
