@@ -503,6 +503,18 @@ SIGNATURES = {
     "emd_affine_chain_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # C N H W limits stream
     "emd_affine_limits_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # ---- exit wave and aberrations by gradient descent (csrc/psiart.hip)
+    # S n params ramp wavelength sampling offset_scale C stream
+    "emd_psiart_ctf_f64": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "emd_psiart_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    # images N S amp phase params ramp weights wavelength sampling offset_scale flags losses pred g_amp g_phase g_params workspace
+    # ws_bytes stream
+    "emd_psiart_loss_grad_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_int] +
+                                 [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    # images N S amp phase params ramp weights wavelength sampling offset_scale flags m_amp v_amp m_phase v_phase m_params v_params
+    # step rates beta1 beta2 epsilon losses pred g_amp g_phase g_params workspace ws_bytes stream
+    "emd_psiart_step_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_int] +
+                            [C.c_void_p] * 8 + [C.c_double] * 3 + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

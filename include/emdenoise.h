@@ -1402,6 +1402,58 @@ int emd_affine_chain_f64(const double* T_pairs, int N, int middle, double* C, em
 int emd_affine_limits_i32(const double* C, int N, int H, int W, int* limits, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exit wave and aberrations by gradient descent (csrc/psiart.hip): machine_learning/psi-art.py:97-130, :170-223,
+ * :293-313, :334-348.  The reference does not run as committed; the formulas below are the specification.  Everything is double
+ * precision; complex arrays are interleaved (re, im) doubles.  S a power of two, 8 <= S <= 2048 (4096 is refused: the column kernels
+ * would spill registers); 1 <= N <= 64.  Every pointer but the workspace's size is a DEVICE pointer.
+ *
+ * Grid (spatial_frequencies): f[i] = (i < S/2 ? i : i - S) * (1.0 / (S * sampling)), as numpy.fft.fftfreq; kx[i][j] = f[i] (the row
+ *     index), ky[i][j] = f[j];   theta = lam sqrt(kx kx + ky ky);   phi = atan2(ky, kx) (0 at the origin).
+ * Parameters: EMD_PSIART_NPARAM = 27 doubles.  0..24, in the reference's all_symbols order: a22 phi22 a20 a33 phi33 a31 phi31 a44 phi44
+ *     a42 phi42 a40 a55 phi55 a53 phi53 a51 phi51 a66 phi66 a64 phi64 a62 phi62 a60;  25: focal_spread D;  26: the raw defocus offset u.
+ * CTF of image k (get_chi, get_temporal_envelope):  off = scale tanh(u / scale);   a20_k = a20 ramp_k + off;
+ *     chi_k = (2 pi / lam) sum_n (1 / n) theta^n sum_m a_nm cos(m (phi - phi_nm)), the terms of get_chi (m = 0: no angle), a20 replaced
+ *     by a20_k;   T = exp(-sign(D) (0.5 pi / lam D theta^2)^2);   C_k = exp(-i chi_k) T.  chi is reduced as t = chi / pi, formed
+ *     without pi:  t_k = (2 / lam) sum' + a20_k theta^2 / lam  (sum': every term but a20's),  C_k = (cospi(t_k) - i sinpi(t_k)) T.
+ * Forward:  psi = A (cos P + i sin P), A and P [S][S];   psi^ = fft2(psi);   b_k = ifft2(C_k psi^);   m_k = |b_k|.
+ *     Targets r_k = sqrt(max(image_k, 0)) of the float32 images [N][S][S] (EMD_PSIART_AMPLITUDES: |image_k|).
+ *     c_k = mean(r_k) / mean(m_k) with EMD_PSIART_NORMALISE, else 1;   p_k = c_k m_k;   loss_k = mean((p_k - r_k)^2), two-pass, fixed
+ *     order;   L = sum_k w_k loss_k in ascending k.  losses [N + 1]: the N per image, then L.  pred (may be NULL) [N][S][S] = p_k.
+ *     An all-zero wave with NORMALISE has mean(m_k) = 0: c_k is then inf or NaN and loss_k, L and pred are NaN, while every
+ *     gradient is exactly 0 (G_b below is 0 everywhere), so nothing non-finite reaches A, P or the scalars.  It is not refused.
+ * Reverse, n = S^2, d = p_k - r_k, M = mean(m_k):   g_m = w_k (2 c_k / n) (d - sum(d m_k) / (n M))  (the second term only with
+ *     NORMALISE);   G_b = g_m b_k / |b_k|, 0 where |b_k| = 0;   F_k = fft2(G_b);   G_psi = sum_k ifft2(conj(C_k) F_k);
+ *     dL/dA = cos P Re G_psi + sin P Im G_psi;   dL/dP = A (-sin P Re G_psi + cos P Im G_psi).
+ *     With z_k = conj(F_k / n) C_k psi^, summed over the frequencies q and the images k:
+ *     dL/da_nm = sum Im z_k (2 pi / lam) (1 / n) theta^n cos(m (phi - phi_nm));   dL/dphi_nm = sum Im z_k (2 pi / lam) (1 / n) theta^n
+ *     a_nm m sin(m (phi - phi_nm));   dL/da20 = sum ramp_k Im z_k (pi / lam) theta^2;   dL/du = sech^2(u / scale) sum Im z_k (pi / lam)
+ *     theta^2;   dL/dD = sum Re z_k (-2 |D| (0.5 pi theta^2 / lam)^2).   g_amp, g_phase [S][S], g_params [27] may be NULL; with none of
+ *     them (and no step) the reverse launches are not made.
+ * Step: tf.train.AdamOptimizer's form, t = step[0] + 1:  lr_t = rate sqrt(1 - beta2^t) / (1 - beta1^t);  m = beta1 m + (1 - beta1) g;
+ *     v = beta2 v + (1 - beta2) g g;  x -= lr_t m / (sqrt(v) + epsilon);  step[0] = t.  rates [29]: A, P, then the 27 scalars; a rate
+ *     of 0 leaves the parameter and its moments bitwise unchanged (a field with rate 0 is not written at all).
+ * Deviations from the reference: the normalisation uses mean|b_k| against the mean of the root image (the reference: a complex mean
+ *     against the mean of the intensity); the loss is on |b_k|; ramp (3 |k - middle| there) and the weights (its bootstrapping window)
+ *     are arguments.  Not here: the spatial-coherence and aperture envelopes, the per-image affine transforms, padding.
+ * No floating-point atomics, fixed summation orders: bitwise reproducible.  The workspace is the caller's and 16-byte aligned, arrays
+ * of doubles 8-byte, the images and the step counter 4-byte; outputs and the workspace overlap nothing.  Launches only: capturable. */
+#define EMD_PSIART_NPARAM 27
+#define EMD_PSIART_NORMALISE 1  /* bits of `flags` */
+#define EMD_PSIART_AMPLITUDES 2
+int emd_psiart_ctf_f64(int S, int n, const double* params, const double* ramp, double wavelength, double sampling, double offset_scale,
+                       double* C, emd_stream_t stream);
+size_t emd_psiart_workspace_bytes(int N, int S);
+int emd_psiart_loss_grad_f64(const float* images, int N, int S, const double* amp, const double* phase, const double* params,
+                             const double* ramp, const double* weights, double wavelength, double sampling, double offset_scale, int flags,
+                             double* losses, double* pred, double* g_amp, double* g_phase, double* g_params, void* workspace,
+                             size_t workspace_bytes, emd_stream_t stream);
+int emd_psiart_step_f64(const float* images, int N, int S, double* amp, double* phase, double* params, const double* ramp,
+                        const double* weights, double wavelength, double sampling, double offset_scale, int flags, double* m_amp,
+                        double* v_amp, double* m_phase, double* v_phase, double* m_params, double* v_params, int* step, const double* rates,
+                        double beta1, double beta2, double epsilon, double* losses, double* pred, double* g_amp, double* g_phase,
+                        double* g_params, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
