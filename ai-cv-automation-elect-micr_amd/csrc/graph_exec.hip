@@ -468,7 +468,15 @@ struct Run {
         // encoder 0 (:252-264): cnn0 = relu6(d * a + t) is an outer product of the 1-channel depthwise result d -- cnn0_last's patch
         // loader rebuilds it (emd_sep3x3_fused_gen_f32) where the fused kernel covers the shape
         T4 cnn0_last;
-        if (emd_sep3x3_fused_supported(S, S, F0, F0, 1, 1)) {
+        if (emd_sep3x3_fused_gen9_supported(S, S, F0, F0)) {
+            // d is formed inside the kernel as well (emd_sep3x3_fused_gen9_f32): the image is the layer's only input
+            cnn0_last = E(B, S, S, F0);
+            if (live()) {
+                const LayerParams &pc = P["cnn0"], &pl = P["cnn0_last"];
+                call(emd_sep3x3_fused_gen9_f32(xin, pc.w9, pc.a, pc.shift, EMD_ACT_RELU6, pl.dw, pl.pw.hi, pl.pw.lo, pl.scale, pl.shift, nullptr,
+                                               nullptr, nullptr, 0, cnn0_last.ptr(), cnn0_last.ld, B, S, S, F0, F0, EMD_ACT_RELU6, EMD_PREC_BF16X3, 0, st));
+            }
+        } else if (emd_sep3x3_fused_supported(S, S, F0, F0, 1, 1)) {
             T4 d4 = E(B, S, S, 4);
             cnn0_last = E(B, S, S, F0);
             if (live()) {

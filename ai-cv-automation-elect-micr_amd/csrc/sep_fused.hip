@@ -20,6 +20,7 @@
 // Epilogue identical to gemm_conv.hip (fp32 LDS staging, 16-byte stores / residual loads).  A workgroup walks up to 8
 // tiles side by side with the staging pipeline running on across them; DESIGN.md 3.3 has the measurements.
 #include <cstdlib>
+#include <type_traits>
 
 #include "sep_params.hpp"
 
@@ -441,6 +442,272 @@ __global__ __launch_bounds__(256, 2) void sep_fused_kernel(const SepParams p) {
 #undef SEP_STAMP
 }
 
+// The generated-input layer with nothing staged but one scalar per pixel (emd_sep3x3_fused_gen9_f32; relu6 generation, zero padding,
+// BN = 64, resident W tiles, split-bf16; NCH = Cin / 32 chunks).  The Cin-channel input act(d * a[c] + t[c]) is a function of d alone,
+// so LDS holds the tile's (8+2) x (16+2) d values (row pitch 20 floats: a thread's six columns are one 16-byte and one 8-byte read) and
+// the depthwise thread generates its 3 x 6 input vectors in registers, with the chunk's nine weight vectors and (a, t) resident in
+// registers as well.  d itself is formed here from the 1-channel image p.x with the taps p.gen_w9 (cin1_kernel's statement): thread
+// idx < 180 owns d pixel idx of the tile, requests its nine image values (clamped indices, unconditional) a whole tile ahead and writes
+// d into the other half of a double-buffered tile before barrier (3), so a tile needs no barrier for d.  Per tile: both chunks'
+// depthwise stages -> their own A planes, barrier (2), all MFMAs (chunk, k-step and pass order of sep_fused_kernel), barrier (3),
+// epilogue through the staging tile (which shares the A planes' storage) as there.
+template <int NCH, bool RES>
+__global__ __launch_bounds__(256, 2) void sep_gen9_kernel(const SepParams p) {
+    constexpr int TH = 8, TW = 16, BM = TH * TW, BN = 64, BK = 32, LDK = BK + 8;
+    constexpr int DH = TH + 2, DW = TW + 2, DLD = 20, ND = DH * DW;
+    constexpr int LDS_STAGE = BN + 4;
+    constexpr int B_CHUNK = 2 * BN * LDK * 2, A_CHUNK = 2 * BM * LDK * 2;
+    constexpr int D_BYTES = DH * DLD * 4, STAGE_BYTES = BM * LDS_STAGE * 4;
+    constexpr int D_OFF = NCH * B_CHUNK, A_OFF = D_OFF + 2 * D_BYTES;
+    constexpr int TILE_BYTES = A_OFF + (NCH * A_CHUNK > STAGE_BYTES ? NCH * A_CHUNK : STAGE_BYTES);
+    static_assert(A_OFF % 16 == 0 && (DLD * 4) % 16 == 0, "16-byte reads of the d tile and the A planes");
+
+    __shared__ __attribute__((aligned(16))) unsigned char smem[TILE_BYTES];
+    float* dt = reinterpret_cast<float*>(smem + D_OFF);
+    float(*stage)[LDS_STAGE] = reinterpret_cast<float(*)[LDS_STAGE]>(smem + A_OFF);
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = tid >> 6;
+    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    xcd_remap(p.xcd, bx, by, bz);
+    const int xbase = bx * p.tpw * TW, y0 = by * TH;
+    const long img = (long)bz * p.H * p.W;
+
+    // ---- W tiles, once
+    {
+        const int w_col = (tid & 3) * 8, w_row = tid >> 2;
+        const uint16_t* __restrict__ whi = p.Whi + (long)w_row * p.Cpad + w_col;
+        const uint16_t* __restrict__ wlo = p.Wlo + (long)w_row * p.Cpad + w_col;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            auto Bc = reinterpret_cast<uint16_t(*)[BN][LDK]>(smem + c * B_CHUNK);
+            *reinterpret_cast<u32x4*>(&Bc[0][w_row][w_col]) = *reinterpret_cast<const u32x4*>(whi + c * BK);
+            *reinterpret_cast<u32x4*>(&Bc[1][w_row][w_col]) = *reinterpret_cast<const u32x4*>(wlo + c * BK);
+        }
+    }
+    // ---- depthwise role: 4 consecutive pixels of tile row ty, 4 channels of every chunk
+    const int c4 = tid & 7, pg = tid >> 3;
+    const int ty = pg >> 2, tx0 = (pg & 3) * 4;
+    f32x4 wk[NCH][9], ga[NCH], gt[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[c][k] = *reinterpret_cast<const f32x4*>(p.dw + (long)k * p.Cin + c * BK + c4 * 4);
+        ga[c] = *reinterpret_cast<const f32x4*>(p.gen_a + c * BK + c4 * 4);
+        gt[c] = *reinterpret_cast<const f32x4*>(p.gen_t + c * BK + c4 * 4);
+    }
+    // ---- d role: d pixel (dpy, dpx) of the tile = image pixel (y0 - 1 + dpy, x0 - 1 + dpx); the threads past the tile compute its last
+    // pixel again and do not write it
+    const int di = tid < ND ? tid : ND - 1;
+    const int dpy = di / DW, dpx = di - dpy * DW;
+    bool rok[3];
+    const float* irow[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int ry = y0 - 2 + dpy + i;
+        rok[i] = ry >= 0 && ry < p.H;
+        irow[i] = p.x + img + (long)(ry < 0 ? 0 : (ry >= p.H ? p.H - 1 : ry)) * p.W;
+    }
+    float w9[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) w9[k] = p.gen_w9[k];
+    float iv[9];
+    auto load_img = [&](int xt) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int rx = xt - 2 + dpx + j;
+            const int cx = rx < 0 ? 0 : (rx >= p.W ? p.W - 1 : rx);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) iv[i * 3 + j] = irow[i][cx];
+        }
+    };
+    auto form_d = [&](int xt, int buf) {   // cin1_kernel: taps in i, j order, the ones off the image skipped
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const int rx = xt - 2 + dpx + j;
+                d = (rok[i] && rx >= 0 && rx < p.W) ? fmaf(w9[i * 3 + j], iv[i * 3 + j], d) : d;
+            }
+        if (tid < ND) dt[buf * (DH * DLD) + dpy * DLD + dpx] = d;
+    };
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+    const int fr = lane & 31, fh = lane >> 5;
+    constexpr int E_C4 = BN / 4, E_RPP = 256 / E_C4, E_NROWS = BM / E_RPP;
+    const int ncol = (tid % E_C4) * 4, er = tid / E_C4;
+
+    load_img(xbase);
+    form_d(xbase, 0);
+    // the resident vectors are pinned as arrived here: with a load of the prologue still pending at the loop's head the compiler puts a
+    // wait for EVERY outstanding memory operation there, which each later tile spends waiting for the stores of the tile before
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) asm volatile("" : "+v"(wk[c][k]));
+        asm volatile("" : "+v"(ga[c]), "+v"(gt[c]));
+    }
+    __syncthreads();   // W tiles and the first d tile visible
+
+    for (int t = 0; t < p.tpw; ++t) {
+        const int x0 = xbase + t * TW;
+        // the thread's 3 x 6 d values
+        float dv[3][6];
+        {
+            const float* dsrc = dt + (t & 1) * (DH * DLD) + ty * DLD + tx0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const f32x4 q = *reinterpret_cast<const f32x4*>(dsrc + i * DLD);
+                const f32x2 r = *reinterpret_cast<const f32x2*>(dsrc + i * DLD + 4);
+                dv[i][0] = q[0]; dv[i][1] = q[1]; dv[i][2] = q[2]; dv[i][3] = q[3]; dv[i][4] = r[0]; dv[i][5] = r[1];
+            }
+        }
+        const bool more = t + 1 < p.tpw;   // workgroup-uniform
+        if (more) load_img(x0 + TW);
+        // generate + depthwise 3x3 -> bf16 hi/lo A planes, both chunks.  BORDER: the tile touches the image's edge; a padding pixel
+        // of the generated input is 0, not relu6(t[c])
+        auto stage1 = [&](auto border) {
+            constexpr bool BORDER = decltype(border)::value;
+            // of a thread's 3 x 6 pixels only whole rows and the first / last column can lie off the image
+            bool rowok[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) rowok[i] = y0 - 1 + ty + i >= 0 && y0 - 1 + ty + i < p.H;
+            const bool c0ok = x0 - 1 + tx0 >= 0, c5ok = x0 + tx0 + 4 < p.W;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                f32x4 o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    f32x4 pr[6];
+#pragma unroll
+                    for (int d = 0; d < 6; ++d) {
+                        const float dd = dv[i][d];
+                        const f32x4 u = __builtin_elementwise_fma(f32x4{dd, dd, dd, dd}, ga[c], gt[c]);   // fmaf per channel, two to an instruction
+#pragma unroll
+                        for (int ch = 0; ch < 4; ++ch) pr[d][ch] = __builtin_amdgcn_fmed3f(u[ch], 0.f, 6.f);
+                        if (BORDER) {
+                            const bool ok = rowok[i] && (d == 0 ? c0ok : (d == 5 ? c5ok : true));
+                            if (!ok) pr[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) o[j] += wk[c][i * 3 + d] * pr[j + d];
+                }
+                auto Ac = reinterpret_cast<uint16_t(*)[BM][LDK]>(smem + A_OFF + c * A_CHUNK);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int r = ty * TW + tx0 + j;
+                    unsigned h0, l0, h1, l1;
+                    split2(o[j][0], o[j][1], h0, l0);
+                    split2(o[j][2], o[j][3], h1, l1);
+                    *reinterpret_cast<u32x2*>(&Ac[0][r][c4 * 4]) = u32x2{h0, h1};
+                    *reinterpret_cast<u32x2*>(&Ac[1][r][c4 * 4]) = u32x2{l0, l1};
+                }
+            }
+        };
+        if (y0 == 0 || y0 + TH == p.H || x0 == 0 || x0 + TW == p.W) stage1(std::true_type{});
+        else stage1(std::false_type{});
+        // The epilogue's operands are requested here: they land under the MFMA phase and are not live in the stage above.  The loads are
+        // unconditional (threads past the last channel quad read quad 0): a load that may still be pending on some path at the loop's head
+        // costs a wait for ALL outstanding memory operations there, the stores of the tile before included.
+        const int ncl = ncol < p.N ? ncol : 0;
+        f32x4 rve[RES ? E_NROWS : 1];
+        if constexpr (RES) {
+            const float* __restrict__ rt = p.res + (img + (long)y0 * p.W) * p.ldres + ncl;
+#pragma unroll
+            for (int k = 0; k < E_NROWS; ++k) {
+                const int r = er + k * E_RPP;
+                rve[k] = *reinterpret_cast<const f32x4*>(rt + ((r >> 4) * p.W + (r & 15) + x0) * p.ldres);
+            }
+        }
+        // (the affine vectors are re-read per tile: as loop-invariant registers they would not fit beside the weights)
+        const bool two = p.scale2 != nullptr;
+        f32x4 s1 = *reinterpret_cast<const f32x4*>(p.scale1 + ncl);
+        f32x4 t1 = *reinterpret_cast<const f32x4*>(p.shift1 + ncl);
+        f32x4 s2 = *reinterpret_cast<const f32x4*>((two ? p.scale2 : p.scale1) + ncl);
+        f32x4 t2 = *reinterpret_cast<const f32x4*>((two ? p.shift2 : p.shift1) + ncl);
+        __syncthreads();  // (2) A planes visible
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            auto Ac = reinterpret_cast<const uint16_t(*)[BM][LDK]>(smem + A_OFF + c * A_CHUNK);
+            auto Bc = reinterpret_cast<const uint16_t(*)[BN][LDK]>(smem + c * B_CHUNK);
+#pragma unroll
+            for (int ks = 0; ks < BK / 16; ++ks) {
+                const int r = wv * 32 + fr;
+                const bf16x8 ah = *reinterpret_cast<const bf16x8*>(&Ac[0][r][ks * 16 + fh * 8]);
+                const bf16x8 al = *reinterpret_cast<const bf16x8*>(&Ac[1][r][ks * 16 + fh * 8]);
+                bf16x8 bh[2], bl[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    bh[j] = *reinterpret_cast<const bf16x8*>(&Bc[0][j * 32 + fr][ks * 16 + fh * 8]);
+                    bl[j] = *reinterpret_cast<const bf16x8*>(&Bc[1][j * 32 + fr][ks * 16 + fh * 8]);
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[j], acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[j], acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[j], acc[j], 0, 0, 0);
+                }
+            }
+        }
+        if (more) form_d(x0 + TW, (t + 1) & 1);   // (that half was last read a tile ago)
+        __syncthreads();  // (3) fragment reads done: the staging tile overwrites the A planes
+
+        // ---- epilogue (sep_fused_kernel's, 64 columns, fp32 output)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r = wv * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
+                stage[r][j * 32 + fr] = acc[j][e];
+                acc[j][e] = 0.f;
+            }
+        __syncthreads();
+        // (the operands requested before barrier (2) are taken as arrived HERE, on every path, before the stores are issued)
+        asm volatile("" : "+v"(s1), "+v"(t1), "+v"(s2), "+v"(t2));
+        if constexpr (RES) {
+#pragma unroll
+            for (int k = 0; k < E_NROWS; ++k) asm volatile("" : "+v"(rve[k]));
+        }
+        if (ncol < p.N) {
+            const float hi = p.act == 1 ? 6.f : __builtin_inff();
+            const float hi2 = p.act == 2 ? __builtin_inff() : 6.f;
+            const float slope = p.act == 4 ? 0.2f : 1.f, lo = (p.act == 1 || p.act == 2) ? 0.f : -__builtin_inff();
+            auto finish = [&](f32x4 v) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    float u = fmaf(v[c], s1[c], t1[c]);
+                    u = fminf(fmaxf(fmaxf(u, lo), slope * u), hi);
+                    if (two) u = fminf(fmaxf(fmaf(u, s2[c], t2[c]), 0.f), hi2);
+                    v[c] = u;
+                }
+                return v;
+            };
+            float* __restrict__ ytile = p.y + (img + (long)y0 * p.W) * p.ldy + ncl;
+#pragma unroll
+            for (int k = 0; k < E_NROWS; ++k) {
+                const int r = er + k * E_RPP;
+                f32x4 v = finish(*reinterpret_cast<const f32x4*>(&stage[r][ncl]));
+                if constexpr (RES) v = v + rve[k];
+                float* dst = ytile + ((r >> 4) * p.W + (r & 15) + x0) * p.ldy;
+                if (p.nt) store_nt16(dst, v);
+                else *reinterpret_cast<f32x4*>(dst) = v;
+            }
+        }
+        __syncthreads();  // the staging tile is read out before the next tile's A planes overwrite it
+    }
+}
+
 
 // several tiles per workgroup where that still leaves >= 8 workgroups per CU
 int tiles_per_workgroup(int tiles_w, long wgs1) {
@@ -464,6 +731,25 @@ int launch_wres(const SepParams& p, int B, hipStream_t st) {
     if (p.gen_a) hipLaunchKernelGGL((sep_fused_kernel<64, 3, true, 8, false, true>), grid, dim3(256), 0, st, q);
     else hipLaunchKernelGGL((sep_fused_kernel<64, 3, false, 8, false, true>), grid, dim3(256), 0, st, q);
     return emd::check_launch("sep_fused_kernel<resident W>");
+}
+
+// the generated-input layer fed by the 1-channel image itself (sep_gen9_kernel): the tile walk of launch_wres
+int launch_gen9(const SepParams& p, int B, hipStream_t st) {
+    SepParams q = p;
+    const int tiles_w = p.W / 16;
+    q.tpw = tiles_per_workgroup(tiles_w, (long)tiles_w * (p.H / 8) * B);
+    const dim3 grid(tiles_w / q.tpw, p.H / 8, B);
+    q.nt = sep_nt();
+    q.xcd = sep_xcd() && ((long)grid.x * grid.y * grid.z) % 8 == 0;
+    if (p.Cin == 64) {
+        if (p.res) hipLaunchKernelGGL((sep_gen9_kernel<2, true>), grid, dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((sep_gen9_kernel<2, false>), grid, dim3(256), 0, st, q);
+    } else if (p.res) {
+        hipLaunchKernelGGL((sep_gen9_kernel<1, true>), grid, dim3(256), 0, st, q);
+    } else {
+        hipLaunchKernelGGL((sep_gen9_kernel<1, false>), grid, dim3(256), 0, st, q);
+    }
+    return emd::check_launch("sep_gen9_kernel");
 }
 
 template <int BN>
@@ -752,6 +1038,45 @@ extern "C" int emd_sep3x3_fused_gen_f32(const float* d, int ldd, const float* ge
     EMD_REQUIRE(gen_a && gen_t, EMD_E_INVALID, "emd_sep3x3_fused_gen_f32: null gen_a / gen_t");
     return sep_fused_entry(d, ldd, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, B, H, W, Cin, Cout, act,
                            precision, reflect, stream, gen_a, gen_t, gen_act);
+}
+
+// The same layer taking the 1-channel image and the nine taps of its depthwise conv instead of d (graph D's cnn0 -> cnn0_last,
+// machine_learning/denoiser.py:252-255): d = what emd_cin1_f32(img, w9, (1,0,0,0), 0, act = 0) writes is formed per tile inside the
+// kernel, so neither d nor the Cin-channel tensor goes through memory.  The rule is a function of the layer's shape alone.
+extern "C" int emd_sep3x3_fused_gen9_supported(int H, int W, int Cin, int Cout) {
+    return H >= 8 && W >= 16 && H % 8 == 0 && W % 16 == 0 && (Cin == 32 || Cin == 64) && Cout % 4 == 0 && Cout >= 4 && Cout <= 64;
+}
+
+extern "C" int emd_sep3x3_fused_gen9_f32(const float* img, const float* w9, const float* gen_a, const float* gen_t, int gen_act,
+                                         const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
+                                         const float* shift1, const float* scale2, const float* shift2, const float* res,
+                                         int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
+                                         int precision, int reflect, emd_stream_t stream) {
+    EMD_REQUIRE(img && w9 && gen_a && gen_t && dw && whi && wlo && scale1 && shift1 && y, EMD_E_INVALID,
+                "emd_sep3x3_fused_gen9_f32: null pointer");
+    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_gen9_f32: scale2/shift2 pair");
+    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_sep3x3_fused_gen9_f32: bad shape");
+    EMD_REQUIRE(gen_act == EMD_ACT_RELU6 && !reflect && precision == 3 && emd_sep3x3_fused_gen9_supported(H, W, Cin, Cout),
+                EMD_E_UNSUPPORTED,
+                "emd_sep3x3_fused_gen9_f32: needs relu6 generation, zero padding, split-bf16, H%8==0, W%16==0, Cin 32 or 64, Cout%4==0, "
+                "Cout<=64 (use emd_cin1_f32 + emd_sep3x3_fused_gen_f32)");
+    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_gen9_f32: B > 65535");
+    EMD_REQUIRE(9L * W * (ldy > ldres ? ldy : ldres) < (1L << 31), EMD_E_UNSUPPORTED,
+                "emd_sep3x3_fused_gen9_f32: 9 image rows of the output must span fewer than 2^31 floats");
+    EMD_REQUIRE(ldy % 4 == 0 && ldy >= Cout && (!res || (ldres % 4 == 0 && ldres >= Cout)), EMD_E_ALIGN,
+                "emd_sep3x3_fused_gen9_f32: pixel strides must be multiples of 4 and >= the channel count");
+    EMD_REQUIRE(emd::aligned16(gen_a) && emd::aligned16(gen_t) && emd::aligned16(dw) && emd::aligned16(whi) && emd::aligned16(wlo) &&
+                    emd::aligned16(y) && (!res || emd::aligned16(res)) && emd::aligned16(scale1) && emd::aligned16(shift1) &&
+                    (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))),
+                EMD_E_ALIGN, "emd_sep3x3_fused_gen9_f32: pointers (but img, w9) must be 16-byte aligned");
+    if (B == 0) return EMD_OK;
+    SepParams p{};
+    p.x = img; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = y; p.res = res;
+    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
+    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
+    p.ldx = 1; p.ldy = ldy; p.ldres = ldres; p.act = act; p.stride = 1;
+    p.gen_a = gen_a; p.gen_t = gen_t; p.gen_act = gen_act; p.gen_w9 = w9;
+    return launch_gen9(p, B, static_cast<hipStream_t>(stream));
 }
 
 // dev hook (not in the header): per-workgroup phase cycle sums for tools/sep_bench.py

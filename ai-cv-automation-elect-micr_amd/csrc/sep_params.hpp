@@ -39,7 +39,9 @@ struct SepParams {
     // Folded final conv (fold != 0; sep_pipe.hip, the 4-wave 64-column FOLD instance: emd_sep3x3_fused_fold_f32): y is not stored -- the
     // epilogue forms z_t[pixel] = sum_c fold_w[t][c] * y[pixel][c], t = 0..8, and writes nine planes fold_z [9][B][H][W].  One output too:
     // its two pointers and its flag share the second output's storage in the same way.
-    union { const uint16_t* W2hi; const float* rg_x; };
+    // d formed in the kernel (sep_fused.hip, sep_gen9_kernel: emd_sep3x3_fused_gen9_f32): x is the contiguous 1-channel image and gen_w9
+    // the nine taps of its 3x3 depthwise conv; one output, no generated residual: the pointer shares the second output's storage too.
+    union { const uint16_t* W2hi; const float* rg_x; const float* gen_w9; };
     union { const uint16_t* W2lo; const float* fold_w; };   // [9][64]: the 3x3 conv's taps, channel innermost
     union { float* y2; float* fold_z; };
     union { const float* scale_b; const float* rg_a; };

@@ -541,10 +541,18 @@ class DenoiserEngine:
             # cnn0 = relu6(d * a + t) is an outer product of the 1-channel depthwise result d: cnn0_last's patch loader
             # rebuilds it from d (4-channel scratch, d in channel 0) instead of reading a [B,S,S,64] tensor
             pc, pl = P["cnn0"], P["cnn0_last"]
-            d4 = ops.cin1(x, pc["w9"], self._unit4, self._zero4, E(S, 4), act=False)
             cnn0 = None
-            cnn0_last = ops.sep_fused_gen(d4, pc["a"], pc["shift"], pl["dw"], pl["pw"], pl["scale"], pl["shift"], E(S, f0),
-                                          scale2=pl.get("scale2"), shift2=pl.get("shift2"), precision=self.precision)
+            if (self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_GEN9", "1") != "0"
+                    and bool(_lib.load().emd_sep3x3_fused_gen9_supported(S, S, f0, f0))):
+                # d is formed inside the kernel too, tile by tile from the image: no d4 scratch, one launch less (same bits; the
+                # development switch EMD_D_GEN9=0 restores cin1 + the kernel that reads d)
+                cnn0_last = ops.sep_fused_gen(ops.Act(x), pc["a"], pc["shift"], pl["dw"], pl["pw"], pl["scale"], pl["shift"], E(S, f0),
+                                              scale2=pl.get("scale2"), shift2=pl.get("shift2"), precision=self.precision,
+                                              gen_w9=pc["w9"])
+            else:
+                d4 = ops.cin1(x, pc["w9"], self._unit4, self._zero4, E(S, 4), act=False)
+                cnn0_last = ops.sep_fused_gen(d4, pc["a"], pc["shift"], pl["dw"], pl["pw"], pl["scale"], pl["shift"], E(S, f0),
+                                              scale2=pl.get("scale2"), shift2=pl.get("shift2"), precision=self.precision)
         else:
             cnn0 = ops.cin1(x, P["cnn0"]["w9"], P["cnn0"]["a"], P["cnn0"]["shift"], E(S, f0))
             cnn0_last = self._sep("cnn0_last", cnn0)

@@ -327,14 +327,25 @@ def sep_dual(x: Act, dw_dev, w: PackedWeights, w2: PackedWeights, scale1, shift1
 
 
 def sep_fused_gen(d: Act, gen_a, gen_t, dw_dev, w: PackedWeights, scale1, shift1, out: Act, gen_act=True, act=True,
-                  scale2=None, shift2=None, res: Act | None = None, precision=PREC_BF16X3, stream=None, reflect=False):
+                  scale2=None, shift2=None, res: Act | None = None, precision=PREC_BF16X3, stream=None, reflect=False, gen_w9=None):
     """sep_fused on the generated input act(d[..., 0] * gen_a + gen_t) (emd_sep3x3_fused_gen_f32): d holds one value per
-    pixel in its channel 0, the w.cin-channel tensor is rebuilt in registers."""
+    pixel in its channel 0, the w.cin-channel tensor is rebuilt in registers.  gen_w9 (nine taps): d is the contiguous 1-channel
+    IMAGE instead and its 3x3 depthwise conv with those taps is formed inside the kernel as well (emd_sep3x3_fused_gen9_f32, where
+    sep_fused_gen9_supported says so)."""
     lib = _lib.load()
     assert (out.B, out.H, out.W, out.C) == (d.B, d.H, d.W, w.cout) and w.taps == 1
     assert gen_a.numel() == w.cin and gen_t.numel() == w.cin
     if res is not None:
         assert (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, out.C)
+    if gen_w9 is not None:
+        assert d.C == 1 and d.ld == 1 and gen_w9.numel() == 9
+        rc = lib.emd_sep3x3_fused_gen9_f32(d.ptr, _p(gen_w9), _p(gen_a), _p(gen_t), _act(gen_act), _p(dw_dev), _p(w.hi), _p(w.lo),
+                                           _p(scale1), _p(shift1), _p(scale2), _p(shift2),
+                                           res.ptr if res is not None else C.c_void_p(0), res.ld if res is not None else 0,
+                                           out.ptr, out.ld, d.B, d.H, d.W, w.cin, w.cout, _act(act), precision,
+                                           1 if reflect else 0, _lib.stream_ptr(stream))
+        _lib.check(rc, "emd_sep3x3_fused_gen9_f32")
+        return out
     rc = lib.emd_sep3x3_fused_gen_f32(d.ptr, d.ld, _p(gen_a), _p(gen_t), _act(gen_act), _p(dw_dev), _p(w.hi), _p(w.lo),
                                       _p(scale1), _p(shift1), _p(scale2), _p(shift2),
                                       res.ptr if res is not None else C.c_void_p(0), res.ld if res is not None else 0,

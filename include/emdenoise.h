@@ -812,6 +812,18 @@ int emd_sep3x3_fused_gen_f32(const float* d, int ldd, const float* gen_a, const 
                              const float* scale2, const float* shift2, const float* res, int ldres, float* y, int ldy, int B,
                              int H, int W, int Cin, int Cout, int act, int precision, int reflect, emd_stream_t stream);
 
+/* The same layer with d formed inside the kernel too: img is the contiguous 1-channel image [B,H,W] and w9 the nine taps of its 3x3
+ * depthwise conv (TF SAME), d = what emd_cin1_f32(img, w9, (1,0,0,0), 0, ..., act = 0) writes into channel 0.  The generated input is
+ * built in registers from a (8+2) x (16+2) tile of d in LDS; neither d nor the Cin-channel tensor exists in memory.  Covers
+ * gen_act == EMD_ACT_RELU6, zero padding (reflect == 0), precision == EMD_PREC_BF16X3 and the shapes
+ * emd_sep3x3_fused_gen9_supported(H, W, Cin, Cout) accepts (H % 8 == 0, W % 16 == 0, Cin 32 or 64, Cout % 4 == 0, Cout <= 64);
+ * anything else is EMD_E_UNSUPPORTED (use emd_cin1_f32 + emd_sep3x3_fused_gen_f32).  Bit-identical to that pair. */
+int emd_sep3x3_fused_gen9_supported(int H, int W, int Cin, int Cout);
+int emd_sep3x3_fused_gen9_f32(const float* img, const float* w9, const float* gen_a, const float* gen_t, int gen_act, const float* dw,
+                              const uint16_t* whi, const uint16_t* wlo, const float* scale1, const float* shift1,
+                              const float* scale2, const float* shift2, const float* res, int ldres, float* y, int ldy, int B,
+                              int H, int W, int Cin, int Cout, int act, int precision, int reflect, emd_stream_t stream);
+
 /* Discriminator head (misc_py/gan-infilling-100.py:560-567, :708): a fully connected layer to ONE output per row,
  * y[b] = x[b,:K].w + bias (x row stride ldx), and output = sigmoid(max(small, medium, large)). */
 int emd_fc_rows_f32(const float* x, int ldx, const float* w, float bias, float* y, int B, int K, emd_stream_t stream);
