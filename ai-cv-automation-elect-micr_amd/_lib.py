@@ -455,6 +455,12 @@ SIGNATURES = {
     "emd_image_stats_f64": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # x y B n stats stream
     "emd_scale01_f32": (C.c_int, [_c_float_p, _c_float_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]),
+    # ---- cv2.resize (csrc/resample.hip; the tap arithmetic: csrc/resize_taps.hpp)
+    # interpolation n_in n_out other_in other_out first_host count_host weights_host block_host
+    "emd_resize_taps": (C.c_int, [C.c_int] * 5 + [C.c_void_p] * 4),
+    # x image_stride row_stride B H W boxes_dev y h w interpolation stream
+    "emd_resize_f32": (C.c_int, [_c_float_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _c_float_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p]),
     # ---- the 2-D FFT and the radial frequency profile (csrc/fft.hip)
     "emd_radial_bins": (C.c_int, [C.c_int]),
     "emd_rfft2_workspace_bytes": (C.c_size_t, [C.c_int] * 2),

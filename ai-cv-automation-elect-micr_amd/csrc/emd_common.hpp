@@ -119,6 +119,7 @@ struct Knobs {
     int conv3_pipe = 1;      // dense 3x3 conv (stride 1, rate 1, H % 8 == 0, W % 32 == 0) on the patch-resident kernel (conv3_pipe.hip): 1 = up to 192 output channels, 2 = any width, 0 = never
     int split_variant = -1;  // pointwise split32 GEMM pipeline variant (-1 = dispatch rule)
     int exitwave_composed = 0;   // exit-wave reconstruction at pad_periods == 0 (exitwave.hip): 1 = composed from the launches of emd_propagate_f64 (the path of pad_periods > 0; rounding-level differences, larger workspace) instead of the two-launch frequency-domain iteration
+    int resize_generic = 0;  // cv2.resize (resample.hip): 1 = the inner loop that serves every form, instead of the one for the fixed forms (at most four taps) and the one for runs (same bits; the A/B of tools/resample_bench.py)
     int sep_stamp_wave = 0;  // sep_pipe2 in-kernel stamps: the wave (0-7) that reports
     int wgrad_msplit = 0;    // weight-gradient GEMM: slices of the pixel dimension (each adds its partial sums atomically): 0 = rule, n = at most n
     int wgrad_tile = 0;      // weight-gradient GEMM: 0 = rule (128 where a dimension exceeds 64), 64 = 64 x 64 tiles everywhere

@@ -13,8 +13,8 @@ Deviations from the reference: ``px`` (the pixel size) replaces its ``px_dim = 1
 ``|b_k| = 0`` the modulus constraint gives ``a_k`` (the reference: NaN); with ``from_intensity`` the amplitude is
 ``sqrt(max(image_k, 0))`` and ``psi_k`` starts as that amplitude, not as the image; with ``cs != 0`` the back-propagation multiplies
 by ``H(-df)`` as the reference does, which is not ``conj H(df)`` (the Cs term keeps its sign; at ``cs == 0`` the two are equal bit
-for bit); ``aperture_mask``, the bisection after the defocus sweep, ``cv2.resize`` of the crops, ``refine_params``, TIFF reading and
-the display helpers are not here.
+for bit); ``aperture_mask``, the bisection after the defocus sweep, ``refine_params``, TIFF reading and the display helpers are not
+here.  ``resize_stack`` (``cv2.resize`` of the crops) is ``emdenoise.resample.resize``.
 
 Registration (csrc/register.hip) is what the reference's ``EWREC.__init__`` does before it reconstructs:
 ``phase_correlate`` / ``rel_pos_estimate`` (``cv2.phaseCorrelate`` restated in include/emdenoise.h; OpenCV is not run), the cropping
@@ -452,6 +452,16 @@ def crop_stack(stack, centres, side, pad_val=0.0):
     x, as_np = _real(stack, device)
     out = _crop(x, c, side, pad_val)
     return out.cpu().numpy() if as_np else out
+
+
+def resize_stack(stack, side, interpolation="linear"):
+    """``EWREC.resize_stack`` (ewrec_class.py:236-238): ``cv2.resize(img, (side, side))`` of every image of ``stack`` ``[N,H,W]`` float32
+    -> ``[N,side,side]``, with cv2's default ``INTER_LINEAR``; a thin call of ``emdenoise.resample.resize``."""
+    from . import resample
+
+    if len(np.shape(stack)) != 3:
+        raise ValueError(f"resize_stack: a stack [N,H,W] (got shape {tuple(np.shape(stack))})")
+    return resample.resize(stack, side, interpolation)
 
 
 def align(stack, side=None, window=False, pad_val=0.0):

@@ -1466,6 +1466,62 @@ int emd_psiart_step_f64(const float* images, int N, int S, double* amp, double* 
                         double* g_params, void* workspace, size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * cv2.resize for one-channel float32 (csrc/resample.hip, csrc/resize_taps.hpp): the reference's
+ * load_image(addr, resizeSize), its random crops resized to the network's side (modified_Xception.py:976-982) and
+ * EWREC.resize_stack (ewrec_class.py:236-238).  OpenCV is not used: the arithmetic is restated from these rules.
+ *
+ * interpolation: cv2's codes, EMD_RESIZE_NEAREST 0, EMD_RESIZE_LINEAR 1, EMD_RESIZE_CUBIC 2, EMD_RESIZE_AREA 3.  For one axis with
+ * n_in source and n_out destination samples, inv = (double)n_out / n_in and scale = 1.0 / inv (cv2's order; not n_in / n_out).
+ * Everything is IEEE double, every operation rounding on its own, except where a rounding to float32 is written out: those are
+ * cv2's own and decide which pixels are read.  For destination sample d:
+ *   NEAREST   s = min(floor(d * scale), n_in - 1); one tap, weight 1.
+ *   LINEAR    f = (float)((d + 0.5) * scale - 0.5);  s = floor(f);  f = (float)(f - s);  s < 0: s = 0, f = 0;  s >= n_in - 1:
+ *             s = n_in - 1, f = 0.  Taps s and min(s + 1, n_in - 1), weights 1 - f and f.
+ *   CUBIC     f and s as LINEAR without the clamps; taps s - 1 .. s + 2, each index clamped into 0 .. n_in - 1; with A = -0.75:
+ *             c0 = ((A (f + 1) - 5 A) (f + 1) + 8 A) (f + 1) - 4 A;   c1 = ((A + 2) f - (A + 3)) f f + 1;
+ *             c2 = ((A + 2) (1 - f) - (A + 3)) (1 - f) (1 - f) + 1;   c3 = 1 - c0 - c1 - c2   (in double from the float32 f: cv2 forms
+ *             them in float32, a deviation of a few 1e-8).
+ *   AREA      scale >= 1 on BOTH axes -- true area:
+ *               whole ratios, i = (int)scale with |scale - i| < DBL_EPSILON on both axes: the mean of the i_y x i_x block, the sum
+ *               formed in double, divided by the block's pixel count, rounded once;
+ *               otherwise, per axis:  f1 = d * scale;  f2 = f1 + scale;  cell = min(scale, n_in - f1);  s1 = ceil(f1);
+ *               s2 = min(floor(f2), n_in - 1);  s1 = min(s1, s2);  if s1 - f1 > 1e-3, pixel s1 - 1 has weight (float)((s1 - f1) / cell);
+ *               pixels s1 .. s2 - 1 have (float)(1.0 / cell);  if f2 - s2 > 1e-3, pixel s2 has
+ *               (float)(min(min(f2 - s2, 1.0), cell) / cell).  The 1e-3 rule drops slivers, so a sample's weights need not sum to 1
+ *               (2001 -> 2000: sample 0 sums to 1 / 1.0005): cv2's behaviour, kept.
+ *             an axis enlarges -- cv2's emulated area, on both axes:  s = floor(d * scale);  f = (float)((d + 1) - (s + 1) * inv);
+ *               f = f <= 0 ? 0 : (float)(f - floor(f));  then LINEAR's two clamps and pair of taps.  A whole-ratio enlargement is
+ *               nearest neighbour.
+ * y[r][c] = sum_j beta_j sum_i alpha_i x[sy_j][sx_i]: a source row's columns first, rows ascending, in double, rounded to float32
+ * once (cv2 accumulates in float32, a horizontal and then a vertical pass: a deviation at float32 rounding level).  Where the columns a
+ * tile of 64 output columns reads span more than 264 source columns (ratios above 4), a row's sum is formed per 264-column segment and
+ * each part is weighted and added on its own: a fixed order, different in the last bits of the double only.  Equal sizes return the
+ * source bit for bit in every mode (the weights are exactly 0 and 1), as does NEAREST always -- but for -0, which comes out as +0.
+ * Non-finite input is the caller's problem.
+ *
+ * No atomics, no workspace, no host synchronisation, one launch: capturable and bitwise reproducible, and an image's result does not
+ * depend on B. */
+#define EMD_RESIZE_NEAREST 0
+#define EMD_RESIZE_LINEAR 1
+#define EMD_RESIZE_CUBIC 2
+#define EMD_RESIZE_AREA 3
+/* HOST only: the tap description of every destination sample along one axis, from the same code the kernel calls (the one copy of
+ * the arithmetic).  other_in -> other_out are the sizes of the other axis (the area rule looks at both).  Sample d has count[d] taps;
+ * tap k reads source index min(max(first[d] + k, 0), n_in - 1) with weight
+ *     k == 0 ? weights[d][0] : k == count[d] - 1 ? weights[d][3] : k == 1 ? weights[d][1] : weights[d][2]
+ * (first, count: [n_out]; weights: [n_out][4]).  *block is 0, or i where this axis takes the whole-ratio area form: the weights are
+ * then 1 and the 2-D sum is divided by the block's pixel count.  1 <= n_in, other_in <= 32768, 1 <= n_out, other_out <= 8192. */
+int emd_resize_taps(int interpolation, int n_in, int n_out, int other_in, int other_out, int* first, int* count, double* weights,
+                    int* block);
+/* y[b] ([B,h,w], contiguous) = cv2.resize of image b (H x W at x + b * image_stride, rows row_stride floats apart) to h x w.
+ * boxes_dev: NULL for the whole image, or DEVICE int32 [B][4] = (x0, y0, bw, bh): image b's source is that rectangle, the sizes and
+ * the area rule taken per image on the device; a box is clamped into the image whatever it holds (x0 into 0 .. W - 1, bw into
+ * 1 .. W - x0, likewise y), so no address leaves the image.  1 <= H, W <= 32768, 1 <= h, w <= 8192, row_stride >= W,
+ * 0 <= B <= 65535 (B == 0 is a no-op).  y may not overlap x. */
+int emd_resize_f32(const float* x, long image_stride, int row_stride, int B, int H, int W, const int* boxes_dev, float* y, int h, int w,
+                   int interpolation, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */

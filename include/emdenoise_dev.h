@@ -37,6 +37,8 @@
  *   exitwave_composed (0)  emd_exitwave_reconstruct_f64 at pad_periods == 0: 1 = the iteration composed from the launches of
  *                       emd_propagate_f64 (the path of pad_periods > 0) instead of the two-launch frequency-domain iteration; differences
  *                       at rounding level.  emd_exitwave_workspace_bytes follows it: set it before asking for the size
+ *   resize_generic (0)  emd_resize_f32: 1 = the instance whose one inner loop serves every form, instead of the loops for the fixed
+ *                       forms (at most four taps) and for runs (same bits; the A/B of tools/resample_bench.py)
  */
 #ifndef EMDENOISE_DEV_H
 #define EMDENOISE_DEV_H
