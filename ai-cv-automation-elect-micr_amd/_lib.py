@@ -74,6 +74,14 @@ SIGNATURES = {
     "emd_conv1x1_f32": (C.c_int, [_c_float_p, C.c_int, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p, _c_float_p,
                                   _c_float_p, _c_float_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # x ldx whi wlo scale1 up ldup Hu Wu scale2 shift2 res ldres y ldy B H W Cin Cout act precision stream
+    "emd_conv1x1_up_f32": (C.c_int, [_c_float_p, C.c_int, C.c_void_p, C.c_void_p, _c_float_p, _c_float_p, C.c_int, C.c_int, C.c_int,
+                                     _c_float_p, _c_float_p, _c_float_p, C.c_int, _c_float_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "emd_dw3x3_up_split32_supported": (C.c_int, [C.c_int] * 6),
+    # lo ldlo Hi Wi Cup x ldx w y ldy B H W C stream
+    "emd_dw3x3_up_split32_f32": (C.c_int, [_c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_float_p, C.c_int, _c_float_p, C.c_void_p,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "emd_sep3x3_fused_supported": (C.c_int, [C.c_int] * 6),
     "emd_deconv3x3s2_fused_preferred": (C.c_int, [C.c_int] * 5),
     # x ldx dw whi wlo scale1 shift1 scale2 shift2 res ldres y ldy B H W Cin Cout act precision stream

@@ -97,6 +97,9 @@ __global__ __launch_bounds__(256) void dw3x3_s1_roll(const float* __restrict__ x
     // where TF SAME pads) and the loads of input row t+3 are issued before row t is used: the first version branched
     // around each of a row's three loads and waited for them at the end of every row -- ten dependent memory round
     // trips per thread, 53 us for the 32 x 32 x 728 maps that a plain copy moves in 30.
+    // (dw3x3_s1_roll_up below carries a copy of this load loop and of the row step for its read channels, and must give this kernel's bits:
+    // a change to the prefetch depth, the clamping or the order of the sums here is made there too.  Sharing the body through a __device__
+    // function was not taken: the same step changed every instance of gemm_conv_kernel's instructions, profiles/r09_experiments.txt 5a.)
     constexpr int PF = 3, NR = TH + 2;
     // REFLECT (graph G: tf.pad(REFLECT, 1) + VALID): index -1 -> 1, H -> H-2, in both directions; nothing is zeroed
     const long xl = hasl ? -(long)ldx : (REFLECT ? (long)ldx : 0), xr = hasr ? (long)ldx : (REFLECT ? -(long)ldx : 0);
@@ -143,6 +146,191 @@ __global__ __launch_bounds__(256) void dw3x3_s1_roll(const float* __restrict__ x
         }
         s0 = add4(s1, h1);
         s1 = h0;
+    }
+}
+
+// dw3x3_s1_roll<TH, SPLIT = true> over concat(resize_bilinear(lo), x) along the channels, without that tensor: graph D's deconv2_a reads
+// [up(aspp) | cnn1_strided] (machine_learning/denoiser.py:350-356), and two thirds of those channels are an interpolation of a tensor
+// 1/16 their size.  Channel quads [0, Cup4) are formed from lo [B,Hi,Wi,4 Cup4] with resize_bilinear_kernel's arithmetic (resize_src,
+// lerp4: x inside a source row, then y -- its bits), quads [Cup4, C4) are read from x [B,H,W,4 (C4 - Cup4)].  4 Cup4 is a multiple of
+// 64, the channels of a workgroup, so "generated or read" is uniform per workgroup.  A generated thread keeps the x-interpolated
+// (left, centre, right column) triples of the two live SOURCE rows (TA: row y0, TB: row y1) and the raw taps of the row after them:
+// loads happen when y0 advances (every fourth output row at 4x), one source-row period ahead of their use.  Workgroup -> tile map,
+// padding, the order of the three row contributions and the store are dw3x3_s1_roll's (the lambda `emit`): bits of resize + depthwise.
+// F > 0 (instantiated for 4, graph D's factor): H == F Hi with F a power of two, so sy = 1 / F and (float)row * sy are exact and
+// y0 = row / F: the rows at which y0 advances are known when the strip loop is unrolled, every load is unconditional and waited for
+// by count.  F = 0: any H >= Hi; y0 is followed at run time
+// with workgroup-uniform branches, and a wait inside a branch also drains the stores in flight (312 us against F = 4's figure in
+// DESIGN.md 3.4 on graph D's shape).
+template <int TH, int F>
+__global__ __launch_bounds__(256) void dw3x3_s1_roll_up(const float* __restrict__ lo, int ldlo, int Hi, int Wi, int Cup4, float sy, float sx,
+                                                        const float* __restrict__ x, int ldx, const float* __restrict__ w,
+                                                        float* __restrict__ y, int ldy, int H, int W, int C4, int nstrip, int C4t, int xcd) {
+    const int ncb = (C4t + 15) >> 4, npb = (W + 15) >> 4;
+    int bidx = xcd ? xcd_run(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int cblk = bidx % ncb;
+    bidx /= ncb;
+    const int pblk = bidx % npb;
+    bidx /= npb;
+    const int strip = bidx % nstrip;
+    const long b = bidx / nstrip;
+    const int c4o = cblk * 16 + (threadIdx.x & 15);
+    const int ox = pblk * 16 + (threadIdx.x >> 4);
+    if (c4o >= C4t || ox >= W) return;
+    const bool padq = c4o >= C4;
+    const int c4 = padq ? C4 - 1 : c4o;
+    const int C = C4 * 4;
+
+    float4 wk[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wk[k] = *reinterpret_cast<const float4*>(w + k * C + c4 * 4);
+    const int oy0 = strip * TH;
+    const bool hasl = ox > 0, hasr = ox + 1 < W;
+    constexpr int PF = 3, NR = TH + 2;
+    auto row_of = [&](int tt) {   // input row of step tt, clamped into the image (a padding row's value is replaced by zero in emit)
+        const int iy = oy0 - 1 + tt;
+        return iy < 0 ? 0 : (iy >= H ? H - 1 : iy);
+    };
+    float4 s0 = f4zero(), s1 = f4zero();  // s0: top+mid of output (t-2); s1: top of output (t-1)
+    auto emit = [&](int tt, float4 c, float4 l, float4 r) {
+        const int iy = oy0 - 1 + tt;
+        const bool ok = iy >= 0 && iy < H;
+        c = ok ? c : f4zero();
+        l = ok && hasl ? l : f4zero();
+        r = ok && hasr ? r : f4zero();
+        const float4 h0 = fma4(wk[0], l, fma4(wk[1], c, fma4(wk[2], r, f4zero())));
+        const float4 h1 = fma4(wk[3], l, fma4(wk[4], c, fma4(wk[5], r, f4zero())));
+        const float4 h2 = fma4(wk[6], l, fma4(wk[7], c, fma4(wk[8], r, f4zero())));
+        if (tt >= 2) {
+            const int oy = oy0 + tt - 2;
+            if (oy < H) emd::dw_store<true>(y, (b * H + oy) * (long)W + ox, ldy, c4o, padq ? f4zero() : add4(s0, h2));
+        }
+        s0 = add4(s1, h1);
+        s1 = h0;
+    };
+
+    if (cblk * 16 >= Cup4) {   // read: dw3x3_s1_roll's loads, three rows ahead
+        const float* xb = x + (b * H) * (long)W * ldx + (c4 - Cup4) * 4;
+        const long xl = hasl ? -(long)ldx : 0, xr = hasr ? (long)ldx : 0;
+        float4 rc[PF], rl[PF], rr[PF];
+#pragma unroll
+        for (int t0 = 0; t0 < PF && t0 < NR; ++t0) {
+            const float* row = xb + ((long)row_of(t0) * W + ox) * ldx;
+            rc[t0] = *reinterpret_cast<const float4*>(row);
+            rl[t0] = *reinterpret_cast<const float4*>(row + xl);
+            rr[t0] = *reinterpret_cast<const float4*>(row + xr);
+        }
+#pragma unroll
+        for (int tt = 0; tt < NR; ++tt) {
+            const float4 c = rc[tt % PF], l = rl[tt % PF], r = rr[tt % PF];
+            if (tt + PF < NR) {
+                const float* row = xb + ((long)row_of(tt + PF) * W + ox) * ldx;
+                rc[tt % PF] = *reinterpret_cast<const float4*>(row);
+                rl[tt % PF] = *reinterpret_cast<const float4*>(row + xl);
+                rr[tt % PF] = *reinterpret_cast<const float4*>(row + xr);
+            }
+            emit(tt, c, l, r);
+        }
+        return;
+    }
+
+    // generated: source columns and weights of the output columns (left, centre, right; a missing neighbour repeats the centre, as the
+    // clamped loads above do, and is zeroed in emit)
+    const float* lb = lo + (b * Hi) * (long)Wi * ldlo + c4 * 4;
+    const int col[3] = {hasl ? ox - 1 : ox, ox, hasr ? ox + 1 : ox};
+    int xa[3], xb2[3];
+    float lx[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        int x0, x1;
+        resize_src(col[k], sx, Wi, x0, x1, lx[k]);
+        xa[k] = x0 * ldlo;   // Wi * ldlo < 2^31 (checked at the entry)
+        xb2[k] = x1 * ldlo;
+    }
+    auto load6 = [&](int ys, float4(&q)[6]) {
+        const float* row = lb + (long)ys * Wi * ldlo;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            q[2 * k] = *reinterpret_cast<const float4*>(row + xa[k]);
+            q[2 * k + 1] = *reinterpret_cast<const float4*>(row + xb2[k]);
+        }
+    };
+    auto xinterp = [&](const float4(&q)[6], float4(&t)[3]) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) t[k] = lerp4(q[2 * k], q[2 * k + 1], lx[k]);
+    };
+    if constexpr (F != 0) {
+        static_assert(TH % F == 0, "a strip starts on a source row");
+        // R_j = the x-interpolated source row base + j (clamped into lo): input rows oy0 - 1 + tt with tt in 1 + p F .. (p + 1) F have
+        // y0 = base + 1 + p and lie between R_{p+1} and R_{p+2}; tt = 0 (row oy0 - 1) between R_0 and R_1
+        const int base = oy0 / F - 1;
+        auto srow = [&](int j) {
+            const int r = base + j;
+            return r < 0 ? 0 : (r > Hi - 1 ? Hi - 1 : r);
+        };
+        float4 TA[3], TB[3], q0[6], q1[6], nq[6];
+        load6(srow(0), q0);
+        load6(srow(1), q1);
+        load6(srow(2), nq);
+        xinterp(q0, TA);
+        xinterp(q1, TB);
+#pragma unroll
+        for (int tt = 0; tt < NR; ++tt) {
+            if (tt >= 1 && (tt - 1) % F == 0) {   // known at compile time
+#pragma unroll
+                for (int k = 0; k < 3; ++k) TA[k] = TB[k];
+                xinterp(nq, TB);
+                if (tt + F < NR) load6(srow((tt - 1) / F + 3), nq);
+            }
+            int y0, y1;
+            float ly;
+            resize_src(row_of(tt), sy, Hi, y0, y1, ly);   // the weight as resize_bilinear_kernel forms it
+            emit(tt, lerp4(TA[1], TB[1], ly), lerp4(TA[0], TB[0], ly), lerp4(TA[2], TB[2], ly));
+        }
+        return;
+    }
+    // rows are workgroup-uniform: the comparisons below are scalar branches
+    auto src_rows = [&](int tt, int& y0, int& y1, float& ly) {
+        resize_src(row_of(tt), sy, Hi, y0, y1, ly);
+        y0 = __builtin_amdgcn_readfirstlane(y0);
+        y1 = __builtin_amdgcn_readfirstlane(y1);
+    };
+    float4 TA[3], TB[3], nq[6];   // nq: the raw taps of source row yn, the row expected next
+    int ya, yb, yn;
+    float ly;
+    src_rows(0, ya, yb, ly);
+    load6(ya, nq);
+    xinterp(nq, TA);
+    load6(yb, nq);
+    xinterp(nq, TB);
+    yn = min(yb + 1, Hi - 1);
+    load6(yn, nq);
+#pragma unroll
+    for (int tt = 0; tt < NR; ++tt) {
+        int y0, y1;
+        src_rows(tt, y0, y1, ly);
+        if (y0 != ya) {
+            if (y0 == yb) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) TA[k] = TB[k];
+            } else {
+                // y0 moved past y1's row: float rounding does that at ratios just below 1 where y0 + 1 is a power of two (19657 -> 19663
+                // rows: y0 = 16383, 16385 at rows 16389, 16390; never below 5793 rows, never at 1 or at 1/2 and below).  Served
+                // through nq, whose prefetched row is then fetched again below.
+                load6(y0, nq);
+                xinterp(nq, TA);
+                yn = -1;
+            }
+            ya = y0;
+        }
+        if (y1 != yb) {
+            if (y1 != yn) load6(y1, nq);
+            xinterp(nq, TB);
+            yb = y1;
+            yn = min(y1 + 1, Hi - 1);
+            load6(yn, nq);
+        }
+        emit(tt, lerp4(TA[1], TB[1], ly), lerp4(TA[0], TB[0], ly), lerp4(TA[2], TB[2], ly));
     }
 }
 
@@ -482,22 +670,16 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __res
     long t = emd::divmod(tid, C4, c4);
     t = emd::divmod(t, Wo, ox);
     const long b = emd::divmod(t, Ho, oy);
-    const float fy = (float)oy * sy, fx = (float)ox * sx;
-    const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-    const int y1 = min(y0 + 1, Hi - 1), x1 = min(x0 + 1, Wi - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    resize_src(oy, sy, Hi, y0, y1, ly);
+    resize_src(ox, sx, Wi, x0, x1, lx);
     const float* xb = x + (b * Hi) * (long)Wi * ldx + c4 * 4;
     const float4 tl = *reinterpret_cast<const float4*>(xb + ((long)y0 * Wi + x0) * ldx);
     const float4 tr = *reinterpret_cast<const float4*>(xb + ((long)y0 * Wi + x1) * ldx);
     const float4 bl = *reinterpret_cast<const float4*>(xb + ((long)y1 * Wi + x0) * ldx);
     const float4 br = *reinterpret_cast<const float4*>(xb + ((long)y1 * Wi + x1) * ldx);
-    auto lerp = [](float a, float b2, float l) { return a + (b2 - a) * l; };
-    float4 o;
-    o.x = lerp(lerp(tl.x, tr.x, lx), lerp(bl.x, br.x, lx), ly);
-    o.y = lerp(lerp(tl.y, tr.y, lx), lerp(bl.y, br.y, lx), ly);
-    o.z = lerp(lerp(tl.z, tr.z, lx), lerp(bl.z, br.z, lx), ly);
-    o.w = lerp(lerp(tl.w, tr.w, lx), lerp(bl.w, br.w, lx), ly);
-    *reinterpret_cast<float4*>(y + ((b * Ho + oy) * (long)Wo + ox) * ldy + c4 * 4) = o;
+    *reinterpret_cast<float4*>(y + ((b * Ho + oy) * (long)Wo + ox) * ldy + c4 * 4) = lerp4(lerp4(tl, tr, lx), lerp4(bl, br, lx), ly);
 }
 
 // The same for an exact 2x upsampling (Ho = 2 Hi, Wo = 2 Wi: every resize of graph G's generator): src = dst / 2, so the
@@ -518,7 +700,6 @@ __global__ __launch_bounds__(256) void resize_up2_kernel(const float* __restrict
     const float4 tr = *reinterpret_cast<const float4*>(xb + ((long)sy * Wi + x1) * ldx);
     const float4 bl = *reinterpret_cast<const float4*>(xb + ((long)y1 * Wi + sx) * ldx);
     const float4 br = *reinterpret_cast<const float4*>(xb + ((long)y1 * Wi + x1) * ldx);
-    auto lerp = [](float a, float b2, float l) { return a + (b2 - a) * l; };
     const int Wo = 2 * Wi;
     float* yb = y + ((b * 2 * Hi + 2 * sy) * (long)Wo + 2 * sx) * ldy + c4 * 4;
 #pragma unroll
@@ -526,12 +707,7 @@ __global__ __launch_bounds__(256) void resize_up2_kernel(const float* __restrict
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const float ly = 0.5f * (float)i, lx = 0.5f * (float)j;
-            float4 o;
-            o.x = lerp(lerp(tl.x, tr.x, lx), lerp(bl.x, br.x, lx), ly);
-            o.y = lerp(lerp(tl.y, tr.y, lx), lerp(bl.y, br.y, lx), ly);
-            o.z = lerp(lerp(tl.z, tr.z, lx), lerp(bl.z, br.z, lx), ly);
-            o.w = lerp(lerp(tl.w, tr.w, lx), lerp(bl.w, br.w, lx), ly);
-            *reinterpret_cast<float4*>(yb + ((long)i * Wo + j) * ldy) = o;
+            *reinterpret_cast<float4*>(yb + ((long)i * Wo + j) * ldy) = lerp4(lerp4(tl, tr, lx), lerp4(bl, br, lx), ly);
         }
 }
 
@@ -794,6 +970,20 @@ inline int grid_for(long nthreads, unsigned* blocks) {
     return EMD_OK;
 }
 
+// Strip height of the rolling stride-1 depthwise kernels (dev knob dw_th forces one).
+inline int dw_strip_height(int B, int H, int W, int C4t) {
+    const int th_force = emd::g_knobs.dw_th;
+    // (round 3: 16 rows also on the short maps while that still leaves >= 1024 workgroups -- 32 x 32 x 728 at a batch of 32: 1536
+    // workgroups, 2.38 -> 2.28 ms over graph D's 43 standalone launches)
+    const long wg16 = (long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((C4t + 15) / 16);
+    int TH = th_force == 4 || th_force == 8 || th_force == 16 || th_force == 32 ? th_force : ((H >= 64 || (H >= 16 && wg16 >= 1024)) ? 16 : 8);
+    // small batches of small maps (4 images of 32 x 32 x 728: 384 workgroups of 8 rows): a thread's 10 dependent row loads are the
+    // kernel's whole life and most CUs hold one workgroup -- 4-row strips double the workgroups and halve the chain (same bits:
+    // the three row contributions of an output are added in the same order at every strip height)
+    if (!th_force && TH == 8 && (long)B * ((H + 7) / 8) * ((W + 15) / 16) * ((C4t + 15) / 16) < 1024) TH = 4;
+    return TH;
+}
+
 template <bool SPLIT, bool PRE = false>
 int dw3x3_launch(const char* who, const float* x, int ldx, const float* w, float* y, int ldy, int B, int H, int W, int C,
                  int stride, int rate, emd_stream_t stream, const float* pre_s = nullptr, const float* pre_t = nullptr, long pre_ld = 0,
@@ -827,15 +1017,7 @@ int dw3x3_launch(const char* who, const float* x, int ldx, const float* w, float
     if (stride == 1 && rate == 1) {
         // strip height: 16 rows (input re-read factor 18/16) measured 1-4 % faster than 8 on the 256^2/512^2 layers;
         // short images keep 8 so that small maps still spread over the chip
-        const int th_force = emd::g_knobs.dw_th;
-        // (round 3: 16 rows also on the short maps while that still leaves >= 1024 workgroups -- 32 x 32 x 728 at a batch of 32: 1536
-        // workgroups, 2.38 -> 2.28 ms over graph D's 43 standalone launches)
-        const long wg16 = (long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((C4t + 15) / 16);
-        int TH = th_force == 4 || th_force == 8 || th_force == 16 || th_force == 32 ? th_force : ((H >= 64 || (H >= 16 && wg16 >= 1024)) ? 16 : 8);
-        // small batches of small maps (4 images of 32 x 32 x 728: 384 workgroups of 8 rows): a thread's 10 dependent row loads are the
-        // kernel's whole life and most CUs hold one workgroup -- 4-row strips double the workgroups and halve the chain (same bits:
-        // the three row contributions of an output are added in the same order at every strip height)
-        if (!th_force && TH == 8 && (long)B * ((H + 7) / 8) * ((W + 15) / 16) * ((C4t + 15) / 16) < 1024) TH = 4;
+        const int TH = dw_strip_height(B, H, W, C4t);
         const int nstrip = (H + TH - 1) / TH;
         const long nblocks = (long)B * nstrip * ((W + 15) / 16) * ((C4t + 15) / 16);
         const long nthreads = nblocks * 256;
@@ -929,6 +1111,48 @@ extern "C" int emd_dw3x3_f32(const float* x, int ldx, const float* w, float* y, 
 extern "C" int emd_dw3x3_split32_f32(const float* x, int ldx, const float* w, void* y, int ldy, int B, int H, int W,
                                      int C, int stride, int rate, emd_stream_t stream) {
     return dw3x3_launch<true>("emd_dw3x3_split32_f32", x, ldx, w, static_cast<float*>(y), ldy, B, H, W, C, stride, rate, stream);
+}
+
+// emd_dw3x3_split32_f32 (stride 1, rate 1) over concat(emd_resize_bilinear_f32(lo -> [H, W]), x) along the channels, the upsampled
+// part formed in registers (dw3x3_s1_roll_up): w [9][C], C = Cup + channels of x.  Bit-identical to the two launches over the concat.
+extern "C" int emd_dw3x3_up_split32_supported(int Hi, int Wi, int H, int W, int Cup, int C) {
+    return Hi >= 1 && Wi >= 1 && H >= Hi && W >= Wi && H <= 65536 && W <= 65536 && Cup >= 64 && Cup % 64 == 0 && C > Cup && C % 4 == 0;
+}
+
+extern "C" int emd_dw3x3_up_split32_f32(const float* lo, int ldlo, int Hi, int Wi, int Cup, const float* x, int ldx, const float* w, void* y,
+                                        int ldy, int B, int H, int W, int C, emd_stream_t stream) {
+    EMD_REQUIRE(lo && x && w && y, EMD_E_INVALID, "emd_dw3x3_up_split32_f32: null pointer");
+    EMD_REQUIRE(B >= 0 && Hi >= 1 && Wi >= 1 && H >= 1 && W >= 1 && Cup >= 4 && C >= 4, EMD_E_INVALID, "emd_dw3x3_up_split32_f32: bad shape");
+    EMD_REQUIRE(emd_dw3x3_up_split32_supported(Hi, Wi, H, W, Cup, C), EMD_E_UNSUPPORTED,
+                "emd_dw3x3_up_split32_f32: needs H >= Hi, W >= Wi (at most 65536), Cup a multiple of 64 and below C, C a multiple of 4");
+    const int Cd = C - Cup, Cp = (C + 31) / 32 * 32;
+    EMD_REQUIRE(ldlo % 4 == 0 && ldlo >= Cup && ldx % 4 == 0 && ldx >= Cd && ldy % 32 == 0 && ldy >= Cp, EMD_E_ALIGN,
+                "emd_dw3x3_up_split32_f32: ldlo, ldx multiples of 4, >= their channel counts; ldy a multiple of 32, >= ceil32(C)");
+    EMD_REQUIRE(emd::aligned16(lo) && emd::aligned16(x) && emd::aligned16(w) && (reinterpret_cast<uintptr_t>(y) & 127u) == 0, EMD_E_ALIGN,
+                "emd_dw3x3_up_split32_f32: lo, x, w 16-byte and y 128-byte aligned");
+    EMD_REQUIRE((long)Wi * ldlo < (1L << 31), EMD_E_UNSUPPORTED, "emd_dw3x3_up_split32_f32: a row of lo must span fewer than 2^31 floats");
+    if (B == 0) return EMD_OK;
+    const int C4 = C / 4, C4t = Cp / 4;
+    const int TH = dw_strip_height(B, H, W, C4t);
+    const int nstrip = (H + TH - 1) / TH;
+    unsigned nb;
+    int rc = grid_for((long)B * nstrip * ((W + 15) / 16) * ((C4t + 15) / 16) * 256, &nb);
+    if (rc != EMD_OK) return rc;
+    const float sy = (float)Hi / (float)H, sx = (float)Wi / (float)W;   // as emd_resize_bilinear_f32
+    // the row schedule: fixed at compile time for the exact factor 4 (graph D's, the one measured; sy = 1/4: y0 = row / 4 exactly),
+    // followed at run time otherwise
+    const int F = H == 4 * Hi ? 4 : 0;
+#define EMD_DW_UP(THV, FV)                                                                                                                 \
+    hipLaunchKernelGGL((dw3x3_s1_roll_up<THV, FV>), dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), lo, ldlo, Hi, Wi, Cup / 4, sy, \
+                       sx, x, ldx, w, static_cast<float*>(y), ldy, H, W, C4, nstrip, C4t, dw_xcd(H, W))
+#define EMD_DW_UP_F(THV)                                                                        \
+    do {                                                                                        \
+        if (F == 4) EMD_DW_UP(THV, 4); else EMD_DW_UP(THV, 0);                                  \
+    } while (0)
+    if (TH == 32) EMD_DW_UP_F(32); else if (TH == 16) EMD_DW_UP_F(16); else if (TH == 4) EMD_DW_UP_F(4); else EMD_DW_UP_F(8);
+#undef EMD_DW_UP_F
+#undef EMD_DW_UP
+    return emd::check_launch("dw3x3_s1_roll_up");
 }
 
 // y = depthwise3x3( relu(x * pre_scale + pre_shift) ): the previous block's batch-statistics norm + relu applied on the fly

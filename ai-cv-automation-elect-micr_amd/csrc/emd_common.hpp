@@ -108,6 +108,7 @@ struct Knobs {
     int sep_wide = 1;        // sep_fused 256-column single-output form: 0 never, 1 Cin <= 256, 2 whenever it fits
     int sep_wres = 1;        // sep_fused 64-column instances keep the pointwise weights resident in LDS
     int fold_final = 1;      // graph D's native executor: deconv_final's channel sum folded into deconv0_b's epilogue (sep_pipe.hip FOLD + the nine-plane gather) where emd_sep3x3_fused_fold_supported holds; 0 = the pair of launches (the Python engine's switch is EMD_D_FOLD_FINAL)
+    int up_fused = 1;        // graph D's native executor: the upsampled ASPP output is formed inside its two consumers (residual2_d: emd_conv1x1_up_f32, deconv2_a: emd_dw3x3_up_split32_f32) where emd_dw3x3_up_split32_supported holds; 0 = resize into the concat buffer (the Python engine's switch is EMD_D_UP_FUSED)
     int epi_width = 0;       // dev: dwords a lane stores at a time in the patch-resident kernels' epilogue: 1 (a lane = one channel, as the MFMA leaves it) or 4 (after a 4 x 4 transpose inside lane quads); 0 = the kernel's rule (1, except sep_pipe with a residual on > 128 columns)
     int deconv_direct = 3;   // one-launch transposed conv: 3 = the patch-resident kernel (deconv_pipe.hip) where it covers the shape (H % 8 == 0, W % 32 == 0), else as 1; 1 = GEMM form, epilogue from the accumulators (deconv4_split_kernel); 2 = the same on 128-row tiles, two workgroups per CU; 0 = LDS-staged epilogue
     int nt_mask = 7;         // non-temporal output stores: bit 0 split32 convolutions, bit 1 fused separable conv, bit 2 pointwise GEMM

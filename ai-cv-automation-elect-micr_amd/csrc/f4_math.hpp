@@ -19,6 +19,23 @@ __device__ __forceinline__ float4 clamp4(float4 a, float hi) {
     return make_float4(fminf(fmaxf(a.x, 0.f), hi), fminf(fmaxf(a.y, 0.f), hi), fminf(fmaxf(a.z, 0.f), hi), fminf(fmaxf(a.w, 0.f), hi));
 }
 
+// tf.image.resize_images (bilinear, align_corners = False, legacy sampling src = dst * (in / out)): the one copy of its index arithmetic
+// and of its interpolation step.  resize_bilinear_kernel (dw_misc.hip) and the kernels that form an upsampled tensor in registers instead
+// of reading it (dw3x3_s1_roll_up, gemm_conv_kernel's UP epilogue) call these, x first inside a source row and then y: the same bits.
+// The fused multiply-adds are written out: the compiler formed them in resize_bilinear_kernel from `f - i0` and `a + (b - a) * l`
+// (the weight is o * s - i0 with the product unrounded; the index is the floor of the rounded product), and whether it forms them
+// must not depend on the kernel the expression is inlined into.
+__device__ __forceinline__ void resize_src(int o, float s, int n_in, int& i0, int& i1, float& l) {
+    const float f = (float)o * s;
+    i0 = (int)floorf(f);
+    i1 = min(i0 + 1, n_in - 1);
+    l = fmaf(s, (float)o, -(float)i0);
+}
+__device__ __forceinline__ float lerpf(float a, float b, float l) { return fmaf(l, b - a, a); }
+__device__ __forceinline__ float4 lerp4(float4 a, float4 b, float l) {
+    return make_float4(lerpf(a.x, b.x, l), lerpf(a.y, b.y, l), lerpf(a.z, b.z, l), lerpf(a.w, b.w, l));
+}
+
 // dy masked by the activation that followed, z = the activation's input
 __device__ __forceinline__ float grad_mask(float dy, float z, int mask) {
     if (mask == 1) return (z > 0.f && z < 6.f) ? dy : 0.f;   // tf.nn.relu6 (Relu6Grad: 0 < z < 6)

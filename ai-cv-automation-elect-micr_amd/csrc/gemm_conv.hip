@@ -31,8 +31,11 @@
 // stores and residual loads are 16 B per lane, a whole pixel's channel run per 32 lanes.
 // Block index -> tile mapping is XCD-aware: the N-tiles of one M-tile (which re-read the same
 // activation rows) get consecutive indices inside one XCD's share of the grid.
+#include <type_traits>
+
 #include "mfma_common.hpp"
 #include "bn_chain_dev.hpp"
+#include "f4_math.hpp"
 
 namespace {
 
@@ -65,9 +68,22 @@ struct GemmParams {
                                           // ((mt / tpi) * nph + ph) * tpi + mt % tpi  (tpi = tiles per image, or all tiles; nph = 0: slab = mt)
 };
 
+// UP epilogue: the per-channel shift is replaced by a per-pixel one, the bilinear upsampling of a low-resolution tensor `up` [B,Hu,Wu,N]
+// to the output's Hc x Wc pixels, sampled with resize_bilinear_kernel's arithmetic (f4_math.hpp) and never written.  Its arguments ride
+// behind GemmParams in the UP instances' own parameter type: the other instances keep their kernel arguments, and their instructions.
+struct UpSample {
+    const float* up;
+    int ldup, Hu, Wu;
+    float sy, sx;   // (float)Hu / Hc, (float)Wu / Wc
+};
+struct GemmUpParams : GemmParams {
+    UpSample u;
+};
+
 // Block tile 128 x BN (BN = 128: 2x2 waves of 64x64; BN = 64: 4x1 waves of 32x64), K step 64.
-template <int BN, int PASSES, bool FLAT>
-__global__ __launch_bounds__(256, 2) void gemm_conv_kernel(const GemmParams p) {
+template <int BN, int PASSES, bool FLAT, bool UP = false>
+__global__ __launch_bounds__(256, 2) void gemm_conv_kernel(const std::conditional_t<UP, GemmUpParams, GemmParams> p) {
+    static_assert(!UP || FLAT, "the upsampled shift is a mode of the plain pointwise instance");
     constexpr int BM = 128, BK = 64;
     constexpr int LDK = BK + 8;                      // bf16 elements per LDS row: 144 B, conflict-free b128 reads
     constexpr int WM = BN == 128 ? 2 : 4, WN = 4 / WM;
@@ -261,6 +277,16 @@ __global__ __launch_bounds__(256, 2) void gemm_conv_kernel(const GemmParams p) {
                 const int r = wm * (BM / WM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
                 stage[r][wn * (BN / WN) + j * 32 + fr] = acc[i][j][e];
             }
+    if constexpr (UP) {
+        // (image, oy, ox) of each row, one division chain per row instead of one per (row, thread): rowA is free after the K loop
+        if (tid < BM) {
+            const long long pix = rowP[tid];
+            if (pix >= 0) {
+                const long long t = pix / p.Wc;
+                rowA[tid] = ((t / p.Hc) << 40) | ((t % p.Hc) << 20) | (pix % p.Wc);   // Hc, Wc <= 2^20 (checked at the entry)
+            }
+        }
+    }
     __syncthreads();
     constexpr int C4 = BN / 4;            // float4 chunks per staged row
     constexpr int ROWS_PER_PASS = 256 / C4;
@@ -271,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void gemm_conv_kernel(const GemmParams p) {
     static_assert(ROWS_PER_PASS * BN * 2 * 8 <= TILE_BYTES && 2 * BN <= 256, "the statistics reduction reuses the tile memory");
     if (n < p.N) {                        // N % 4 == 0: a chunk is all inside or all outside
         const f32x4 s1 = *reinterpret_cast<const f32x4*>(p.scale1 + n);
-        const f32x4 t1 = *reinterpret_cast<const f32x4*>(p.shift1 + n);
+        const f32x4 t1 = UP ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(p.shift1 + n);   // UP: sampled per pixel below
         f32x4 s2 = {1.f, 1.f, 1.f, 1.f}, t2 = {0.f, 0.f, 0.f, 0.f};
         if (p.scale2) {
             s2 = *reinterpret_cast<const f32x4*>(p.scale2 + n);
@@ -294,7 +320,47 @@ __global__ __launch_bounds__(256, 2) void gemm_conv_kernel(const GemmParams p) {
             }
             return v;
         };
-        if (p.res) {
+        if constexpr (UP) {
+            // y = act(fmaf(acc, scale1, up(pixel, n))): no second affine, no residual (refused at the entry).  Four rows at a time: their
+            // 16 taps (16 bytes each, this thread's channel quad) are requested before the first is used; a row beyond M reads zeros.
+            constexpr int G = 4;
+            static_assert(NROWS % G == 0, "rows per thread come in groups of four");
+            const UpSample& u = p.u;
+#pragma unroll 1
+            for (int g = 0; g < NROWS; g += G) {
+                f32x4 tp[G][4];
+                float ly[G], lx[G];
+                long long pixv[G];
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    const int r = er + (g + k) * ROWS_PER_PASS;
+                    const long long pix = rowP[r], q = rowA[r];
+                    pixv[k] = pix;
+                    int y0, y1, x0, x1;
+                    resize_src((int)((q >> 20) & 0xfffff), u.sy, u.Hu, y0, y1, ly[k]);
+                    resize_src((int)(q & 0xfffff), u.sx, u.Wu, x0, x1, lx[k]);
+                    const float* ub = u.up + ((q >> 40) * u.Hu) * (long)u.Wu * u.ldup + n;
+                    const bool ok = pix >= 0;
+                    tp[k][0] = *reinterpret_cast<const f32x4*>(ok ? ub + ((long)y0 * u.Wu + x0) * u.ldup : g_zero16);
+                    tp[k][1] = *reinterpret_cast<const f32x4*>(ok ? ub + ((long)y0 * u.Wu + x1) * u.ldup : g_zero16);
+                    tp[k][2] = *reinterpret_cast<const f32x4*>(ok ? ub + ((long)y1 * u.Wu + x0) * u.ldup : g_zero16);
+                    tp[k][3] = *reinterpret_cast<const f32x4*>(ok ? ub + ((long)y1 * u.Wu + x1) * u.ldup : g_zero16);
+                }
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    if (pixv[k] < 0) continue;
+                    const int r = er + (g + k) * ROWS_PER_PASS;
+                    f32x4 v = *reinterpret_cast<const f32x4*>(&stage[r][ec]);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float sh = lerpf(lerpf(tp[k][0][c], tp[k][1][c], lx[k]), lerpf(tp[k][2][c], tp[k][3][c], lx[k]), ly[k]);
+                        const float a = fmaf(v[c], s1[c], sh);
+                        v[c] = fminf(fmaxf(fmaxf(a, lo), slope * a), hi);
+                    }
+                    *reinterpret_cast<f32x4*>(outp + pixv[k] * p.ldc + n) = v;
+                }
+            }
+        } else if (p.res) {
             // all residual values of this thread's rows are requested before the first one is used
             f32x4 rv[NROWS];
 #pragma unroll
@@ -356,12 +422,20 @@ __global__ __launch_bounds__(256, 2) void gemm_conv_kernel(const GemmParams p) {
 }
 
 template <int BN>
-int launch(const GemmParams& p0, int passes, hipStream_t st) {
+int launch(const GemmParams& p0, int passes, hipStream_t st, const UpSample* up = nullptr) {
     GemmParams p = p0;
     p.n_mtiles = (int)((p.M + 127) / 128);
     p.n_ntiles = (p.N + BN - 1) / BN;
     const long nblk = (long)p.n_mtiles * p.n_ntiles;
     if (nblk <= 0 || nblk > 0x7fffffffL) return emd::fail(EMD_E_UNSUPPORTED, "gemm_conv: grid too large");
+    if (up) {
+        GemmUpParams pu;
+        static_cast<GemmParams&>(pu) = p;
+        pu.u = *up;
+        if (passes == 3) hipLaunchKernelGGL((gemm_conv_kernel<BN, 3, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, pu);
+        else hipLaunchKernelGGL((gemm_conv_kernel<BN, 1, true, true>), dim3((unsigned)nblk), dim3(256), 0, st, pu);
+        return emd::check_launch("gemm_conv_kernel (upsampled shift)");
+    }
     if (passes == 3)
         if (p.flat) hipLaunchKernelGGL((gemm_conv_kernel<BN, 3, true>), dim3((unsigned)nblk), dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_conv_kernel<BN, 3, false>), dim3((unsigned)nblk), dim3(256), 0, st, p);
@@ -371,13 +445,13 @@ int launch(const GemmParams& p0, int passes, hipStream_t st) {
     return emd::check_launch("gemm_conv_kernel");
 }
 
-int dispatch(const GemmParams& p, int passes, hipStream_t st) {
-    if (p.N <= 64) return launch<64>(p, passes, st);
+int dispatch(const GemmParams& p, int passes, hipStream_t st, const UpSample* up = nullptr) {
+    if (p.N <= 64) return launch<64>(p, passes, st, up);
     // a grid that cannot even give every CU one 128x128 tile (a single 32x32 training tower: 8 x 6 tiles) runs as
     // 128x64 tiles: twice the workgroups, each latency-bound pass over K shorter
     const long tiles128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
-    if (tiles128 < 192) return launch<64>(p, passes, st);
-    return launch<128>(p, passes, st);
+    if (tiles128 < 192) return launch<64>(p, passes, st, up);
+    return launch<128>(p, passes, st, up);
 }
 
 inline uint16_t f32_to_bf16_rne(float f) {
@@ -479,6 +553,34 @@ extern "C" int emd_conv1x1_f32(const float* x, int ldx, const uint16_t* whi, con
     p.Hg = Ho; p.Wg = Wo; p.Ha = H; p.Wa = W; p.Hc = Ho; p.Wc = Wo; p.sa = stride; p.sc = 1; p.py = p.px = 0;
     set_taps(p, 1, nullptr, nullptr);
     return dispatch(p, precision, static_cast<hipStream_t>(stream));
+}
+
+// emd_conv1x1_f32 (stride 1) whose shift is a per-pixel value: y = act(fmaf(x . W, scale1, U)), U = emd_resize_bilinear_f32 of
+// up [B,Hu,Wu,Cout] to [H, W], sampled in the epilogue (the resize kernel's arithmetic on the same taps: U carries its bits) and never
+// written.  For a 1x1 conv over concat(resize(a), x): the interpolation weights sum to 1, so resize commutes with the conv and the affine
+// -- up = scale1 * (a . W_a) + shift1 at a's resolution (graph D's residual2_d, machine_learning/denoiser.py:350-356).  No second
+// affine and no residual in this mode.
+extern "C" int emd_conv1x1_up_f32(const float* x, int ldx, const uint16_t* whi, const uint16_t* wlo, const float* scale1, const float* up,
+                                  int ldup, int Hu, int Wu, const float* scale2, const float* shift2, const float* res, int ldres, float* y,
+                                  int ldy, int B, int H, int W, int Cin, int Cout, int act, int precision, emd_stream_t stream) {
+    EMD_REQUIRE(!scale2 && !shift2 && !res, EMD_E_UNSUPPORTED, "emd_conv1x1_up_f32: no second affine and no residual with an upsampled shift");
+    int rc = common_checks("emd_conv1x1_up_f32", x, whi, wlo, scale1, up, nullptr, nullptr, nullptr, y, Cin, Cout, ldx, ldy, ldres, precision);
+    if (rc != EMD_OK) return rc;
+    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1 && Hu >= 1 && Wu >= 1, EMD_E_INVALID, "emd_conv1x1_up_f32: bad shape");
+    EMD_REQUIRE(ldup % 4 == 0 && ldup >= Cout, EMD_E_ALIGN, "emd_conv1x1_up_f32: ldup must be a multiple of 4, >= Cout");
+    EMD_REQUIRE(H <= (1 << 20) && W <= (1 << 20) && B < (1 << 23), EMD_E_UNSUPPORTED, "emd_conv1x1_up_f32: H, W <= 2^20, B < 2^23");
+    if (B == 0) return EMD_OK;
+    GemmParams p{};
+    p.A = x; p.Whi = whi; p.Wlo = wlo; p.C = y;
+    p.scale1 = scale1;
+    p.N = Cout; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.ntaps = 1;
+    p.lda = ldx; p.ldc = ldy; p.act = act;
+    p.M = (long)B * H * W;
+    p.flat = 1;
+    p.Hg = H; p.Wg = W; p.Ha = H; p.Wa = W; p.Hc = H; p.Wc = W; p.sa = 1; p.sc = 1;
+    set_taps(p, 1, nullptr, nullptr);
+    const UpSample u{up, ldup, Hu, Wu, (float)Hu / (float)H, (float)Wu / (float)W};
+    return dispatch(p, precision, static_cast<hipStream_t>(stream), &u);
 }
 
 // The convolutions of a TRAINING forward pass (misc_py/denoiser-multi-gpu.py:200-540 with phase = True: every conv is followed by a batch

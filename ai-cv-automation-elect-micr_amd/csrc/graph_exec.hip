@@ -120,6 +120,7 @@ struct LayerParams {
     LayerDecl d;
     float* dw = nullptr;                          // [9][Cin]
     Packed pw;                                    // pointwise / 1x1 / 3x3 conv weights
+    Packed pw_a, pw_b;                            // residual2_d: the rows of pw that meet up(aspp) / cnn1_strided
     Packed phase[4];                              // transposed conv
     float *scale = nullptr, *shift = nullptr;     // folded affine(s)
     float *scale2 = nullptr, *shift2 = nullptr;   // the extra batch norm of the ASPP rate branches
@@ -234,6 +235,17 @@ struct Run {
         return cout >= 128 && ktot >= 512 && ((npix + 255) / 256) * ((cout + 127) / 128) >= 192;
     }
     static bool deconv_fused_ok(int B, int H, int W, int cin, int cout) { return emd_deconv3x3s2_fused_preferred(B, H, W, cin, cout) != 0; }
+    // The Python engine's _up_fused rule: the 4x upsampling of the ASPP output ([B,Hi,Hi,AOUT] -> H x H) is formed inside residual2_d and
+    // deconv2_a wherever sep() would run deconv2_a as depthwise -> split32 GEMM and the depthwise instance covers the shape.  Never a
+    // rule of B (residual2_d sums in another order on this route; image b of a batch == the image alone): the split32 GEMM is asked
+    // about a fixed pixel count, as conv1x1() asks it
+    bool up_fused_ok(int Hi, int H) const {
+        const LayerParams& p = g->P["deconv2_a"];
+        const LayerDecl& d = p.d;
+        return emd::g_knobs.up_fused && !p.scale2 && d.stride == 1 && d.rate == 1 && d.cin == AOUT + F1 &&
+               !emd_sep3x3_fused_supported(H, H, d.cin, d.cout, 1, 1) && emd_conv1x1_split32_supported(1L << 20, d.cin, d.cout) &&
+               emd_dw3x3_up_split32_supported(Hi, Hi, H, H, AOUT, d.cin);
+    }
 
     // strided_conv_block (denoiser.py:110-136); out: optional destination (a concat slice); split_out: write a split32 tensor
     T4 sep(const std::string& key, const T4& x, const T4* out_opt, const T4* res, void** split_out = nullptr) {
@@ -515,9 +527,15 @@ struct Run {
         T4 residual1 = conv1x1("residual1", cnn0_strided, nullptr);
         T4 cnn1 = sep("cnn1", cnn0_strided, nullptr, nullptr);
         T4 cnn1_last = sep("cnn1_last", cnn1, nullptr, nullptr);
-        T4 concat2 = E(B, S4, S4, AOUT + F1);
-        T4 c2s = concat2.slice(AOUT, F1);
-        T4 cnn1_strided = sep("cnn1_strided", cnn1_last, &c2s, &residual1);
+        // cnn1_strided lives in its channel slice of concat2 (:353) -- unless the decoder forms concat2's other channels inside their
+        // consumers (up_fused_ok): then it is a tensor of its own and concat2 does not exist
+        const bool up_fused = up_fused_ok(S16, S4);
+        T4 concat2, c2s;
+        if (!up_fused) {
+            concat2 = E(B, S4, S4, AOUT + F1);
+            c2s = concat2.slice(AOUT, F1);
+        }
+        T4 cnn1_strided = sep("cnn1_strided", cnn1_last, up_fused ? nullptr : &c2s, &residual1);
         free(cnn1); free(cnn1_last); free(residual1);
         // encoder 2 (:282-294)
         T4 residual2 = conv1x1("residual2", cnn1_strided, nullptr);
@@ -582,11 +600,37 @@ struct Run {
         free(cat);
         ar->release(curs);
         // decoder (:350-384)
-        T4 c2a = concat2.slice(0, AOUT);
-        if (live()) call(emd_resize_bilinear_f32(aspp.ptr(), aspp.ld, c2a.ptr(), c2a.ld, B, S16, S16, S4, S4, AOUT, st));
-        free(aspp);
-        T4 residual2_d = conv1x1("residual2_d", concat2, nullptr);
-        T4 d2a = sep("deconv2_a", concat2, nullptr, nullptr);
+        T4 residual2_d, d2a;
+        if (up_fused) {
+            // concat2 = [up(aspp) | cnn1_strided] (:350-353) is never written: residual2_d = relu6(s (cnn1_strided . W_b) + up(P')) with
+            // P' = s (aspp . W_a) + t at 1/16 resolution (a 1x1 conv commutes with the bilinear upsampling), sampled in the GEMM's
+            // epilogue; deconv2_a's depthwise stage forms up(aspp) in registers.  The Python engine's launches, in its order.
+            const LayerParams &pr = P["residual2_d"], &pa = P["deconv2_a"];
+            const long M = (long)B * S4 * S4;
+            const int ldd = emd_split32_ld(AOUT + F1);
+            T4 pp = E(B, S16, S16, F2);
+            residual2_d = E(B, S4, S4, F2);
+            void* dsp = raw((size_t)M * ldd * 4);
+            d2a = E(B, S4, S4, F2);
+            if (live()) {
+                call(emd_conv1x1_f32(aspp.ptr(), aspp.ld, pr.pw_a.hi, pr.pw_a.lo, pr.scale, pr.shift, nullptr, nullptr, nullptr, 0, pp.ptr(), pp.ld,
+                                     B, S16, S16, AOUT, F2, 1, EMD_ACT_NONE, EMD_PREC_BF16X3, st));
+                call(emd_conv1x1_up_f32(cnn1_strided.ptr(), cnn1_strided.ld, pr.pw_b.hi, pr.pw_b.lo, pr.scale, pp.ptr(), pp.ld, S16, S16, nullptr,
+                                        nullptr, nullptr, 0, residual2_d.ptr(), residual2_d.ld, B, S4, S4, F1, F2, EMD_ACT_RELU6, EMD_PREC_BF16X3, st));
+                call(emd_dw3x3_up_split32_f32(aspp.ptr(), aspp.ld, S16, S16, AOUT, cnn1_strided.ptr(), cnn1_strided.ld, pa.dw, dsp, ldd, B, S4, S4,
+                                              AOUT + F1, st));
+                call(emd_conv1x1_split32_f32(dsp, ldd, pa.pw.hi, pa.pw.lo, pa.scale, pa.shift, nullptr, nullptr, nullptr, 0, d2a.ptr(), d2a.ld, M,
+                                             AOUT + F1, F2, EMD_ACT_RELU6, st));
+            }
+            ar->release(dsp);
+            free(pp); free(aspp); free(cnn1_strided);
+        } else {
+            T4 c2a = concat2.slice(0, AOUT);
+            if (live()) call(emd_resize_bilinear_f32(aspp.ptr(), aspp.ld, c2a.ptr(), c2a.ld, B, S16, S16, S4, S4, AOUT, st));
+            free(aspp);
+            residual2_d = conv1x1("residual2_d", concat2, nullptr);
+            d2a = sep("deconv2_a", concat2, nullptr, nullptr);
+        }
         const bool so2 = deconv_fused_ok(B, S4, S4, F2, F2) && S4 % 8 == 0 && S4 % 16 == 0;
         void* deconv2_s = nullptr;
         T4 deconv2 = sep("deconv2_b", d2a, nullptr, &residual2_d, so2 ? &deconv2_s : nullptr);
@@ -716,6 +760,8 @@ extern "C" int emd_graph_create(emd_graph** out, int variant, int n_vars, const 
                 ok = p.wfin != nullptr;
             } else {
                 ok = pack(g, wt, d.k * d.k, d.cin, d.cout, 0, &p.pw);
+                if (ok && d.key == "residual2_d")   // over [up(aspp) | cnn1_strided]: the two row blocks on their own (Run::forward, up_fused)
+                    ok = pack(g, wt, 1, AOUT, d.cout, 0, &p.pw_a) && pack(g, wt + (size_t)AOUT * d.cout, 1, d.cin - AOUT, d.cout, 0, &p.pw_b);
                 p.scale = upload_f(g, s);
                 p.shift = upload_f(g, t);
                 ok = ok && p.scale && p.shift;

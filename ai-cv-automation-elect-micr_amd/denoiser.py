@@ -312,6 +312,10 @@ class DenoiserEngine:
                 else:
                     p["pw"] = ops.PackedWeights(wt.reshape(L.k * L.k, L.cin, L.cout), False, device)
                     p["scale"], p["shift"] = d(s), d(t)
+                    if key == "residual2_d":   # over [up(aspp) | cnn1_strided]: the two row blocks on their own (the _up_fused route)
+                        wab = wt.reshape(1, L.cin, L.cout)
+                        p["pw_a"] = ops.PackedWeights(wab[:, :aspp_output], False, device)
+                        p["pw_b"] = ops.PackedWeights(wab[:, aspp_output:], False, device)
             elif L.kind == "deconv":
                 s, t = _fold(weights, L, weights[L.scope + "/" + L.bname])
                 p["phases"] = ops.pack_deconv(weights[L.scope + "/" + L.wname], device)
@@ -367,6 +371,22 @@ class DenoiserEngine:
         return bool(self.fuse_sep and self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_FOLD_FINAL", "1") != "0"
                     and L.stride == 1 and L.rate == 1 and self.layers["deconv_final"].cin == L.cout
                     and ops.sep_fused_supported(x, L.cout, L.stride, L.rate) and ops.sep_fused_fold_supported(x, L.cout))
+
+    def _up_fused(self, Hi, H):
+        """True where the 4x upsampling of the ASPP output (:350) is formed inside its two consumers instead of written into concat2
+        (emd_conv1x1_up_f32 for residual2_d, emd_dw3x3_up_split32_f32 for deconv2_a): wherever _sep would run deconv2_a as depthwise ->
+        split32 GEMM and the depthwise instance covers the shape -- a rule of the shape alone, never of the batch size: residual2_d sums
+        in another order on this route, and image b of a batch must equal the image alone.  So the split32 GEMM is asked about a fixed
+        pixel count, as _pw_split_ok asks it (emd_conv1x1_split32_supported ignores M today; the answer here must not follow B even if
+        that changes).  aspp is [B,Hi,Hi,aspp_output], cnn1_strided [B,H,H,features1]."""
+        L = self.layers["deconv2_a"]
+        Cc = aspp_output + features1
+        return bool(self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_UP_FUSED", "1") != "0"
+                    and L.stride == 1 and L.rate == 1 and L.cin == Cc and "scale2" not in self.P["deconv2_a"]
+                    and not (self.fuse_sep and _lib.load().emd_sep3x3_fused_supported(H, H, Cc, L.cout, 1, 1))
+                    and not (self.fuse_sep and os.environ.get("EMD_D_SEPGEMM", "0") == "1")
+                    and ops.conv1x1_split32_supported(1 << 20, Cc, L.cout)
+                    and ops.dw3x3_up_split32_supported(Hi, Hi, H, H, aspp_output, Cc))
 
     def _sep_gemm_ok(self, x, L):
         return (self.fuse_sep and self.precision == ops.PREC_BF16X3 and os.environ.get("EMD_D_SEPGEMM", "0") == "1"   # opt-in: measured slower than the two-kernel route (DESIGN.md 3.2c)
@@ -573,8 +593,10 @@ class DenoiserEngine:
         residual1 = self._conv1x1("residual1", cnn0_strided)
         cnn1 = self._sep("cnn1", cnn0_strided)
         cnn1_last = self._sep("cnn1_last", cnn1)
-        concat2 = E(S4, aspp_output + f1)
-        cnn1_strided = self._sep("cnn1_strided", cnn1_last, out=concat2.slice(aspp_output, f1), res=residual1)
+        # ... unless the decoder forms the other 256 channels of concat2 inside its consumers (_up_fused): then it is a tensor of its own
+        up_fused = self._up_fused(S16, S4)
+        concat2 = None if up_fused else E(S4, aspp_output + f1)
+        cnn1_strided = self._sep("cnn1_strided", cnn1_last, out=None if up_fused else concat2.slice(aspp_output, f1), res=residual1)
         del cnn1, cnn1_last, residual1
         # encoder 2 (:282-294)
         residual2 = self._conv1x1("residual2", cnn1_strided)
@@ -623,9 +645,19 @@ class DenoiserEngine:
         if stage is not None and not stage_first:
             stage("mid")
         # decoder (:350-384)
-        ops.resize_bilinear(aspp, concat2.slice(0, aspp_output))            # deconv3 (:350)
-        residual2_d = self._conv1x1("residual2_d", concat2)
-        t = self._sep("deconv2_a", concat2)
+        if up_fused:
+            # concat2 = [up(aspp) | cnn1_strided] (:350-353) is never written.  A 1x1 conv commutes with the bilinear upsampling (its weights
+            # sum to 1): relu6(s (concat2 . W) + t) = relu6(s (cnn1_strided . W_b) + up(P')) with P' = s (aspp . W_a) + t at 1/16
+            # resolution, sampled in residual2_d's epilogue; deconv2_a's depthwise stage forms up(aspp) in registers (same bits)
+            pr, pa = P["residual2_d"], P["deconv2_a"]
+            pp = ops.conv1x1(aspp, pr["pw_a"], pr["scale"], pr["shift"], E(S16, f2), act=False, precision=self.precision)
+            residual2_d = ops.conv1x1(cnn1_strided, pr["pw_b"], pr["scale"], None, E(S4, f2), act=True, precision=self.precision, up=pp)
+            t = ops.sep_split32(cnn1_strided, pa["dw"], pa["pw"], pa["scale"], pa["shift"], E(S4, f2), up=aspp)
+            del pp
+        else:
+            ops.resize_bilinear(aspp, concat2.slice(0, aspp_output))            # deconv3 (:350)
+            residual2_d = self._conv1x1("residual2_d", concat2)
+            t = self._sep("deconv2_a", concat2)
         deconv2 = self._sep("deconv2_b", t, res=residual2_d, out=self._split_out(B, S4, S4, f2))
         del aspp, concat2, cnn1_strided, residual2_d, t
         self._deconv("deconv2to1", deconv2, concat1.slice(0, f2))

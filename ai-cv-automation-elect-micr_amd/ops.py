@@ -102,12 +102,21 @@ class PackedWeights:
 
 
 def conv1x1(x: Act, w: PackedWeights, scale1, shift1, out: Act, stride=1, act=True, scale2=None, shift2=None,
-            res: Act | None = None, precision=PREC_BF16X3, stream=None):
+            res: Act | None = None, precision=PREC_BF16X3, stream=None, up: Act | None = None):
+    """up: a low-resolution tensor [B,Hi,Wi,Cout] whose bilinear upsampling (resize_bilinear's expression) takes the place of shift1
+    (emd_conv1x1_up_f32; stride 1, no second affine, no residual: the library refuses them)."""
     lib = _lib.load()
     Ho, Wo = -(-x.H // stride), -(-x.W // stride)
     assert (out.B, out.H, out.W, out.C) == (x.B, Ho, Wo, w.cout) and w.cin == x.C and w.taps == 1
     if res is not None:
         assert (res.B, res.H, res.W, res.C) == (out.B, out.H, out.W, out.C)
+    if up is not None:
+        assert stride == 1 and shift1 is None and (up.B, up.C) == (out.B, out.C)
+        rc = lib.emd_conv1x1_up_f32(x.ptr, x.ld, _p(w.hi), _p(w.lo), _p(scale1), up.ptr, up.ld, up.H, up.W, _p(scale2), _p(shift2),
+                                    res.ptr if res is not None else C.c_void_p(0), res.ld if res is not None else 0,
+                                    out.ptr, out.ld, x.B, x.H, x.W, x.C, w.cout, _act(act), precision, _lib.stream_ptr(stream))
+        _lib.check(rc, "emd_conv1x1_up_f32")
+        return out
     rc = lib.emd_conv1x1_f32(x.ptr, x.ld, _p(w.hi), _p(w.lo), _p(scale1), _p(shift1), _p(scale2), _p(shift2),
                              res.ptr if res is not None else C.c_void_p(0), res.ld if res is not None else 0,
                              out.ptr, out.ld, x.B, x.H, x.W, x.C, w.cout, stride, _act(act), precision,
@@ -459,8 +468,20 @@ def to_split32(x: Act, out: SplitAct | None = None, stream=None):
     return out
 
 
-def dw3x3_split32(x: Act, w_dev, out: SplitAct, stride=1, rate=1, stream=None, pre=None):
+def dw3x3_up_split32_supported(Hi: int, Wi: int, Ho: int, Wo: int, cup: int, c: int) -> bool:
+    return bool(_lib.load().emd_dw3x3_up_split32_supported(Hi, Wi, Ho, Wo, cup, c))
+
+
+def dw3x3_split32(x: Act, w_dev, out: SplitAct, stride=1, rate=1, stream=None, pre=None, up: Act | None = None):
+    """up: a low-resolution tensor [B,Hi,Wi,Cup]: the depthwise input is concat(resize_bilinear(up), x) along the channels, the upsampled
+    part formed in registers (emd_dw3x3_up_split32_f32; stride 1, rate 1; w_dev [9, Cup + C]).  Bits of the two-launch route."""
     lib = _lib.load()
+    if up is not None:
+        assert pre is None and stride == 1 and rate == 1 and out.C == up.C + x.C and (out.B, out.H, out.W) == (x.B, x.H, x.W) and up.B == x.B
+        rc = lib.emd_dw3x3_up_split32_f32(up.ptr, up.ld, up.H, up.W, up.C, x.ptr, x.ld, _p(w_dev), out.ptr, out.ld, x.B, x.H, x.W, out.C,
+                                          _lib.stream_ptr(stream))
+        _lib.check(rc, "emd_dw3x3_up_split32_f32")
+        return out
     assert out.C == x.C and out.B == x.B and (out.H, out.W) == (-(-x.H // stride), -(-x.W // stride))
     if pre is not None:
         rc = lib.emd_dw3x3_pre_split32_f32(x.ptr, x.ld, _p(pre[0]), _p(pre[1]), _p(w_dev), out.ptr, out.ld, x.B, x.H, x.W, x.C,
@@ -481,15 +502,16 @@ def dw3x3_reflect_split32(x: Act, w_dev, out: SplitAct, stride=1, stream=None):
 
 
 def sep_split32(x: Act, dw_dev, w: PackedWeights, scale1, shift1, out: Act, stride=1, rate=1, act=True, scale2=None,
-                shift2=None, res: Act | None = None, reflect=False, stream=None, pre=None, stats=False, fold=None):
+                shift2=None, res: Act | None = None, reflect=False, stream=None, pre=None, stats=False, fold=None, up: Act | None = None):
     """Separable conv as depthwise (split32 output) -> LDS-DMA pointwise GEMM; the intermediate exists only in split form.
-    stats=True: (out, mean, var) with the batch statistics of the output from the GEMM epilogue."""
-    d = SplitAct(out.B, out.H, out.W, x.C, x.buf.device)
+    stats=True: (out, mean, var) with the batch statistics of the output from the GEMM epilogue.
+    up: the leading input channels are the bilinear upsampling of this low-resolution tensor (see dw3x3_split32)."""
+    d = SplitAct(out.B, out.H, out.W, x.C + (up.C if up is not None else 0), x.buf.device)
     if reflect:
-        assert pre is None
+        assert pre is None and up is None
         dw3x3_reflect_split32(x, dw_dev, d, stride=stride, stream=stream)
     else:
-        dw3x3_split32(x, dw_dev, d, stride=stride, rate=rate, stream=stream, pre=pre)
+        dw3x3_split32(x, dw_dev, d, stride=stride, rate=rate, stream=stream, pre=pre, up=up)
     return conv1x1_split32(d, w, scale1, shift1, out, act=act, scale2=scale2, shift2=shift2, res=res, stream=stream, stats=stats,
                            fold=fold)
 

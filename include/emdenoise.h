@@ -270,6 +270,13 @@ int emd_conv1x1_f32(const float* x, int ldx, const uint16_t* whi, const uint16_t
                     const float* scale1, const float* shift1, const float* scale2, const float* shift2,
                     const float* res, int ldres, float* y, int ldy, int B, int H, int W, int Cin,
                     int Cout, int stride, int act, int precision, emd_stream_t stream);
+/* emd_conv1x1_f32 (stride 1) with a per-pixel shift: y = act((x . W) * scale1 + U), U = emd_resize_bilinear_f32 of up [B,Hu,Wu,Cout]
+ * (pixel stride ldup) to [H,W], sampled in the epilogue with the resize kernel's arithmetic and never written.  For a 1x1 conv over
+ * concat(resize(a), x): up = (a . W_a) * scale1 + shift1 at a's resolution, W = W_x (bilinear weights sum to 1).  scale2 / shift2 / res
+ * must be NULL: EMD_E_UNSUPPORTED otherwise. */
+int emd_conv1x1_up_f32(const float* x, int ldx, const uint16_t* whi, const uint16_t* wlo, const float* scale1, const float* up,
+                       int ldup, int Hu, int Wu, const float* scale2, const float* shift2, const float* res, int ldres, float* y,
+                       int ldy, int B, int H, int W, int Cin, int Cout, int act, int precision, emd_stream_t stream);
 
 /* Dense 3x3 convolution on the matrix cores (9-tap implicit GEMM), TF SAME, stride 1 or 2, or stride 1 with
  * dilation `rate` <= 31.
@@ -373,6 +380,13 @@ int emd_dw3x3_split32_f32(const float* x, int ldx, const float* w, void* y, int 
                           int stride, int rate, emd_stream_t stream);
 int emd_dw3x3_reflect_split32_f32(const float* x, int ldx, const float* w, void* y, int ldy, int B, int H, int W, int C,
                                   int stride, emd_stream_t stream); /* emd_dw3x3_reflect_f32 (graph G) with split32 output */
+/* emd_dw3x3_split32_f32 (stride 1, rate 1) over concat(emd_resize_bilinear_f32(lo [B,Hi,Wi,Cup] -> [H,W]), x [B,H,W,C-Cup]) along the
+ * channels, without that tensor: the upsampled channels are formed in registers from lo (graph D's deconv2_a,
+ * machine_learning/denoiser.py:350-356).  w [3][3][C], y split32 [B,H,W,C].  Bit-identical to the two launches over the concat.
+ * Supported (emd_dw3x3_up_split32_supported; EMD_E_UNSUPPORTED otherwise): H >= Hi, W >= Wi, Cup a multiple of 64 and below C. */
+int emd_dw3x3_up_split32_supported(int Hi, int Wi, int H, int W, int Cup, int C);
+int emd_dw3x3_up_split32_f32(const float* lo, int ldlo, int Hi, int Wi, int Cup, const float* x, int ldx, const float* w, void* y,
+                             int ldy, int B, int H, int W, int C, emd_stream_t stream);
 int emd_conv1x1_split32_supported(long M, int Cin, int Cout);
 /* emd_conv1x1_split32_f32 (no second affine, no residual) that also returns the per-channel batch mean and BIASED variance
  * of its output y -- what emd_bn_stats_f32 computes in a second pass over y (the batch-statistics norms that follow the

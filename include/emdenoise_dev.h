@@ -37,6 +37,9 @@
  *   exitwave_composed (0)  emd_exitwave_reconstruct_f64 at pad_periods == 0: 1 = the iteration composed from the launches of
  *                       emd_propagate_f64 (the path of pad_periods > 0) instead of the two-launch frequency-domain iteration; differences
  *                       at rounding level.  emd_exitwave_workspace_bytes follows it: set it before asking for the size
+ *   up_fused (1)        graph D's native executor: the 4x upsampling of the ASPP output is formed inside its two consumers
+ *                       (emd_conv1x1_up_f32, emd_dw3x3_up_split32_f32) instead of written into the concat buffer; 0 = the resize launch
+ *                       (residual2_d's sum is associated differently: rounding-level differences)
  *   resize_generic (0)  emd_resize_f32: 1 = the instance whose one inner loop serves every form, instead of the loops for the fixed
  *                       forms (at most four taps) and for runs (same bits; the A/B of tools/resample_bench.py)
  */
