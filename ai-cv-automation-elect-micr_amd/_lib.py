@@ -469,6 +469,21 @@ SIGNATURES = {
     # x image_stride row_stride B H W boxes_dev y h w interpolation stream
     "emd_resize_f32": (C.c_int, [_c_float_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, _c_float_p, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p]),
+    # ---- autofocus: Laplacian moments, histogram entropy, spline minimum (csrc/focus.hip)
+    # x B H W ksize y stream
+    "emd_laplacian_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "emd_laplacian_moments_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x B H W ksize rectify out workspace ws_bytes stream
+    "emd_laplacian_moments_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
+    "emd_histogram01_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # x B H W bins normalize counts workspace ws_bytes stream
+    "emd_histogram01_i64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    # counts B bins eps entropy stream
+    "emd_hist_entropy_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    # z scores B N interp_factor zbest curve index stream
+    "emd_spline_argmin_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # ---- the 2-D FFT and the radial frequency profile (csrc/fft.hip)
     "emd_radial_bins": (C.c_int, [C.c_int]),
     "emd_rfft2_workspace_bytes": (C.c_size_t, [C.c_int] * 2),

@@ -1536,6 +1536,55 @@ int emd_resize_f32(const float* x, long image_stride, int row_stride, int B, int
                    int interpolation, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Autofocus (csrc/focus.hip): the arithmetic of em_env/fresnel_env.py:163-179 (fresnel_quantifier), :188-208
+ * (get_optimal_z) and misc_py/entropy.py:36-53 (image_entropy).  OpenCV is not used: the Laplacian is restated from its rules, not
+ * run against OpenCV (its own summation order is not known here).  Images are float32 [B,H,W], contiguous.
+ *
+ * Laplacian: cv2.Laplacian(x, CV_32F, ksize) with BORDER_REFLECT_101 (index -1 -> 1, n -> n - 2), scale 1, delta 0, in float32, every
+ *   operation rounding on its own, in this order (u, d, l, r the four neighbours, ul .. dr the diagonal ones, c the centre):
+ *     ksize 1  [0 1 0; 1 -4 1; 0 1 0]:   ((u + d) + (l + r)) - 4 c
+ *     ksize 3  [2 0 2; 0 -8 0; 2 0 2]:   2 ((ul + ur) + (dl + dr)) - 8 c
+ *   2 <= H, W <= 32768.  One launch; y may not overlap x.
+ * Moments: out [B][EMD_NFOCUS] doubles of the Laplacian L above (never written to memory):
+ *     0  mean_L = sum L / (H W)            1  n = #S, S = {L : (double)L >= mean_L} with rectify, every L without
+ *     2  mean_S = sum S / n                3  m2 = sum (s - mean_S)^2 / n         4  m4 = sum (s - mean_S)^4 / n
+ *     5  m4 / (m2 m2) - 3: scipy.stats.kurtosis with its defaults (Fisher, biased), the reference's fresnel_quantifier
+ *   Two-pass in double, fixed order: three reads of x with rectify (mean_L; n and mean_S; the moments), two without.  Every term
+ *   ((s - mean_S), its square, the square's square) is rounded to double on its own; the four sums are carried as pairs hi + lo of
+ *   doubles (two-sum) and rounded once at the end, so each is the exactly rounded sum of its terms (math.fsum's) but for ties within
+ *   about n 2^-104, and the cancellation of column 5 amplifies no summation error.  L must be finite.  A constant image has L = 0:
+ *   m2 = m4 = 0, column 5 NaN, as scipy.  Deviation: the reference's threshold is numpy's float32 pairwise mean of L; here it is the
+ *   double mean.
+ * Histogram: numpy.histogram(x, bins, range=(0, 1)) as int64 [B][bins], bins a power of two 2..4096: bin floor(x bins) for
+ *   0 <= x < 1, x == 1 in the last bin, everything else (NaN included) dropped; the product is exact, so no rounding case exists.
+ *   normalize == 1 bins t = 0.15 (x - mean) / std + 0.5 instead (entropy.py:48-49), mean and the population std the image's own,
+ *   two-pass in double; t = ((0.15 (x - mean)) / std) + 0.5 in double, each operation rounding on its own (deviation: the reference
+ *   evaluates t in float32).  A constant image has std = 0: nothing is counted.  Integer LDS atomics per workgroup, integer global
+ *   adds (exact, so their order does not matter); counts is zeroed by a memset node first.  1 <= H, W <= 32768.  The workspace is
+ *   needed with normalize only (emd_histogram01_workspace_bytes is 0 otherwise, and workspace may be NULL).
+ * Entropy: scipy.stats.entropy(counts + eps, base=2) per row: p = (c + eps) / sum (c + eps); (sum -p log p) / log 2, fixed order.
+ * Spline: z [N] doubles, strictly increasing (not checked: device data), scores [B][N], 4 <= N <= 256, 1 <= interp_factor <= 4096.
+ *   The interpolating cubic spline with not-a-knot end conditions (scipy's InterpolatedUnivariateSpline(z, s), k = 3) is evaluated on
+ *   numpy.linspace(z[0], z[N-1], G), G = interp_factor N: grid[i] = (i * step) + z[0] with two roundings, step = (z[N-1] - z[0]) /
+ *   (G - 1), grid[G-1] = z[N-1] exactly.  index[b] = the first i with the smallest value (numpy.argmin; values must be finite),
+ *   zbest[b] = grid[index[b]], curve[b][i] the values; curve and index may be NULL.  One workgroup per series.
+ *
+ * No floating-point atomics, no host synchronisation, launches (and the histogram's memset) only: capturable, bitwise reproducible, and
+ * an image's results do not depend on B.  Workspaces are the caller's and 16-byte aligned; outputs and workspaces overlap nothing.
+ * 0 <= B <= 65535 (B == 0 is a no-op). */
+#define EMD_NFOCUS 6
+int emd_laplacian_f32(const float* x, int B, int H, int W, int ksize, float* y, emd_stream_t stream);
+size_t emd_laplacian_moments_workspace_bytes(int B, int H, int W);
+int emd_laplacian_moments_f64(const float* x, int B, int H, int W, int ksize, int rectify, double* out, void* workspace,
+                              size_t workspace_bytes, emd_stream_t stream);
+size_t emd_histogram01_workspace_bytes(int B, int H, int W, int normalize);
+int emd_histogram01_i64(const float* x, int B, int H, int W, int bins, int normalize, int64_t* counts, void* workspace,
+                        size_t workspace_bytes, emd_stream_t stream);
+int emd_hist_entropy_f64(const int64_t* counts, int B, int bins, double eps, double* entropy, emd_stream_t stream);
+int emd_spline_argmin_f64(const double* z, const double* scores, int B, int N, int interp_factor, double* zbest, double* curve,
+                          int64_t* index, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
