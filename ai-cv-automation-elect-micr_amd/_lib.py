@@ -484,6 +484,17 @@ SIGNATURES = {
     "emd_hist_entropy_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
     # z scores B N interp_factor zbest curve index stream
     "emd_spline_argmin_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- dose series: integer CDF, inverse-CDF electron counts, min-max rescale (csrc/dose.hip)
+    "emd_dose_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x B H W cdf status workspace ws_bytes stream
+    "emd_dose_cdf_i64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # cdf B H W seed first_image bounds_host L planes stream
+    "emd_dose_draw_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_int64), C.c_int,
+                                    C.c_void_p, C.c_void_p]),
+    # planes B L H W minmax stream
+    "emd_dose_cumulate_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # planes minmax B L H W mode out stream
+    "emd_dose_rescale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # ---- the 2-D FFT and the radial frequency profile (csrc/fft.hip)
     "emd_radial_bins": (C.c_int, [C.c_int]),
     "emd_rfft2_workspace_bytes": (C.c_size_t, [C.c_int] * 2),

@@ -1585,6 +1585,62 @@ int emd_spline_argmin_f64(const double* z, const double* scores, int B, int N, i
                           int64_t* index, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dose series (csrc/dose.hip): the arithmetic of misc_py/lq_img_gen-backup.py:6-91 (lq_chunks_gen, record_lq,
+ * lq_img_gen) -- a micrograph as an unnormalised probability density, a fixed number of electrons thrown at it through its
+ * cumulative sum -- in integers, so that every output is exact.  Images are float32 [B,H,W], contiguous; n = H W.
+ *
+ * Weights: a pixel that is not finite or <= 0 weighs 0; m = the largest remaining pixel;
+ *     q[i] = rint(double(x[i]) / double(m) * 2^32)     (IEEE double division and multiply, round half to even; 0 .. 2^32)
+ *   status[b] (may be NULL): EMD_DOSE_EMPTY when no pixel is positive (every q is 0 and every count stays 0), EMD_DOSE_SANITIZED when
+ *   a pixel was zeroed for being negative, infinite or NaN (-0 is a zero).  |q[i] / 2^32 - x[i] / m| <= 2^-33 + 2^-53: a pixel below
+ *   m 2^-33 gets no electrons.  The weights are never stored.
+ * CDF: cdf[b][i] = q[0] + ... + q[i] in row-major order, inclusive, int64; T = cdf[b][n-1] <= 2^62.  Separate launches, none waits
+ *   for another workgroup: the maximum (one integer atomicMax per workgroup on the float's bits), a sum per tile of EMD_DOSE_TILE
+ *   pixels, a scan of those by one workgroup per image, the scan inside the tiles.  Workspace: emd_dose_workspace_bytes.
+ * Draws: draw d of image b comes from philox4x32_10({j lo, j hi, first_image + b, 9}, {seed lo, seed hi}) = (x, y, z, w) with
+ *   j = d >> 1: r = x 2^32 | y for even d, z 2^32 | w for odd d;  t = (r T) >> 64 (the high half of the 128-bit product, so t < T);
+ *   the electron lands in pixel p = #{i : cdf[i] <= t} (numpy.searchsorted(cdf, t, side="right")): a zero-weight pixel is never hit.
+ *   bounds: a HOST array of L + 1 draw indices, not descending, bounds[0] >= 0, bounds[L] - bounds[0] < 2^31,
+ *   1 <= L <= EMD_DOSE_MAX_LEVELS; draw d in [bounds[k], bounds[k+1]) adds 1 to planes[b][k][p] (int32 [B][L][H][W]).  The entry point
+ *   ADDS to what the planes hold: the caller zeroes them (a memset), or extends a series by a later call whose bounds[0] is where
+ *   the last one stopped -- the draws [0, D) are the same electrons however they are split into calls or levels.  One launch,
+ *   grid-stride over the Philox calls, one no-return integer atomicAdd per electron; no draw, target or index is written to memory.
+ *   A table of at most EMD_DOSE_COARSE values of the CDF, one every ceil(n / EMD_DOSE_COARSE) pixels rounded up to a multiple of 16
+ *   (the tile ends where the image has EMD_DOSE_COARSE tiles), is staged in LDS once per workgroup and searched there; the pixels
+ *   between two entries are searched in global memory.  An image of more than EMD_DOSE_COARSE tiles has several tiles per table entry
+ *   and a correspondingly longer second search; it is not refused.
+ *   first_image + B <= 2^32.
+ * Cumulate: plane k becomes the sum of the planes 0 .. k, in place, so that it holds every draw below bounds[k+1]; minmax[b][k] =
+ *   {min, max} of that plane (int32 [B][L][2]; integer atomics on words that a small launch sets first).  Counts must not be negative.  L = 1 leaves the plane as it is.
+ * Rescale (record_lq, :30-35), per plane with that min and max: EMD_DOSE_UINT16  out = (int32) trunc(65535.0 * (c - min) / (max - min)),
+ *   product and quotient in double as numpy forms them; EMD_DOSE_UNIT  out = (float32)((c - min) / (max - min)), the quotient in
+ *   double, rounded once.  Where max == min the reference divides by zero; here the plane is all 0.  out: [B][L][H][W], 4 bytes an
+ *   element either way.
+ *
+ * Deviations from the reference: its walk along the sorted uniforms advances at most one pixel per draw (:21-26), so a draw that skips
+ * a whole low-weight pixel is booked to the wrong pixel -- here the lookup is the inverse CDF; it normalises the cumulative sum in
+ * floating point -- here the comparison is scaled by T in integers; it reseeds numpy from numpy per chunk -- here one Philox stream per
+ * image.
+ *
+ * No floating-point atomics, no host synchronisation, launches only: capturable on one stream, bitwise reproducible, and an
+ * image's result does not depend on B.  Every argument is checked before any launch.  0 <= B <= 65535 (B == 0 is a no-op),
+ * 2 <= H, W <= 32768, H W <= 2^30.  The workspace is the caller's, 16-byte aligned; cdf 8-byte; outputs and the workspace overlap nothing. */
+#define EMD_DOSE_EMPTY 1
+#define EMD_DOSE_SANITIZED 2
+#define EMD_DOSE_UNIT 0
+#define EMD_DOSE_UINT16 1
+#define EMD_DOSE_TILE 2048
+#define EMD_DOSE_COARSE 2048
+#define EMD_DOSE_MAX_LEVELS 32
+size_t emd_dose_workspace_bytes(int B, int H, int W);
+int emd_dose_cdf_i64(const float* x, int B, int H, int W, int64_t* cdf, int* status, void* workspace, size_t workspace_bytes,
+                     emd_stream_t stream);
+int emd_dose_draw_i32(const int64_t* cdf, int B, int H, int W, unsigned long long seed, unsigned long long first_image,
+                      const int64_t* bounds_host, int L, int* planes, emd_stream_t stream);
+int emd_dose_cumulate_i32(int* planes, int B, int L, int H, int W, int* minmax, emd_stream_t stream);
+int emd_dose_rescale(const int* planes, const int* minmax, int B, int L, int H, int W, int mode, void* out, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
