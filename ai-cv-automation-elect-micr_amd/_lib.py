@@ -566,6 +566,7 @@ SIGNATURES = {
 DEV_SIGNATURES = {
     "emd_debug_knob": (C.c_int, [C.c_char_p, C.c_long]),
     "emd_debug_reduce_final_cl": (C.c_int, [C.c_int]),
+    "emd_debug_sep_pipe2_chunk_covers": (C.c_int, [C.c_int] * 5),
     "emd_debug_split_variant": (None, [C.c_int]),
     "emd_debug_split_stamps": (None, [C.c_void_p]),
     "emd_debug_sep_stamps": (None, [C.c_void_p]),

@@ -1079,6 +1079,14 @@ extern "C" int emd_sep3x3_fused_gen9_f32(const float* img, const float* w9, cons
     return launch_gen9(p, B, static_cast<hipStream_t>(stream));
 }
 
+// dev hook (include/emdenoise_dev.h), host only: the shape rule of the whole-chunk instance of sep_pipe2.hip -- no batch argument
+extern "C" int emd_debug_sep_pipe2_chunk_covers(int H, int W, int Cin, int Cout, int Cout2) {
+    if (!emd_sep3x3_dual_supported(H, W, Cin, Cout, Cout2)) return 0;
+    emd::SepParams p{};
+    p.H = H; p.W = W; p.Cin = Cin; p.N = Cout; p.N2 = Cout2; p.stride = 1;
+    return emd::sep_pipe2_chunk_covers(p) ? 1 : 0;
+}
+
 // dev hook (not in the header): per-workgroup phase cycle sums for tools/sep_bench.py
 extern "C" void emd_debug_sep_stamps(void* buf) { g_knobs.sep_stamps = static_cast<long long*>(buf); }
 

@@ -66,5 +66,8 @@ int sep_pipe_launch(const SepParams& p, int B, hipStream_t st);
 // sep_pipe2.hip: the software-pipelined form (8 x 32 tiles, stride 1): sep_pipe_launch hands it the shapes the rule below gives it
 bool sep_pipe2_covers(const SepParams& p);
 int sep_pipe2_launch(const SepParams& p, int B, hipStream_t st);
+// sep_pipe2.hip: its whole-chunk instance (round 10; two outputs on the 256-column tile): compile-time slot parity, one role per wave
+bool sep_pipe2_chunk_covers(const SepParams& p);
+int sep_pipe2_chunk_launch(const SepParams& p, int B, hipStream_t st);
 
 }  // namespace emd

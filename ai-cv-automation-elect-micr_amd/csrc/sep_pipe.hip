@@ -973,8 +973,19 @@ static bool use_pipe2(const SepParams& p) {
     return p.N2 > 0 && (p.N > 64 || p.N2 > 64);
 }
 
+// The whole-chunk instance of sep_pipe2.hip (round 10; same bits): the two-output launches on the 256-column tile (deconv1_a + residual1_d of
+// graph D), by the layer's shape alone.  Dev knob sep_pipe2_chunk: 1 takes it, 0 keeps this file's lockstep kernel, -1 (default) = kChunkRule;
+// the older knob sep_pipe2 (run-time parity instances) and the forced forms go first.
+constexpr int kChunkRule = 1;
+static bool use_pipe2_chunk(const SepParams& p) {
+    const int on = g_knobs.sep_pipe2_chunk < 0 ? kChunkRule : g_knobs.sep_pipe2_chunk;
+    if (!on || g_knobs.sep_pipe2 || g_knobs.sep_ablate || g_knobs.sep_nw == 4 || g_knobs.sep_stamps) return false;
+    return sep_pipe2_chunk_covers(p);
+}
+
 int sep_pipe_launch(const SepParams& p, int B, hipStream_t st) {
     if (use_pipe2(p)) return sep_pipe2_launch(p, B, st);
+    if (use_pipe2_chunk(p)) return sep_pipe2_chunk_launch(p, B, st);
     SepParams q = p;
     const bool s2 = p.stride == 2;
     const int nw = (p.gen_a || folded(p) || (!s2 && use_nw4(p))) ? 4 : 8, tw = s2 ? 16 : 4 * nw, th = s2 ? 4 : 8;

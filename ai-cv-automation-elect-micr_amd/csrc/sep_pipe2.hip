@@ -30,6 +30,8 @@
 // Patch swizzle: 16-byte chunk c of patch pixel column px is stored at c ^ ((px >> 1) & 7) (applied to the DMA's source address): the
 // depthwise stage's 8-byte reads (a 32-lane group = 2 rows x pixel groups {g, g + 2} x 8 channel pairs), and the projection's 16-byte
 // centre reads (16 consecutive pixels of a row) then cover the 64 banks evenly.  A / B rows (64 B): chunk ^ ((row >> 2) & 3).
+#include <type_traits>
+
 #include "sep_params.hpp"
 
 namespace {
@@ -640,6 +642,459 @@ __global__ __launch_bounds__(512, 2) void sep_pipe2_kernel(const SepParams p) {
 #undef PIPE_STAMP
 }
 
+// ---- Whole-chunk form (round 10): the two-output instance of 256 columns (128 | 128, fp32 outputs, no residual, no second affine) with
+// the instruction count of the lockstep kernel and the overlap of the kernel above.  Same LDS image, same DMA stream, same vmcnt
+// arithmetic, same slot order and same bits; what differs:
+//   * the loop steps by a CHUNK: its body is slot 2t (K half 0) then slot 2t + 1 (K half 1), each written out once with its parity a
+//     compile-time constant -- the A / B half offsets and the depthwise stage's K half are immediates of the LDS instructions.  The fill
+//     (slot -1) and the drain (slot 2 total) are peeled: the accumulators cross the loop's back edge only, never a join of two bodies.
+//     The patch stage alternates per chunk and stays one run-time base (an unrolling by two chunks would double the code and need a
+//     third peeled form for odd totals): four v_add per slot.
+//   * the wave's role is chosen ONCE, outside the loop, by a wave-uniform branch: waves 0-3 (the block) carry the depthwise stage and
+//     the block's MFMAs, waves 4-7 (the projection) the operand split and the projection's MFMAs; neither holds the other's registers.
+//     Both run one barrier per slot.
+//   * the depthwise stage is 4 pixels x 4 channels per thread on ds_read_b128 (27 per slot), packed FMAs, 8-byte A writes: a slot's
+//     256 pixels x 16 channels are 256 such threads = the four block waves, wave w rows 2w, 2w + 1 of the tile.  The nine-tap sum of a
+//     channel runs in sep_pipe.hip's order (rows outermost, then the output pixel, then the tap of the row).
+// Bank argument (DESIGN.md 3.3c has it in full): a ds_read_b128 is served in four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19,
+// 28-31} and the same + 32; with lane = 4 cell + quad these are the cells of even / odd bit count.  A cell's bits are (row of the pair,
+// pixel group + 2, set): a 16-lane group then holds 4 channel quads x 2 rows x pixel columns {dx, dx + 8}.  Rows differ in the parity of
+// their slot (pitch 35: the 128-byte half of the bank row), dx and dx + 8 in bit 3 of the pixel column = bit 2 of the patch swizzle
+// (px >> 1) & 7, which moves the K half's four chunks to the other 64 bytes of that half: 16 distinct 16-byte slots, no conflict, for
+// each of the 18 reads (the swizzle of the kernel above serves unchanged).  The nine weight reads hit four addresses (broadcast).
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void sep_pipe2_chunk_kernel(const SepParams p) {
+    constexpr int BN = 256, NW = 8, TW = 32, TH = 8, BM = TH * TW;
+    constexpr int PW = TW + 2, PH = TH + 2, PWS = PW | 1;
+    constexpr int NPATCH = PH * PWS, NSLOT = NPATCH;
+    constexpr int WK0 = PW, WKS = PWS;
+    constexpr int NPIECE = (NSLOT + 7) / 8, PP = (NPIECE + NW - 1) / NW, STAGE = NPIECE * 1024;
+    constexpr int A_HALF = BM * 64, B_HALF = BN * 64;
+    constexpr int A_OFF = 2 * STAGE, B_OFF = A_OFF + 2 * A_HALF, C_OFF = B_OFF + 2 * B_HALF, P_OFF = C_OFF + 8 * BN, SMEM = P_OFF + 128;   // [scale1 | shift1][BN], the launch's scalars
+    constexpr int NBP = BN / 16, PB = NBP / NW;
+    constexpr int WN = BN / 64, WM = NW / WN, TM = BM / WM / 32, TN = 2;
+    constexpr int E = 16 / EPI * TM * TN;
+    static_assert(SMEM <= 160 * 1024 && PP >= 2 && PB >= 1 && TM == 4, "shape");
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEM];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int idx = wv & 3, wm = idx % WM, wn = (wv >> 2) * (WN / 2) + idx / WM;
+    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    xcd_remap(p.xcd, bx, by, bz);
+    const int xbase = bx * p.tpw * TW;
+    // The launch's scalars that only the rare paths read (a tile at an image edge, the epilogue) sit in LDS and are fetched where they are
+    // used: held in SGPRs through the slots, with what the compiler derives from them, they spill.
+    enum { L_X = 0, L_DW = 8, L_Y = 16, L_Y2 = 24, L_LDY = 32, L_LDY2 = 36, L_N = 40, L_N2 = 44, L_ACT = 48, L_H = 52, L_W = 56, L_CIN = 60, L_LDX = 64,
+           L_REFLECT = 68, L_Y0 = 72, L_BZ = 76 };
+    if (tid == 0) {
+        unsigned char* l = smem + P_OFF;
+        *reinterpret_cast<const float**>(l + L_X) = p.x;
+        *reinterpret_cast<const float**>(l + L_DW) = p.dw;
+        *reinterpret_cast<float**>(l + L_Y) = p.y;
+        *reinterpret_cast<float**>(l + L_Y2) = p.y2;
+        *reinterpret_cast<int*>(l + L_LDY) = p.ldy;
+        *reinterpret_cast<int*>(l + L_LDY2) = p.ldy2;
+        *reinterpret_cast<int*>(l + L_N) = p.N;
+        *reinterpret_cast<int*>(l + L_N2) = p.N2;
+        *reinterpret_cast<int*>(l + L_ACT) = p.act;
+        *reinterpret_cast<int*>(l + L_H) = p.H;
+        *reinterpret_cast<int*>(l + L_W) = p.W;
+        *reinterpret_cast<int*>(l + L_CIN) = p.Cin;
+        *reinterpret_cast<int*>(l + L_LDX) = p.ldx;
+        *reinterpret_cast<int*>(l + L_REFLECT) = p.reflect;
+        *reinterpret_cast<int*>(l + L_Y0) = by * TH;
+        *reinterpret_cast<int*>(l + L_BZ) = bz;
+    }
+    __syncthreads();
+    auto lds_i = [&](int off) { return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(smem + P_OFF + off)); };
+    auto lds_p = [&](int off) {
+        const unsigned lo = lds_i(off), hi = lds_i(off + 4);
+        return reinterpret_cast<float*>(((unsigned long long)hi << 32) | lo);
+    };
+
+    // ---- patch and weight DMA: the kernel above's, piece for piece (both roles issue their share)
+    const float* psrc[PP];
+    unsigned pmove = 0;
+    auto set_tile = [&](int xt) {
+        int drow = lane >> 3, dk = lane & 7, w = wv;
+        asm volatile("" : "+v"(drow), "+v"(dk), "+s"(w));   // opaque: nothing of this (rare: image edges) computation is held across the slots
+        pmove = 0;
+        const float* px_ = lds_p(L_X);
+        const float* pdw = lds_p(L_DW);
+        const int H = lds_i(L_H), W = lds_i(L_W), Cin = lds_i(L_CIN), ldx = lds_i(L_LDX), reflect = lds_i(L_REFLECT), y0 = lds_i(L_Y0);
+        const long img = (long)lds_i(L_BZ) * H * W;
+#pragma unroll
+        for (int j = 0; j < PP; ++j) {
+            int q = w + NW * j;
+            if (q >= NPIECE) q -= NW;
+            const int slot = q * 8 + drow;
+            const int py = slot / PWS, px = slot - py * PWS;
+            int gy = y0 - 1 + py, gx = xt - 1 + px;
+            if (reflect) {
+                gy = gy < 0 ? -gy : (gy >= H ? 2 * H - 2 - gy : gy);
+                gx = gx < 0 ? -gx : (gx >= W ? 2 * W - 2 - gx : gx);
+            }
+            const bool real = slot < NPATCH && px < PW && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const bool wk = slot < NPATCH && px == PW && py < 9;
+            const int kk = dk ^ ((px >> 1) & 7);
+            const float* o = g_zero_pipe2 + dk * 4;
+            const float* o_px = px_ + (img + (long)gy * W + gx) * ldx + kk * 4;
+            const float* o_wk = pdw + (long)py * Cin + dk * 4;
+            o = real ? o_px : o;
+            o = wk ? o_wk : o;
+            psrc[j] = o;
+            pmove |= real ? 1u << j : 0u;
+        }
+    };
+    auto issue_patch = [&](int stage, int coff, int j0 = 0, int j1 = PP) {
+#pragma unroll
+        for (int j = j0; j < j1; ++j) {
+            int q = wv + NW * j;
+            if (q >= NPIECE) q -= NW;
+            __builtin_amdgcn_global_load_lds((gptr_t)(psrc[j] + coff), (lptr_t)(smem + stage * STAGE + q * 1024), 16, 0, 0);
+        }
+    };
+    const uint16_t* bsrc[PB];
+    int bq[PB];
+    bool bproj[PB];
+#pragma unroll
+    for (int j = 0; j < PB; ++j) {
+        const int q = (wv * PB + j) % NBP;
+        const int row = q * 16 + (lane >> 2);
+        const int c = (lane & 3) ^ ((row >> 2) & 3);
+        const bool second = row >= BN / 2;
+        const int rr = second ? row - BN / 2 : row;
+        const uint16_t* plane = (c & 2) ? (second ? p.W2lo : p.Wlo) : (second ? p.W2hi : p.Whi);
+        bsrc[j] = plane + (long)rr * p.Cpad + (c & 1) * 8;
+        bq[j] = q;
+        bproj[j] = q >= NBP / 2;
+    }
+    auto issue_B = [&](int hm, int cm, int hp, int cp) {
+#pragma unroll
+        for (int j = 0; j < PB; ++j) {
+            const int h = bproj[j] ? hp : hm, c = bproj[j] ? cp : cm;
+            __builtin_amdgcn_global_load_lds((gptr_t)(bsrc[j] + c + h * 16), (lptr_t)(smem + B_OFF + h * B_HALF + bq[j] * 1024), 16, 0, 0);
+        }
+    };
+
+    const bool full = p.N == BN / 2 && p.N2 == BN / 2;
+    const int nchunks = p.Cin / 32;
+    const int total = p.tpw * nchunks;
+    int istep = 0, ic = 0, ixt = xbase;
+    set_tile(xbase);
+    auto advance_issue = [&]() {
+        if (istep + 1 >= total) return;
+        ++istep;
+        if (++ic == nchunks) {
+            ic = 0;
+            const int xn = ixt + TW;
+            if (ixt >= 1 && xn + TW + 1 <= p.W) {
+                const long step = (long)TW * p.ldx;
+#pragma unroll
+                for (int j = 0; j < PP; ++j) psrc[j] += ((pmove >> j) & 1) ? step : 0;
+            } else {
+                set_tile(xn);
+            }
+            ixt = xn;
+        }
+    };
+
+    if (tid < BN) {   // the epilogue's per-channel affines: [scale1 | shift1][BN], the projection's in columns BN/2 .. (no second affine: the rule)
+        const bool second = tid >= BN / 2;
+        const int nn = second ? tid - BN / 2 : tid;
+        const bool valid = nn < (second ? p.N2 : p.N);
+        float* cst = reinterpret_cast<float*>(smem + C_OFF);
+        cst[tid] = valid ? (second ? p.scale_b : p.scale1)[nn] : 0.f;
+        cst[BN + tid] = valid ? (second ? p.shift_b : p.shift1)[nn] : 0.f;
+    }
+
+    // ---- prologue: weights of the projection's step 0, patches of chunks 0 and 1
+    issue_B(1, 0, 0, 0);
+    issue_patch(0, 0);
+    advance_issue();
+    issue_patch(1, ic * 32);
+    wait_vm<PP>();
+    __builtin_amdgcn_s_barrier();
+
+    // ---- one role, start to end.  OUT2: the projection (waves 4-7), else the block (waves 0-3)
+    auto role = [&](auto out2c) {
+        constexpr bool OUT2 = decltype(out2c)::value;
+        const int fr = lane & 31, fh = lane >> 5, gf = (fr >> 2) & 3;
+        const int row0 = wm * TM * 32;
+        // block: depthwise lane map (see the header).  cell = lane >> 2: bit 0 = row of the pair, bit 1 = pixel group + 2, the set of
+        // four pixel groups = bit 2 ^ bit 1 ^ bit 0 and lane >> 5; wave w owns tile rows 2 w, 2 w + 1
+        const int qd = lane & 3, cell = (lane >> 2) & 7;
+        const int st = (((cell >> 2) ^ (cell >> 1) ^ cell) & 1) + 2 * (lane >> 5);
+        const int dy = 2 * idx + (cell & 1), dx = 4 * (st & 1) + 16 * (st >> 1) + 8 * ((cell >> 1) & 1);
+        int rdv[3];       // pixel columns dx + 2 m, dx + 2 m + 1: byte offset in a stage of this thread's 16 bytes of pixel (dy, dx), K half 0 (half 1: ^ 64)
+#pragma unroll
+        for (int m = 0; m < 3; ++m) rdv[m] = (dy * PWS + dx) * 128 + ((qd ^ (((dx >> 1) + m) & 7)) << 4);
+        const int wk_off = WK0 * 128 + qd * 16;                      // + h * 64 + tap * WKS * 128
+        const int a_wr = A_OFF + (dy * TW + dx) * 64 + (((qd >> 1) ^ ((dx >> 2) & 3)) << 4) + (qd & 1) * 8;   // hi of pixel j: + 64 j; lo: ^ 32
+        const int a_wr2 = a_wr ^ 32;
+        // fragments.  block: A rows, hi at a_rd + h A_HALF + 2048 i, lo at a_rd2 + the same; projection: fp32 centre pixels of the patch
+        const int a_rd = A_OFF + (row0 + fr) * 64 + ((fh ^ gf) << 4), a_rd2 = a_rd ^ 32;
+        const int cen = ((row0 / TW + 1) * PWS + fr + 1) * 128 + (((fh * 2) ^ (((fr + 1) >> 1) & 7)) << 4);
+        const int b_rd = B_OFF + (wn * 64 + fr) * 64 + ((fh ^ gf) << 4), b_rd2 = b_rd ^ 32;
+
+        f32x16 acc[TM][TN];
+        auto zero_acc = [&]() {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        };
+        zero_acc();
+
+        // epilogue from the accumulators: the kernel above's two forms without the residual and the split32 output
+        auto epilogue = [&](int x0) {
+            int fr = lane & 31, fh = lane >> 5;
+            asm volatile("" : "+v"(fr), "+v"(fh));
+            int actc = OUT2 ? 1 : lds_i(L_ACT);
+            const float hi = actc == 1 ? 6.f : __builtin_inff();
+            const float slope = actc == 4 ? 0.2f : 1.f, lo = (actc == 1 || actc == 2) ? 0.f : -__builtin_inff();
+            const bool simple = actc == 1;
+            float* __restrict__ outp = lds_p(OUT2 ? L_Y2 : L_Y);
+            const int ldo = lds_i(OUT2 ? L_LDY2 : L_LDY), nlim = lds_i(OUT2 ? L_N2 : L_N), wo = lds_i(L_W);
+            int yrow = row0 / TW;
+            asm volatile("" : "+s"(yrow));   // opaque: the tile's addresses are formed here, not held across the slots
+            yrow += lds_i(L_Y0);
+            const long imgo = (long)lds_i(L_BZ) * lds_i(L_H) * wo;
+            float es1[TN], et1[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const float* cst = reinterpret_cast<const float*>(smem + C_OFF) + wn * 64 + j * 32 + fr;
+                es1[j] = cst[0];
+                et1[j] = cst[BN];
+            }
+            const int li = fr & 3, cq = fr >> 2;
+            unsigned voff[TN];
+            bool live[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int nb = wn * 64 + j * 32 - (OUT2 ? BN / 2 : 0);
+                const int n = EPI == 1 ? nb + fr : nb + 4 * cq;   // (EPI 4: a lane's four channels are all in or all out, Cout % 4 == 0)
+                live[j] = n < nlim;
+                voff[j] = EPI == 1 ? (unsigned)(4 * fh * ldo + n) * 4u : (unsigned)((4 * fh + li) * ldo + n) * 4u;
+            }
+            // M tile, then eight pixel rows of it, then the two column groups: an address serves both groups at once (column groups
+            // outermost, the 64 addresses of a wave's tile stayed live from the first group to the second: SGPR spills)
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const long pixr = imgo + (long)(yrow + i) * wo + x0;   // uniform: the M tile's first pixel (a tile row)
+                float* obase = outp + pixr * ldo;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float r[TN][4];
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const float s1 = es1[j], t1 = et1[j];
+                        if constexpr (EPI == 1) {
+                            if (simple) {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) r[j][k] = __builtin_amdgcn_fmed3f(fmaf(acc[i][j][4 * q + k], s1, t1), 0.f, 6.f);
+                            } else {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const float u = fmaf(acc[i][j][4 * q + k], s1, t1);
+                                    r[j][k] = __builtin_amdgcn_fmed3f(fmaxf(u, slope * u), lo, hi);
+                                }
+                            }
+                        } else {
+                            if (simple) {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) r[j][k] = fminf(fmaxf(fmaf(acc[i][j][4 * q + k], s1, t1), 0.f), 6.f);
+                            } else {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) {
+                                    const float u = fmaf(acc[i][j][4 * q + k], s1, t1);
+                                    r[j][k] = fminf(fmaxf(fmaxf(u, lo), slope * u), hi);
+                                }
+                            }
+                            quad_transpose(r[j], li);
+                        }
+                    }
+                    if constexpr (EPI == 1) {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            float* ob = obase + (8 * q + k) * ldo;   // row 8 q + k of the M tile
+#pragma unroll
+                            for (int j = 0; j < TN; ++j)
+                                if (live[j]) store_nt_d(ob, voff[j], __builtin_bit_cast(unsigned, r[j][k]));
+                        }
+                    } else {
+                        float* ob = obase + 8 * q * ldo;
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            if (live[j]) store_nt_s(ob, voff[j], f32x4{r[j][0], r[j][1], r[j][2], r[j][3]});
+                    }
+                }
+            }
+            zero_acc();
+        };
+
+        // ---- one slot's arithmetic with its parity a constant.  Block: MFMAs on K half ODD of A / B, depthwise stage -> A half 1 - ODD from
+        // the patch stage at stg; projection (one step ahead): MFMAs on the centre pixels of that stage and B half 1 - ODD.  Issue order as
+        // above: [MFMAs of a quarter | FMAs of one patch row | the reads the next quarter needs] x 3, then [MFMAs | split + A writes].
+        auto body = [&](auto oddc, const int stg, const bool patch, const int pstage, const int pcoff) {
+            constexpr int ODD = decltype(oddc)::value;
+            constexpr int HS = 1 - ODD, HM = OUT2 ? 1 - ODD : ODD;
+            const int fa_1 = OUT2 ? stg + (cen ^ (HM * 64)) : a_rd, fa_2 = OUT2 ? stg + (cen ^ (HM * 64) ^ 16) : a_rd2;
+            constexpr int FA_IMM = OUT2 ? 0 : HM * A_HALF, FSTRIDE = OUT2 ? PWS * 128 : 2048;
+            const int swk = stg + wk_off;
+            int srd[3];
+#pragma unroll
+            for (int m = 0; m < 3; ++m) srd[m] = stg + (rdv[m] ^ (HS * 64));
+            f32x4 wk[3], pr[6], o[4];
+            auto rd_row = [&](int i) {
+                if constexpr (!OUT2) {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) wk[d] = *reinterpret_cast<const f32x4*>(smem + swk + HS * 64 + (i * 3 + d) * (WKS * 128));
+#pragma unroll
+                    for (int d = 0; d < 6; ++d) pr[d] = *reinterpret_cast<const f32x4*>(smem + srd[d >> 1] + (i * PWS + d) * 128);
+                }
+            };
+            auto fma_row = [&]() {
+                if constexpr (!OUT2) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) o[j] += wk[d] * pr[j + d];
+                    asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]));   // a use in THIS segment (see the kernel above)
+                }
+            };
+            bf16x8 bh[TN], bl[TN];
+            u32x4 f0[TM], f1[TM];
+            auto ld_b = [&]() {
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    bh[j] = *reinterpret_cast<const bf16x8*>(smem + b_rd + HM * B_HALF + j * 2048);
+                    bl[j] = *reinterpret_cast<const bf16x8*>(smem + b_rd2 + HM * B_HALF + j * 2048);
+                }
+            };
+            auto ld_a = [&](int i) {
+                f0[i] = *reinterpret_cast<const u32x4*>(smem + fa_1 + FA_IMM + i * FSTRIDE);
+                f1[i] = *reinterpret_cast<const u32x4*>(smem + fa_2 + FA_IMM + i * FSTRIDE);
+            };
+            auto cvt_a = [&](int i) {
+                if constexpr (OUT2) {   // the projection's A operand = the block's INPUT at the tile's own pixels, split here
+                    const f32x4 v0 = __builtin_bit_cast(f32x4, f0[i]), v1 = __builtin_bit_cast(f32x4, f1[i]);
+                    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+                    split2(v0[0], v0[1], h0, l0);
+                    split2(v0[2], v0[3], h1, l1);
+                    split2(v1[0], v1[1], h2, l2);
+                    split2(v1[2], v1[3], h3, l3);
+                    f0[i] = u32x4{h0, h1, h2, h3};
+                    f1[i] = u32x4{l0, l1, l2, l3};
+                }
+            };
+            auto mm = [&](int i, int j) {
+                const bf16x8 ah = __builtin_bit_cast(bf16x8, f0[i]), al = __builtin_bit_cast(bf16x8, f1[i]);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[j], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[j], acc[i][j], 0, 0, 0);
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[j], acc[i][j], 0, 0, 0);
+            };
+            auto seg_mm = [&](int i) {   // segment i = M tile i (TM = 4 segments of TN atoms)
+                cvt_a(i);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) mm(i, j);
+            };
+            if constexpr (!OUT2) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            constexpr int P3 = (PP + 2) / 3;
+            ld_b();
+            ld_a(0);
+            rd_row(0);
+            __builtin_amdgcn_sched_barrier(0);
+            seg_mm(0);
+            fma_row();
+            rd_row(1);
+            ld_a(1);
+            if (patch) issue_patch(pstage, pcoff, 0, P3);
+            __builtin_amdgcn_sched_barrier(0);
+            seg_mm(1);
+            fma_row();
+            rd_row(2);
+            ld_a(2);
+            if (patch) issue_patch(pstage, pcoff, P3, 2 * P3 < PP ? 2 * P3 : PP);
+            __builtin_amdgcn_sched_barrier(0);
+            seg_mm(2);
+            fma_row();
+            ld_a(3);
+            if (patch) issue_patch(pstage, pcoff, 2 * P3 < PP ? 2 * P3 : PP, PP);
+            __builtin_amdgcn_sched_barrier(0);
+            seg_mm(3);
+            if constexpr (!OUT2) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    unsigned h0, l0, h1, l1;
+                    split2(o[j][0], o[j][1], h0, l0);
+                    split2(o[j][2], o[j][3], h1, l1);
+                    *reinterpret_cast<u32x2*>(smem + a_wr + HS * A_HALF + j * 64) = u32x2{h0, h1};
+                    *reinterpret_cast<u32x2*>(smem + a_wr2 + HS * A_HALF + j * 64) = u32x2{l0, l1};
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+
+        // ---- a slot: what it requests, the epilogue of the tile whose last MFMAs ran in the slot before (projection: odd slots, block: even
+        // slots), its arithmetic, its waits, its barrier.  State as in the kernel above: chunk k's second half / chunk k + 1's first.
+        int k = -1, ct1 = 0, x_epi = xbase;
+        auto slot = [&](auto oddc, auto epic) {
+            constexpr int ODD = decltype(oddc)::value;
+            constexpr bool MAYEPI = decltype(epic)::value && (ODD != 0) == OUT2;
+            const int stg = ((k + 1) & 1) * STAGE;
+            const int ct2 = ct1 + 1 == nchunks ? 0 : ct1 + 1;
+            const bool last0 = k >= 0 && ct1 == 0;
+            const bool epi_here = MAYEPI && last0;
+            const bool patch = ODD && k >= 0;
+            const int pstage = k & 1;
+            if (patch) advance_issue();
+            const int pcoff = ic * 32;
+            issue_B(ODD ? 0 : 1, ct1 * 32, ODD ? 1 : 0, (ODD ? ct1 : ct2) * 32);
+            if constexpr (MAYEPI) {
+                if (epi_here) {   // the DMA pieces in one block, the epilogue behind them: its stores are the youngest entries of the queue
+                    if (patch) issue_patch(pstage, pcoff);
+                    epilogue(x_epi);
+                }
+            }
+            body(oddc, stg, patch && !epi_here, pstage, pcoff);
+            wait_lgkm0();
+            if constexpr (ODD) {
+                if (k < 0 || (!full && epi_here)) wait_vm<0>();
+                else if (epi_here) wait_vm<PP + E>();
+                else wait_vm<PP>();
+            } else {
+                if (epi_here && full) wait_vm<E>();
+                else wait_vm<0>();
+            }
+            __builtin_amdgcn_s_barrier();
+            if constexpr (!ODD) {
+                if (last0) x_epi += TW;
+                ct1 = ct2;
+                ++k;
+            }
+        };
+        using C0 = std::integral_constant<int, 0>;
+        using C1 = std::integral_constant<int, 1>;
+        slot(C1{}, std::false_type{});           // fill: the block's MFMAs run on nothing, their sums are dropped
+        if constexpr (!OUT2) zero_acc();
+        for (int t = 0; t < total; ++t) {
+            slot(C0{}, std::true_type{});
+            slot(C1{}, std::true_type{});
+        }
+        slot(C0{}, std::true_type{});            // drain: the block's last epilogue
+    };
+    if (wv < 4) role(std::false_type{});
+    else role(std::true_type{});
+    wait_vm<0>();   // the surplus DMA groups must have landed before this workgroup's LDS goes to the next one
+}
+
 template <int BN, bool DUAL, bool OSPLIT, int EPI>
 int launch2(const SepParams& q, dim3 grid, hipStream_t st) {
     hipLaunchKernelGGL((sep_pipe2_kernel<BN, DUAL, OSPLIT, EPI>), grid, dim3(512), 0, st, q);
@@ -681,6 +1136,31 @@ int sep_pipe2_launch(const SepParams& p, int B, hipStream_t st) {
     if (p.N <= 128) return p.out_split ? launch2<128, false, true, 1>(q, grid, st) : launch2<128, false, false, 1>(q, grid, st);
     if (p.out_split) return epi == 4 ? launch2<256, false, true, 4>(q, grid, st) : launch2<256, false, true, 1>(q, grid, st);
     return epi == 4 ? launch2<256, false, false, 4>(q, grid, st) : launch2<256, false, false, 1>(q, grid, st);
+}
+
+// The whole-chunk instance (sep_pipe2_chunk_kernel): two fp32 outputs, more than 64 columns in one of them (the 256-column tile), stride 1,
+// 8 x 32 tiles.  A rule of the layer's shape alone.
+bool sep_pipe2_chunk_covers(const SepParams& p) {
+    if (p.stride != 1 || p.gen_a || p.rg_stride || p.H % 8 != 0 || p.W % 32 != 0 || p.Cin % 32 != 0 || p.Cin < 32 || p.Cin > 4064) return false;
+    return p.N2 > 0 && p.N <= 128 && p.N2 <= 128 && (p.N > 64 || p.N2 > 64) && !p.out_split && !p.res && !p.scale2;
+}
+
+int sep_pipe2_chunk_launch(const SepParams& p, int B, hipStream_t st) {
+    SepParams q = p;
+    const int tiles_w = p.W / 32;
+    const long wgs1 = (long)tiles_w * (p.H / 8) * B;
+    int tpw = 1;   // as sep_pipe2_launch
+    for (int t = 8; t >= 2; t >>= 1)
+        if (tiles_w % t == 0 && wgs1 / t >= 1024) { tpw = t; break; }
+    if (g_knobs.sep_tpw > 0 && tiles_w % g_knobs.sep_tpw == 0) tpw = g_knobs.sep_tpw;
+    q.tpw = tpw;
+    q.stamps = nullptr;
+    q.ablate = 0;
+    const dim3 grid(tiles_w / tpw, p.H / 8, B);
+    q.xcd = g_knobs.sep_xcd && ((long)grid.x * grid.y * grid.z) % 8 == 0;
+    if (g_knobs.epi_width == 4) hipLaunchKernelGGL((sep_pipe2_chunk_kernel<4>), grid, dim3(512), 0, st, q);
+    else hipLaunchKernelGGL((sep_pipe2_chunk_kernel<1>), grid, dim3(512), 0, st, q);
+    return emd::check_launch("sep_pipe2_chunk_kernel");
 }
 
 }  // namespace emd

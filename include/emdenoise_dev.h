@@ -9,6 +9,8 @@
  * Nothing in the library reads the environment.  The kernel-selection knobs are fields of one struct (csrc/emd_common.hpp, emd::Knobs),
  * set by name through emd_debug_knob; defaults = the measured-best path:
  *   sep_pipe (1)        1: the LDS-DMA pipelined fused separable conv (csrc/sep_pipe.hip) where it covers the shape, 0: csrc/sep_fused.hip
+ *   sep_pipe2_chunk (-1) two fp32 outputs on the 256-column tile (more than 64 channels in one of them; H % 8 == 0, W % 32 == 0): 1 = the whole-chunk
+ *                       instance of csrc/sep_pipe2.hip, 0 = csrc/sep_pipe.hip's lockstep kernel (same bits), -1 = the rule (the faster one)
  *   sep_mode (-1)       sep_pipe schedule of the one-output instances: -1 = rule, 0 / 1 = the patch requested two / one steps ahead
  *   sep_nw (0)          sep_pipe waves per workgroup: 0 = rule (4 wherever there is an instance), 8 (8 x 32 pixel tiles, one workgroup per CU)
  *                       or 4 (8 x 16 tiles, two per CU: up to 128 output columns, 64 | 64 for two outputs)
@@ -55,6 +57,9 @@ int emd_debug_knob(const char* name, long value);
  * chan_reduce_final) for `nslab` partials per channel -- the launch rule itself (csrc/emd_common.hpp, emd::reduce_final_cl), so that
  * tests/test_reduce_routes.py can prove which instance each of its shapes selects. */
 int emd_debug_reduce_final_cl(int nslab);
+/* Host only, no state: 1 where emd_sep3x3_dual_f32 has the whole-chunk instance of csrc/sep_pipe2.hip for the layer's shape (what the knob
+ * sep_pipe2_chunk switches; the rule has no batch argument), else 0. */
+int emd_debug_sep_pipe2_chunk_covers(int H, int W, int Cin, int Cout, int Cout2);
 /* Force the pipeline variant of emd_conv1x1_split32_f32 (csrc/gemm_split.hip); -1 restores the dispatch rule. */
 void emd_debug_split_variant(int v);
 /* Device buffer that the split32 GEMM writes s_memtime phase stamps into (NULL = off). */
