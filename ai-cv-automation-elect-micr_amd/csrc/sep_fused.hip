@@ -32,11 +32,6 @@ namespace {
 // the load where it is issued instead of a whole depthwise + MFMA phase later)
 __device__ __attribute__((aligned(16))) float g_zero_px[4096];
 
-// Knobs of the 512^2 / 256^2 layers' cache behaviour (dev, emd_debug_knob): nt_mask bit 1 = non-temporal output stores here (default on), sep_xcd = 0
-// turns the XCD-contiguous tile order off.
-inline int sep_nt() { return (g_knobs.nt_mask >> 1) & 1; }
-inline int sep_xcd() { return g_knobs.sep_xcd; }
-
 // BN = columns of the workgroup's GEMM tile: 64 / 128 (one output), or with DUAL the two outputs side by side: 128 = 64 | 64 on an
 // 8 x 16 pixel tile, 256 = 128 | 128 on a 4 x 16 pixel tile (TH = 4: the accumulators of both outputs fit the same registers).
 // WRES (BN = 64, Cin <= 64): the whole pointwise weight matrix (at most two 32-channel chunks, 10 KB each with the lo plane) is put into
@@ -708,435 +703,52 @@ __global__ __launch_bounds__(256, 2) void sep_gen9_kernel(const SepParams p) {
     }
 }
 
-
-// several tiles per workgroup where that still leaves >= 8 workgroups per CU
-int tiles_per_workgroup(int tiles_w, long wgs1) {
-    const int force = g_knobs.sep_tpw;
-    int tpw = 1;
-    for (int t = 8; t >= 2; t >>= 1)
-        if (tiles_w % t == 0 && wgs1 / t >= 2048) { tpw = t; break; }
-    if (force > 0 && tiles_w % force == 0) tpw = force;
-    return tpw;
-}
-
-// BN = 64, Cin <= 64, split-bf16: the pointwise weights stay in LDS for the workgroup's whole life
-int launch_wres(const SepParams& p, int B, hipStream_t st) {
-    SepParams q = p;
-    const int tiles_w = p.W / 16;
-    q.tpw = tiles_per_workgroup(tiles_w, (long)tiles_w * (p.H / 8) * B);
-    q.stamps = g_knobs.sep_stamps;
-    const dim3 grid(tiles_w / q.tpw, p.H / 8, B);
-    q.nt = sep_nt();
-    q.xcd = sep_xcd() && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    if (p.gen_a) hipLaunchKernelGGL((sep_fused_kernel<64, 3, true, 8, false, true>), grid, dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((sep_fused_kernel<64, 3, false, 8, false, true>), grid, dim3(256), 0, st, q);
-    return emd::check_launch("sep_fused_kernel<resident W>");
-}
-
-// the generated-input layer fed by the 1-channel image itself (sep_gen9_kernel): the tile walk of launch_wres
-int launch_gen9(const SepParams& p, int B, hipStream_t st) {
-    SepParams q = p;
-    const int tiles_w = p.W / 16;
-    q.tpw = tiles_per_workgroup(tiles_w, (long)tiles_w * (p.H / 8) * B);
-    const dim3 grid(tiles_w / q.tpw, p.H / 8, B);
-    q.nt = sep_nt();
-    q.xcd = sep_xcd() && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    if (p.Cin == 64) {
-        if (p.res) hipLaunchKernelGGL((sep_gen9_kernel<2, true>), grid, dim3(256), 0, st, q);
-        else hipLaunchKernelGGL((sep_gen9_kernel<2, false>), grid, dim3(256), 0, st, q);
-    } else if (p.res) {
-        hipLaunchKernelGGL((sep_gen9_kernel<1, true>), grid, dim3(256), 0, st, q);
-    } else {
-        hipLaunchKernelGGL((sep_gen9_kernel<1, false>), grid, dim3(256), 0, st, q);
-    }
-    return emd::check_launch("sep_gen9_kernel");
-}
-
 template <int BN>
-int launch(const SepParams& p, int B, int passes, hipStream_t st) {
-    if constexpr (BN == 64) {
-        const int wres = g_knobs.sep_wres;   // dev knob: 0 = per-chunk W loads
-        if (wres && p.Cin <= 64 && passes == 3) return launch_wres(p, B, st);
-    }
-    SepParams q = p;
-    const int tiles_w = p.W / 16;
-    q.tpw = tiles_per_workgroup(tiles_w, (long)tiles_w * (p.H / 8) * B);
-    q.stamps = g_knobs.sep_stamps;
-    const dim3 grid(tiles_w / q.tpw, p.H / 8, B);
-    q.nt = sep_nt();
-    q.xcd = sep_xcd() && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    if (p.gen_a) {
-        if (passes == 3)
-            hipLaunchKernelGGL((sep_fused_kernel<BN, 3, true>), grid, dim3(256), 0, st, q);
+int launch_bn(const SepParams& q, const SepPlan& plan, hipStream_t st) {
+    if (q.gen_a) {
+        if (plan.passes == 3)
+            hipLaunchKernelGGL((sep_fused_kernel<BN, 3, true>), plan.grid, dim3(256), 0, st, q);
         else
-            hipLaunchKernelGGL((sep_fused_kernel<BN, 1, true>), grid, dim3(256), 0, st, q);
-    } else if (passes == 3)
-        hipLaunchKernelGGL((sep_fused_kernel<BN, 3, false>), grid, dim3(256), 0, st, q);
+            hipLaunchKernelGGL((sep_fused_kernel<BN, 1, true>), plan.grid, dim3(256), 0, st, q);
+    } else if (plan.passes == 3)
+        hipLaunchKernelGGL((sep_fused_kernel<BN, 3, false>), plan.grid, dim3(256), 0, st, q);
     else
-        hipLaunchKernelGGL((sep_fused_kernel<BN, 1, false>), grid, dim3(256), 0, st, q);
+        hipLaunchKernelGGL((sep_fused_kernel<BN, 1, false>), plan.grid, dim3(256), 0, st, q);
     return emd::check_launch("sep_fused_kernel");
-}
-
-// DUAL: 64 | 64 columns on 8 x 16 pixel tiles, or 128 | 128 columns on 4 x 16 pixel tiles
-int launch_dual(const SepParams& p, int B, hipStream_t st) {
-    SepParams q = p;
-    const int tiles_w = p.W / 16;
-    const bool wide = p.N > 64 || p.N2 > 64;
-    const int th = wide ? 4 : 8;
-    q.tpw = tiles_per_workgroup(tiles_w, (long)tiles_w * (p.H / th) * B);
-    q.stamps = g_knobs.sep_stamps;
-    const dim3 grid(tiles_w / q.tpw, p.H / th, B);
-    q.nt = sep_nt();
-    q.xcd = sep_xcd() && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    if (wide)
-        hipLaunchKernelGGL((sep_fused_kernel<256, 3, false, 4, true>), grid, dim3(256), 0, st, q);
-    else
-        hipLaunchKernelGGL((sep_fused_kernel<128, 3, false, 8, true>), grid, dim3(256), 0, st, q);
-    return emd::check_launch("sep_fused_kernel<dual>");
 }
 
 }  // namespace
 
-// 128 < Cout <= 256: one N tile of 256 columns on 4 x 16 pixel tiles (sep_fused_kernel<256, PASSES, false, 4>).  Against depthwise ->
-// HBM -> pointwise at [32,128,128,.]: 128 -> 256 256 vs 335 us, 256 -> 256 (+ residual) 537 vs 609 us, 384 -> 256 773 vs 734 us: the
-// rule takes it up to Cin = 256.  dev knob sep_wide: 0 = never, 2 = whenever it fits.
-inline int sep_wide() { return g_knobs.sep_wide; }
-
-// stride 2 (round 3): only the LDS-DMA pipelined kernel has the form (csrc/sep_pipe.hip, STRIDE = 2) -- even sizes with H % 8 == 0,
-// W % 32 == 0 (output tiles of 4 x 16 pixels), Cout <= 256; emd_sep3x3_fused_s2_f32
-static bool sep_s2_supported(int H, int W, int Cin, int Cout) {
-    // ask the kernel that has the form (its dev knob sep_pipe = 0 switches it off: hosts then take depthwise + pointwise, they do not get an error)
-    emd::SepParams q{};
-    q.H = H; q.W = W; q.Cin = Cin; q.N = Cout; q.stride = 2;
-    return Cout % 4 == 0 && Cout >= 4 && emd::sep_pipe_covers(q, 3);
-}
-
-extern "C" int emd_sep3x3_fused_supported(int H, int W, int Cin, int Cout, int stride, int rate) {
-    if (stride == 2 && rate == 1) return sep_s2_supported(H, W, Cin, Cout);
-    const bool wide = Cout > 128 && Cout <= 256 && (sep_wide() == 2 || (sep_wide() == 1 && Cin <= 256));
-    return stride == 1 && rate == 1 && H % 8 == 0 && W % 16 == 0 && Cin % 32 == 0 && Cin >= 32 && Cin <= 4096 && Cout % 4 == 0 &&
-           Cout >= 4 && (Cout <= 128 || wide);
-}
-
-static int sep_fused_entry(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
-                           const float* scale1, const float* shift1, const float* scale2, const float* shift2,
-                           const float* res, int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                           int precision, int reflect, emd_stream_t stream, const float* gen_a = nullptr,
-                           const float* gen_t = nullptr, int gen_act = 0, int out_split = 0) {
-    EMD_REQUIRE(x && dw && whi && scale1 && shift1 && y, EMD_E_INVALID, "emd_sep3x3_fused_f32: null pointer");
-    EMD_REQUIRE(precision == 1 || precision == 3, EMD_E_INVALID, "emd_sep3x3_fused_f32: bad precision");
-    EMD_REQUIRE(precision == 1 || wlo, EMD_E_INVALID, "emd_sep3x3_fused_f32: the split-bf16 mode needs the lo plane");
-    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_f32: scale2/shift2 pair");
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_sep3x3_fused_f32: bad shape");
-    EMD_REQUIRE(emd_sep3x3_fused_supported(H, W, Cin, Cout, 1, 1), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_f32: needs H%8==0, W%16==0, Cin%32==0, Cout%4==0, Cout<=128 or Cout<=256 with Cin<=256 (use emd_dw3x3_f32 + emd_conv1x1_f32)");
-    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_f32: B > 65535");
-    EMD_REQUIRE(9L * W * (ldy > ldres ? ldy : ldres) < (1L << 31), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_f32: 9 image rows of the output must span fewer than 2^31 floats");
-    EMD_REQUIRE(!out_split || (Cout % 32 == 0 && ldy % 32 == 0 && (reinterpret_cast<uintptr_t>(y) & 127u) == 0), EMD_E_ALIGN,
-                "emd_sep3x3_fused_out_f32: a split32 output needs Cout % 32 == 0, ldy % 32 == 0 and y 128-byte aligned");
-    EMD_REQUIRE((gen_a ? ldx >= 1 : (ldx % 4 == 0 && ldx >= Cin)) && ldy % 4 == 0 && ldy >= Cout &&
-                    (!res || (ldres % 4 == 0 && ldres >= Cout)),
-                EMD_E_ALIGN, "emd_sep3x3_fused_f32: pixel strides must be multiples of 4 and >= the channel count");
-    EMD_REQUIRE(!gen_a || (gen_t && emd::aligned16(gen_a) && emd::aligned16(gen_t) && gen_act >= 0 && gen_act <= 4 && gen_act != 3),
-                EMD_E_INVALID, "emd_sep3x3_fused_gen_f32: gen_a / gen_t must be 16-byte aligned device vectors, gen_act an EMD_ACT_* code");
-    EMD_REQUIRE(emd::aligned16(x) && emd::aligned16(dw) && emd::aligned16(whi) && (!wlo || emd::aligned16(wlo)) &&
-                    emd::aligned16(y) && (!res || emd::aligned16(res)) && emd::aligned16(scale1) &&
-                    emd::aligned16(shift1) && (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))),
-                EMD_E_ALIGN, "emd_sep3x3_fused_f32: pointers must be 16-byte aligned");
-    if (B == 0) return EMD_OK;
-    SepParams p{};
-    p.x = x; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = y; p.res = res;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
-    p.ldx = ldx; p.ldy = ldy; p.ldres = ldres; p.act = act; p.reflect = reflect; p.stride = 1;
-    p.gen_a = gen_a; p.gen_t = gen_t; p.gen_act = gen_act; p.out_split = out_split ? 1 : 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (emd::sep_pipe_covers(p, precision)) return emd::sep_pipe_launch(p, B, st);   // W % 32 == 0: the LDS-DMA pipelined kernel
-    if (Cout > 128) {   // the wide single-output form (dev): 4 x 16 pixel tiles, split-bf16 only, no generated input
-        EMD_REQUIRE(!gen_a, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_gen_f32: Cout > 128 has no generated-input form");
-        SepParams q = p;
-        const int tiles_w = p.W / 16;
-        q.tpw = tiles_per_workgroup(tiles_w, (long)tiles_w * (p.H / 4) * B);
-        q.stamps = g_knobs.sep_stamps;
-        const dim3 grid(tiles_w / q.tpw, p.H / 4, B);
-        q.nt = sep_nt();
-        q.xcd = sep_xcd() && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-        if (precision == 3) hipLaunchKernelGGL((sep_fused_kernel<256, 3, false, 4, false>), grid, dim3(256), 0, st, q);
+// The plan's route -> the instance (sep_entry.hip made the plan and filled q from it).  The order of the launch sites is the order of the
+// kernels in the code object.
+int emd::sep_fused_launch(const SepParams& q, const SepPlan& plan, hipStream_t st) {
+    const dim3 grid = plan.grid;
+    switch (plan.route) {
+    case kSepFusedWres:   // BN = 64, Cin <= 64, split-bf16: the pointwise weights stay in LDS for the workgroup's whole life
+        if (q.gen_a) hipLaunchKernelGGL((sep_fused_kernel<64, 3, true, 8, false, true>), grid, dim3(256), 0, st, q);
+        else hipLaunchKernelGGL((sep_fused_kernel<64, 3, false, 8, false, true>), grid, dim3(256), 0, st, q);
+        return emd::check_launch("sep_fused_kernel<resident W>");
+    case kSepGen9:   // the generated-input layer fed by the 1-channel image itself
+        if (q.Cin == 64) {
+            if (q.res) hipLaunchKernelGGL((sep_gen9_kernel<2, true>), grid, dim3(256), 0, st, q);
+            else hipLaunchKernelGGL((sep_gen9_kernel<2, false>), grid, dim3(256), 0, st, q);
+        } else if (q.res) {
+            hipLaunchKernelGGL((sep_gen9_kernel<1, true>), grid, dim3(256), 0, st, q);
+        } else {
+            hipLaunchKernelGGL((sep_gen9_kernel<1, false>), grid, dim3(256), 0, st, q);
+        }
+        return emd::check_launch("sep_gen9_kernel");
+    case kSepFusedDual:   // 64 | 64 columns on 8 x 16 pixel tiles, or 128 | 128 columns on 4 x 16 pixel tiles
+        if (plan.th == 4)
+            hipLaunchKernelGGL((sep_fused_kernel<256, 3, false, 4, true>), grid, dim3(256), 0, st, q);
+        else
+            hipLaunchKernelGGL((sep_fused_kernel<128, 3, false, 8, true>), grid, dim3(256), 0, st, q);
+        return emd::check_launch("sep_fused_kernel<dual>");
+    case kSepFusedWide:   // one N tile of 256 columns on 4 x 16 pixel tiles, no generated input
+        if (plan.passes == 3) hipLaunchKernelGGL((sep_fused_kernel<256, 3, false, 4, false>), grid, dim3(256), 0, st, q);
         else hipLaunchKernelGGL((sep_fused_kernel<256, 1, false, 4, false>), grid, dim3(256), 0, st, q);
         return emd::check_launch("sep_fused_kernel<wide>");
+    default:
+        return q.N <= 64 ? launch_bn<64>(q, plan, st) : launch_bn<128>(q, plan, st);
     }
-    return Cout <= 64 ? launch<64>(p, B, precision, st) : launch<128>(p, B, precision, st);
-}
-
-extern "C" int emd_sep3x3_fused_f32(const float* x, int ldx, const float* dw, const uint16_t* whi,
-                                    const uint16_t* wlo, const float* scale1, const float* shift1,
-                                    const float* scale2, const float* shift2, const float* res, int ldres,
-                                    float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                    int precision, emd_stream_t stream) {
-    return sep_fused_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, B, H, W, Cin, Cout, act,
-                           precision, 0, stream);
-}
-
-// The stride-1 block whose output feeds only a 3x3 convolution to one channel (deconv0_b -> deconv_final, machine_learning/denoiser.py:
-// 383-387), with that convolution's CHANNEL sum folded into the epilogue: y = the block's output (affine, activation, second affine,
-// + res, the arithmetic of emd_sep3x3_fused_f32) is not stored; z[t][b][h][w] = sum_c wfin[t][c] * y[b][h][w][c], t = 0..8, is -- nine
-// planes of B*H*W floats.  emd_cout1_gather9_f32 adds the nine shifted planes.  csrc/sep_pipe.hip (FOLD) only: there is no other form.
-extern "C" int emd_sep3x3_fused_fold_supported(int H, int W, int Cin, int Cout) {
-    emd::SepParams q{};
-    q.H = H; q.W = W; q.Cin = Cin; q.N = Cout; q.stride = 1; q.fold = 1;
-    return H >= 1 && W >= 1 && emd::sep_pipe_covers(q, 3);
-}
-
-extern "C" int emd_sep3x3_fused_fold_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
-                                         const float* scale1, const float* shift1, const float* scale2, const float* shift2,
-                                         const float* res, int ldres, const float* wfin, float* z, int B, int H, int W, int Cin, int Cout,
-                                         int act, emd_stream_t stream) {
-    EMD_REQUIRE(x && dw && whi && wlo && scale1 && shift1 && wfin && z, EMD_E_INVALID, "emd_sep3x3_fused_fold_f32: null pointer");
-    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_fold_f32: scale2/shift2 pair");
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_sep3x3_fused_fold_f32: bad shape");
-    EMD_REQUIRE(emd_sep3x3_fused_fold_supported(H, W, Cin, Cout), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_fold_f32: needs H%8==0, W%16==0, Cin%32==0, Cout==64 (use emd_sep3x3_fused_f32 + emd_conv3x3_cout1_f32)");
-    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_fold_f32: B > 65535");
-    EMD_REQUIRE(9L * W * (ldx > ldres ? ldx : ldres) < (1L << 31), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_fold_f32: 9 image rows of the input must span fewer than 2^31 floats");
-    EMD_REQUIRE(ldx % 4 == 0 && ldx >= Cin && (!res || (ldres % 4 == 0 && ldres >= Cout)), EMD_E_ALIGN,
-                "emd_sep3x3_fused_fold_f32: pixel strides must be multiples of 4 and >= the channel count");
-    EMD_REQUIRE(emd::aligned16(x) && emd::aligned16(dw) && emd::aligned16(whi) && emd::aligned16(wlo) && emd::aligned16(z) &&
-                    (!res || emd::aligned16(res)) && emd::aligned16(scale1) && emd::aligned16(shift1) && emd::aligned16(wfin) &&
-                    (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))),
-                EMD_E_ALIGN, "emd_sep3x3_fused_fold_f32: pointers must be 16-byte aligned");
-    if (B == 0) return EMD_OK;
-    SepParams p{};
-    p.x = x; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = nullptr; p.res = res;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
-    p.ldx = ldx; p.ldy = 0; p.ldres = ldres; p.act = act; p.stride = 1;
-    p.fold_w = wfin; p.fold_z = z; p.fold = 1;
-    return emd::sep_pipe_launch(p, B, static_cast<hipStream_t>(stream));
-}
-
-// The stride-2 separable block (strided_conv_block(stride=2), machine_learning/denoiser.py:258, :273, :288) in one launch: x [B,H,W,Cin]
-// (H, W even; TF SAME = no padding before, one pixel after) -> y [B,H/2,W/2,Cout].  Split-bf16.  Same arithmetic as emd_dw3x3_f32(stride 2)
-// followed by emd_conv1x1_f32; the depthwise result never exists in memory.
-struct GenRes {   // the generated residual of emd_sep3x3_fused_s2_genres_f32 (SepParams::rg_*)
-    const float* img;
-    int ld, stride;
-    const float* a;
-    const float* t;
-    int act;
-};
-
-static int sep_s2_entry(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
-                        const float* shift1, const float* scale2, const float* shift2, const float* res, int ldres, float* y, int ldy,
-                        int B, int H, int W, int Cin, int Cout, int act, int reflect, emd_stream_t stream, const GenRes* gr = nullptr);
-
-// The same block with the residual GENERATED in the epilogue: res[b][oy][ox][c] = f(img[b][oy * img_stride][ox * img_stride] * res_a[c] +
-// res_t[c]), f = relu6 if res_act else the identity -- what emd_cin1_f32(img, NULL, res_a, res_t, ..., stride = img_stride, res_act) writes
-// for a residual projection of the 1-channel image (residual0 of graph D, machine_learning/denoiser.py:252: a 1x1 conv of one channel is
-// rank 1), same fma, same clamp; that tensor is then neither written nor read.  Cout <= 128.
-extern "C" int emd_sep3x3_fused_s2_genres_supported(int H, int W, int Cin, int Cout) {
-    emd::SepParams q{};
-    q.H = H; q.W = W; q.Cin = Cin; q.N = Cout; q.stride = 2; q.rg_stride = 2;
-    return Cout % 4 == 0 && Cout >= 4 && 64 % (Cout / 4) == 0 && emd::sep_pipe_covers(q, 3);   // (Cout / 4 divides 64: emd_cin1_f32's rule)
-}
-
-extern "C" int emd_sep3x3_fused_s2_genres_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
-                                              const float* scale1, const float* shift1, const float* scale2, const float* shift2,
-                                              const float* img, int ldimg, int img_stride, const float* res_a, const float* res_t,
-                                              int res_act, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                              emd_stream_t stream) {
-    EMD_REQUIRE(img && res_a && res_t, EMD_E_INVALID, "emd_sep3x3_fused_s2_genres_f32: null pointer");
-    EMD_REQUIRE(ldimg >= 1 && img_stride >= 1, EMD_E_INVALID, "emd_sep3x3_fused_s2_genres_f32: image pitch and sampling stride must be >= 1");
-    // what emd_cin1_f32 takes (stride 1 or 2; Cout / 4 a divisor of 64: the predicate), so that the promised equivalence has a left-hand
-    // side; the pixel pitch is the one thing beyond it (d as channel 0 of a wider scratch tensor, as emd_sep3x3_fused_gen_f32 takes it)
-    EMD_REQUIRE(img_stride <= 2 && ldimg <= 64, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_s2_genres_f32: sampling stride 1 or 2, image pitch <= 64");
-    EMD_REQUIRE(emd_sep3x3_fused_s2_genres_supported(H, W, Cin, Cout), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_s2_genres_f32: needs H%8==0, W%32==0, Cin%32==0, Cout%4==0, Cout<=128 (use emd_cin1_f32 + emd_sep3x3_fused_s2_f32)");
-    const GenRes gr{img, ldimg, img_stride, res_a, res_t, res_act ? 1 : 0};
-    return sep_s2_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, nullptr, 0, y, ldy, B, H, W, Cin, Cout, act, 0, stream, &gr);
-}
-
-extern "C" int emd_sep3x3_fused_s2_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
-                                       const float* scale1, const float* shift1, const float* scale2, const float* shift2,
-                                       const float* res, int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                       emd_stream_t stream) {
-    return sep_s2_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, B, H, W, Cin, Cout, act, 0, stream);
-}
-
-// The same with the depthwise stage on the tf.pad(REFLECT, 1) image and VALID padding: graph G's strided_conv_block(stride 2,
-// pad_size = (1, 1)) (misc_py/gan-infilling-100.py:205-243, the down-sampling layers :345-352): output pixel (i, j) reads input rows
-// 2 i - 1 .. 2 i + 1 (row -1 = row 1); on even sizes nothing is read beyond the last row / column.
-extern "C" int emd_sep3x3_fused_s2_reflect_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
-                                               const float* scale1, const float* shift1, const float* scale2, const float* shift2,
-                                               const float* res, int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout,
-                                               int act, emd_stream_t stream) {
-    return sep_s2_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, B, H, W, Cin, Cout, act, 1, stream);
-}
-
-static int sep_s2_entry(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
-                        const float* shift1, const float* scale2, const float* shift2, const float* res, int ldres, float* y, int ldy,
-                        int B, int H, int W, int Cin, int Cout, int act, int reflect, emd_stream_t stream, const GenRes* gr) {
-    EMD_REQUIRE(x && dw && whi && wlo && scale1 && shift1 && y, EMD_E_INVALID, "emd_sep3x3_fused_s2_f32: null pointer");
-    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_s2_f32: scale2/shift2 pair");
-    EMD_REQUIRE(B >= 0 && H >= 2 && W >= 2, EMD_E_INVALID, "emd_sep3x3_fused_s2_f32: bad shape");
-    EMD_REQUIRE(sep_s2_supported(H, W, Cin, Cout), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_s2_f32: needs H%8==0, W%32==0, Cin%32==0, Cout%4==0, Cout<=256 (use emd_dw3x3_f32 + emd_conv1x1_f32)");
-    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_s2_f32: B > 65535");
-    EMD_REQUIRE(ldx % 4 == 0 && ldx >= Cin && ldy % 4 == 0 && ldy >= Cout && (!res || (ldres % 4 == 0 && ldres >= Cout)), EMD_E_ALIGN,
-                "emd_sep3x3_fused_s2_f32: pixel strides must be multiples of 4 and >= the channel count");
-    EMD_REQUIRE(9L * W * (ldy > ldres ? ldy : ldres) < (1L << 31), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_s2_f32: 9 image rows of the output must span fewer than 2^31 floats");
-    EMD_REQUIRE(emd::aligned16(x) && emd::aligned16(dw) && emd::aligned16(whi) && emd::aligned16(wlo) && emd::aligned16(y) &&
-                    (!res || emd::aligned16(res)) && emd::aligned16(scale1) && emd::aligned16(shift1) &&
-                    (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))),
-                EMD_E_ALIGN, "emd_sep3x3_fused_s2_f32: pointers must be 16-byte aligned");
-    if (B == 0) return EMD_OK;
-    SepParams p{};
-    p.x = x; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = y; p.res = res;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
-    p.ldx = ldx; p.ldy = ldy; p.ldres = ldres; p.act = act; p.stride = 2; p.reflect = reflect ? 1 : 0;
-    if (gr) {
-        p.rg_x = gr->img; p.rg_ld = gr->ld; p.rg_stride = gr->stride; p.rg_a = gr->a; p.rg_t = gr->t; p.rg_act = gr->act;
-    }
-    EMD_REQUIRE(emd::sep_pipe_covers(p, 3), EMD_E_UNSUPPORTED, "emd_sep3x3_fused_s2_f32: the pipelined kernel is switched off (dev knob sep_pipe)");
-    return emd::sep_pipe_launch(p, B, static_cast<hipStream_t>(stream));
-}
-
-// emd_sep3x3_fused_f32 writing y as a split32 tensor (Cout % 32 == 0; pitch ldy 4-byte units, % 32): the producer of a split32
-// convolution's input (graph D: deconv1_b -> deconv1to0) then writes no fp32 activation and needs no converter pass.
-extern "C" int emd_sep3x3_fused_out_f32(const float* x, int ldx, const float* dw, const uint16_t* whi,
-                                        const uint16_t* wlo, const float* scale1, const float* shift1,
-                                        const float* scale2, const float* shift2, const float* res, int ldres,
-                                        void* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                        emd_stream_t stream) {
-    return sep_fused_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, static_cast<float*>(y), ldy, B, H, W, Cin,
-                           Cout, act, 3, 0, stream, nullptr, nullptr, 0, 1);
-}
-
-// The same with the depthwise stage reading the tf.pad(REFLECT, 1) border instead of zeros: graph G's
-// strided_conv_block(stride 1, pad_size=(1,1)) (misc_py/gan-infilling-100.py:205-243); act is usually EMD_ACT_LEAKY.
-extern "C" int emd_sep3x3_fused_reflect_f32(const float* x, int ldx, const float* dw, const uint16_t* whi,
-                                            const uint16_t* wlo, const float* scale1, const float* shift1,
-                                            const float* scale2, const float* shift2, const float* res, int ldres,
-                                            float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                            int precision, emd_stream_t stream) {
-    return sep_fused_entry(x, ldx, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, B, H, W, Cin, Cout, act,
-                           precision, 1, stream);
-}
-
-// The fused separable conv on a GENERATED input: the layer's Cin-channel input is act(d[pixel] * gen_a[c] + gen_t[c]), d a
-// one-value-per-pixel tensor (pitch ldd floats) -- what emd_cin1_f32 / emd_cin1_k7_reflect_f32 would write out for the layer
-// that follows the one fed by the 1-channel image (cnn0 -> cnn0_last, machine_learning/denoiser.py:252-255; the generator's first
-// two layers, misc_py/gan-infilling-100.py:343-349).  The Cin-channel tensor never exists in memory.
-extern "C" int emd_sep3x3_fused_gen_f32(const float* d, int ldd, const float* gen_a, const float* gen_t, int gen_act,
-                                        const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
-                                        const float* shift1, const float* scale2, const float* shift2, const float* res,
-                                        int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                        int precision, int reflect, emd_stream_t stream) {
-    EMD_REQUIRE(gen_a && gen_t, EMD_E_INVALID, "emd_sep3x3_fused_gen_f32: null gen_a / gen_t");
-    return sep_fused_entry(d, ldd, dw, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, B, H, W, Cin, Cout, act,
-                           precision, reflect, stream, gen_a, gen_t, gen_act);
-}
-
-// The same layer taking the 1-channel image and the nine taps of its depthwise conv instead of d (graph D's cnn0 -> cnn0_last,
-// machine_learning/denoiser.py:252-255): d = what emd_cin1_f32(img, w9, (1,0,0,0), 0, act = 0) writes is formed per tile inside the
-// kernel, so neither d nor the Cin-channel tensor goes through memory.  The rule is a function of the layer's shape alone.
-extern "C" int emd_sep3x3_fused_gen9_supported(int H, int W, int Cin, int Cout) {
-    return H >= 8 && W >= 16 && H % 8 == 0 && W % 16 == 0 && (Cin == 32 || Cin == 64) && Cout % 4 == 0 && Cout >= 4 && Cout <= 64;
-}
-
-extern "C" int emd_sep3x3_fused_gen9_f32(const float* img, const float* w9, const float* gen_a, const float* gen_t, int gen_act,
-                                         const float* dw, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
-                                         const float* shift1, const float* scale2, const float* shift2, const float* res,
-                                         int ldres, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int act,
-                                         int precision, int reflect, emd_stream_t stream) {
-    EMD_REQUIRE(img && w9 && gen_a && gen_t && dw && whi && wlo && scale1 && shift1 && y, EMD_E_INVALID,
-                "emd_sep3x3_fused_gen9_f32: null pointer");
-    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "emd_sep3x3_fused_gen9_f32: scale2/shift2 pair");
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_sep3x3_fused_gen9_f32: bad shape");
-    EMD_REQUIRE(gen_act == EMD_ACT_RELU6 && !reflect && precision == 3 && emd_sep3x3_fused_gen9_supported(H, W, Cin, Cout),
-                EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_gen9_f32: needs relu6 generation, zero padding, split-bf16, H%8==0, W%16==0, Cin 32 or 64, Cout%4==0, "
-                "Cout<=64 (use emd_cin1_f32 + emd_sep3x3_fused_gen_f32)");
-    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_fused_gen9_f32: B > 65535");
-    EMD_REQUIRE(9L * W * (ldy > ldres ? ldy : ldres) < (1L << 31), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_fused_gen9_f32: 9 image rows of the output must span fewer than 2^31 floats");
-    EMD_REQUIRE(ldy % 4 == 0 && ldy >= Cout && (!res || (ldres % 4 == 0 && ldres >= Cout)), EMD_E_ALIGN,
-                "emd_sep3x3_fused_gen9_f32: pixel strides must be multiples of 4 and >= the channel count");
-    EMD_REQUIRE(emd::aligned16(gen_a) && emd::aligned16(gen_t) && emd::aligned16(dw) && emd::aligned16(whi) && emd::aligned16(wlo) &&
-                    emd::aligned16(y) && (!res || emd::aligned16(res)) && emd::aligned16(scale1) && emd::aligned16(shift1) &&
-                    (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))),
-                EMD_E_ALIGN, "emd_sep3x3_fused_gen9_f32: pointers (but img, w9) must be 16-byte aligned");
-    if (B == 0) return EMD_OK;
-    SepParams p{};
-    p.x = img; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = y; p.res = res;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
-    p.ldx = 1; p.ldy = ldy; p.ldres = ldres; p.act = act; p.stride = 1;
-    p.gen_a = gen_a; p.gen_t = gen_t; p.gen_act = gen_act; p.gen_w9 = w9;
-    return launch_gen9(p, B, static_cast<hipStream_t>(stream));
-}
-
-// dev hook (include/emdenoise_dev.h), host only: the shape rule of the whole-chunk instance of sep_pipe2.hip -- no batch argument
-extern "C" int emd_debug_sep_pipe2_chunk_covers(int H, int W, int Cin, int Cout, int Cout2) {
-    if (!emd_sep3x3_dual_supported(H, W, Cin, Cout, Cout2)) return 0;
-    emd::SepParams p{};
-    p.H = H; p.W = W; p.Cin = Cin; p.N = Cout; p.N2 = Cout2; p.stride = 1;
-    return emd::sep_pipe2_chunk_covers(p) ? 1 : 0;
-}
-
-// dev hook (not in the header): per-workgroup phase cycle sums for tools/sep_bench.py
-extern "C" void emd_debug_sep_stamps(void* buf) { g_knobs.sep_stamps = static_cast<long long*>(buf); }
-
-// The decoder pair "separable conv + 1x1 residual projection of the same input" in ONE launch (machine_learning/denoiser.py:356-359,
-// :368-371, :380-383: deconv*_a = strided_conv_block(concat) and residual*_d = conv_block_not_sep(concat, kernel_size=1)):
-//   y  = relu6(BN2(BN1(pointwise(depthwise3x3(x)))))        the fused separable conv of emd_sep3x3_fused_f32 (scale1 / shift1)
-//   y2 = relu6(BN(x * W2 + bias))                           a 1x1 conv of x itself (scale_b / shift_b: bias and BN folded)
-// Both read the 384- or 128-channel input, the largest tensors of the decoder; fused, it comes from HBM once.  The input patch of
-// a tile is staged in LDS for the depthwise stage anyway; its centre pixels are the projection's A operand.
-extern "C" int emd_sep3x3_dual_supported(int H, int W, int Cin, int Cout, int Cout2) {
-    const bool wide = Cout > 64 || Cout2 > 64;
-    return H % (wide ? 4 : 8) == 0 && W % 16 == 0 && Cin % 32 == 0 && Cin >= 32 && Cin <= 4096 && Cout % 4 == 0 && Cout2 % 4 == 0 &&
-           Cout >= 4 && Cout2 >= 4 && Cout <= 128 && Cout2 <= 128;
-}
-
-// 1 when the one-launch form is the faster route for the shape (a pure function of the shape; graph D's decoder pairs): always for two
-// outputs of up to 64 channels; for wider ones only where the LDS-DMA pipelined kernel takes the launch (W % 32 == 0, H % 8 == 0:
-// 384 -> 128 | 128 at 256^2 2.07 ms against 1.32 + 0.99 for the pair; the 4 x 16-tile form of sep_fused.hip is slower than the pair).
-extern "C" int emd_sep3x3_dual_preferred(int H, int W, int Cin, int Cout, int Cout2) {
-    if (!emd_sep3x3_dual_supported(H, W, Cin, Cout, Cout2)) return 0;
-    if (Cout <= 64 && Cout2 <= 64) return 1;
-    return H % 8 == 0 && W % 32 == 0;
-}
-
-extern "C" int emd_sep3x3_dual_f32(const float* x, int ldx, const float* dw, const uint16_t* whi, const uint16_t* wlo,
-                                   const float* scale1, const float* shift1, float* y, int ldy, const uint16_t* w2hi,
-                                   const uint16_t* w2lo, const float* scale_b, const float* shift_b, float* y2, int ldy2, int B, int H,
-                                   int W, int Cin, int Cout, int Cout2, int act, emd_stream_t stream) {
-    EMD_REQUIRE(x && dw && whi && wlo && scale1 && shift1 && y && w2hi && w2lo && scale_b && shift_b && y2, EMD_E_INVALID,
-                "emd_sep3x3_dual_f32: null pointer");
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_sep3x3_dual_f32: bad shape");
-    EMD_REQUIRE(emd_sep3x3_dual_supported(H, W, Cin, Cout, Cout2), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_dual_f32: needs H%8==0 (H%4==0 above 64 output channels), W%16==0, Cin%32==0, Cout%4==0, Cout<=128 (both outputs)");
-    EMD_REQUIRE(B <= 65535, EMD_E_UNSUPPORTED, "emd_sep3x3_dual_f32: B > 65535");
-    EMD_REQUIRE(9L * W * (ldy > ldy2 ? ldy : ldy2) < (1L << 31), EMD_E_UNSUPPORTED,
-                "emd_sep3x3_dual_f32: 9 image rows of an output must span fewer than 2^31 floats");
-    EMD_REQUIRE(ldx % 4 == 0 && ldx >= Cin && ldy % 4 == 0 && ldy >= Cout && ldy2 % 4 == 0 && ldy2 >= Cout2, EMD_E_ALIGN,
-                "emd_sep3x3_dual_f32: pixel strides must be multiples of 4 and >= the channel count");
-    EMD_REQUIRE(emd::aligned16(x) && emd::aligned16(dw) && emd::aligned16(whi) && emd::aligned16(wlo) && emd::aligned16(w2hi) &&
-                    emd::aligned16(w2lo) && emd::aligned16(y) && emd::aligned16(y2) && emd::aligned16(scale1) && emd::aligned16(shift1) &&
-                    emd::aligned16(scale_b) && emd::aligned16(shift_b),
-                EMD_E_ALIGN, "emd_sep3x3_dual_f32: pointers must be 16-byte aligned");
-    EMD_REQUIRE(y != y2, EMD_E_INVALID, "emd_sep3x3_dual_f32: the two outputs alias");
-    if (B == 0) return EMD_OK;
-    SepParams p{};
-    p.x = x; p.dw = dw; p.Whi = whi; p.Wlo = wlo; p.y = y; p.res = nullptr;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = nullptr; p.shift2 = nullptr;
-    p.H = H; p.W = W; p.Cin = Cin; p.Cpad = (Cin + kBK - 1) / kBK * kBK; p.N = Cout;
-    p.ldx = ldx; p.ldy = ldy; p.ldres = 0; p.act = act; p.reflect = 0; p.stride = 1;
-    p.W2hi = w2hi; p.W2lo = w2lo; p.y2 = y2; p.scale_b = scale_b; p.shift_b = shift_b; p.N2 = Cout2; p.ldy2 = ldy2;
-    if (emd::sep_pipe_covers(p, 3)) return emd::sep_pipe_launch(p, B, static_cast<hipStream_t>(stream));
-    return launch_dual(p, B, static_cast<hipStream_t>(stream));
 }

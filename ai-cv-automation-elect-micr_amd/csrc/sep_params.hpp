@@ -1,5 +1,7 @@
-// Parameter block shared by the fused separable-convolution kernels (sep_fused.hip: register-staged loader, any W % 16 == 0;
-// sep_pipe.hip: LDS-DMA ring, W % 32 == 0) and the dev knobs that choose between them.
+// Parameter block shared by the fused separable-convolution kernels -- sep_fused.hip: register-staged loader, 8 x 16 (4 x 16) pixel tiles;
+// sep_pipe.hip: LDS-DMA ring, 8 or 4 waves on 8 x 32 / 8 x 16 tiles, stride 1 and 2; sep_pipe2.hip: its software-pipelined form and the
+// whole-chunk instance -- and the host-side plan (route, geometry) that sep_entry.hip makes for a launch and each kernel file maps to an
+// instance.  The entry points, their checks and every routing rule are in sep_entry.hip.
 #pragma once
 
 #include "mfma_common.hpp"
@@ -59,15 +61,39 @@ struct SepParams {
 inline bool folded(const SepParams& p) { return p.N2 == 0 && p.fold != 0; }   // a two-output launch keeps its pitch in the same word
 static_assert(sizeof(SepParams) == 232, "SepParams: the rg_* fields fill padding and share storage; see above before adding a field");
 
-// sep_pipe.hip: true when the LDS-DMA pipelined kernel covers the launch (stride 1, split-bf16, no generated input, W % 32 == 0)
-bool sep_pipe_covers(const SepParams& p, int precision);
-// sep_pipe.hip: launches it; p.N2 > 0 selects the two-output (DUAL) instances
-int sep_pipe_launch(const SepParams& p, int B, hipStream_t st);
-// sep_pipe2.hip: the software-pipelined form (8 x 32 tiles, stride 1): sep_pipe_launch hands it the shapes the rule below gives it
-bool sep_pipe2_covers(const SepParams& p);
-int sep_pipe2_launch(const SepParams& p, int B, hipStream_t st);
-// sep_pipe2.hip: its whole-chunk instance (round 10; two outputs on the 256-column tile): compile-time slot parity, one role per wave
-bool sep_pipe2_chunk_covers(const SepParams& p);
-int sep_pipe2_chunk_launch(const SepParams& p, int B, hipStream_t st);
+// Which kernel takes a launch.  sep_entry.hip (sep_plan) holds the rules; emd_debug_sep_plan reports these numbers (sep_fused.hip's
+// routes come first: sep_plan tells the files apart by the order).
+enum SepRoute {
+    kSepNone = 0,
+    kSepFused,        // sep_fused.hip: 64 / 128 columns, weights per chunk
+    kSepFusedWres,    //   64 columns, Cin <= 64: weights resident in LDS
+    kSepFusedWide,    //   one output of 129 .. 256 columns on 4 x 16 tiles
+    kSepFusedDual,    //   two outputs
+    kSepGen9,         //   sep_gen9_kernel
+    kSepPipe,         // sep_pipe.hip
+    kSepPipe2,        // sep_pipe2.hip, sep_pipe2_kernel
+    kSepPipe2Chunk,   //   sep_pipe2_chunk_kernel
+};
+
+// Host side: everything a launch is made of besides the caller's pointers and shape.
+struct SepPlan {
+    int route;            // SepRoute
+    int nw;               // waves per workgroup
+    int tw, th;           // output pixels of a tile
+    int tpw;
+    dim3 grid;
+    int xcd, nt;          // (nt is set on the sep_fused routes only)
+    int mode;             // sep_pipe schedule: 1 = the patch one step ahead, 0 = two
+    int epi;              // epilogue width the instance is compiled for (0: sep_fused has one form)
+    int passes;           // sep_fused: MFMA passes = the precision
+    long long* stamps;    // what the kernel gets as SepParams::stamps / ablate
+    int ablate;
+};
+SepPlan sep_plan(const SepParams& p, int B, int precision);   // a pure function of its arguments and g_knobs
+
+// One per kernel file: q is the caller's block with the plan's tpw, xcd, nt, stamps and ablate filled in; maps plan to an instance.
+int sep_fused_launch(const SepParams& q, const SepPlan& plan, hipStream_t st);   // the kSepFused* routes and kSepGen9
+int sep_pipe_launch(const SepParams& q, const SepPlan& plan, hipStream_t st);
+int sep_pipe2_launch(const SepParams& q, const SepPlan& plan, hipStream_t st);   // kSepPipe2 and kSepPipe2Chunk
 
 }  // namespace emd

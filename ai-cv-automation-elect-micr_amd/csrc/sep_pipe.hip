@@ -915,113 +915,36 @@ int launch_bn(const SepParams& q, dim3 grid, int mode, int nw, hipStream_t st) {
 }
 
 template <int EPI>
-int launch_epi(const SepParams& p, const SepParams& q, dim3 grid, int mode, int nw, hipStream_t st) {
-    if (p.stride == 2) return p.N <= 128 ? launch_s2<128, EPI>(q, grid, mode, st) : launch_s2<256, EPI>(q, grid, mode, st);
-    if (p.N2 > 0) {
-        const bool wide = p.N > 64 || p.N2 > 64;
+int launch_epi(const SepParams& q, dim3 grid, int mode, int nw, hipStream_t st) {
+    if (q.stride == 2) return q.N <= 128 ? launch_s2<128, EPI>(q, grid, mode, st) : launch_s2<256, EPI>(q, grid, mode, st);
+    if (q.N2 > 0) {
+        const bool wide = q.N > 64 || q.N2 > 64;
         if (wide) return launch_bn<256, true, EPI>(q, grid, 1, 8, st);
         return launch_bn<128, true, EPI>(q, grid, 1, nw, st);
     }
-    if (p.N <= 64) return launch_bn<64, false, EPI>(q, grid, mode, nw, st);
-    if (p.N <= 128) return launch_bn<128, false, EPI>(q, grid, mode, nw, st);
+    if (q.N <= 64) return launch_bn<64, false, EPI>(q, grid, mode, nw, st);
+    if (q.N <= 128) return launch_bn<128, false, EPI>(q, grid, mode, nw, st);
     return launch_bn<256, false, EPI>(q, grid, mode, nw, st);
 }
 
 }  // namespace
 
-namespace emd {
-
-// 4-wave form (8 x 16 tiles, 80 KiB of LDS or less: two workgroups per CU, whose phases -- DMA wait, depthwise stage, MFMAs, epilogue --
-// interleave): instances up to 128 output columns (one output, fp32 or split32) and 64 | 64 (two outputs).  Rule: wherever there is an
-// instance.  Measured on graph D's shapes (tools/sep_epi_bench.py with SEB_KNOB=sep_nw, [32, ., ., .], two boxes): the two-output launch
-// 512^2 x 128 -> 64 | 64 2078 -> 1892 us, 2084 -> 1921; 64 -> 64 961 -> 859, 943 -> 873; 128 -> 64 1382 -> 1354; 64 -> 64 with a
-// residual 1161 / 1288 -> 1212 / 1210; 256^2 x 128 -> 128 480 -> 467, 486 -> 469; with residual and split32 output 669 -> 647 / 653;
-// 384 -> 128 1155 -> 1144; the whole D step 23.36 -> 23.24 ms in one process (tools/d_knob_ab.py).  Dev knob sep_nw = 8 / 4 forces.
-static bool use_nw4(const SepParams& p) {
-    if (g_knobs.sep_nw == 8 || p.stride == 2) return false;
-    return p.N2 > 0 ? (p.N <= 64 && p.N2 <= 64) : (p.N <= 128 && !(p.out_split && p.N <= 64));    // instances: launch_mode
-}
-
-bool sep_pipe_covers(const SepParams& p, int precision) {
-    if (!g_knobs.sep_pipe || precision != 3) return false;
-    if (folded(p))    // folded final conv: the 4-wave 64-column instance only -- deconv0_b of graph D and its likes
-        return p.stride == 1 && p.H % 8 == 0 && p.W % 16 == 0 && p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 4064 && p.N == 64 && p.N2 == 0 &&
-               !p.out_split && !p.gen_a && !p.rg_stride && !p.reflect && g_knobs.sep_nw != 8;
-    if (p.gen_a)   // generated input (round 4, opt-in: dev knob sep_gen_pipe): the 4-wave 64-column instance only -- cnn0_last of graphs D / X and its likes
-        return g_knobs.sep_gen_pipe && p.stride == 1 && p.H % 8 == 0 && p.W % 16 == 0 && (p.Cin == 32 || p.Cin == 64) && p.N <= 64 && p.N2 == 0 &&
-               !p.out_split && !p.res && g_knobs.sep_nw != 8;
-    if (p.rg_stride && (p.stride != 2 || p.N2 > 0 || p.N > 128 || p.res || p.reflect)) return false;   // generated residual: the stride-2 128-column instance only
-    if (p.stride == 2)   // output tiles of 4 x 16 pixels: H % 8 == 0, W % 32 == 0 (input sizes); one fp32 output of up to 256 channels
-        return p.H % 8 == 0 && p.W % 32 == 0 && p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 4064 && p.N2 == 0 && !p.out_split && p.N <= 256;
-    if (p.H % 8 != 0 || p.W % (use_nw4(p) ? 16 : 32) != 0 || p.Cin % 32 != 0 || p.Cin < 32 || p.Cin > 4064) return false;
-    if (p.N2 > 0) return p.N <= 128 && p.N2 <= 128 && !p.out_split && !p.res && !p.scale2;
-    if (p.out_split && p.N <= 64) return false;
-    return p.N <= 256;
-}
-
-// Which launches go to the software-pipelined kernel (sep_pipe2.hip; same bits).  Dev knob sep_pipe2: 0 (default) none, 1 the two-output
-// launches with more than 64 columns per output (deconv1_a + residual1_d, 384 -> 128 | 128: the one shape whose slots are matrix-core
-// bound), 2 everything it has an instance for (the parity tests).  Measured (profiles/r04_experiments.txt 3): standalone at parity on
-// that shape (2034 / 2070 us against 2059 / 2004 on two boxes), 5-50 % SLOWER on every one-output shape -- where this file's 4-wave
-// two-workgroups-per-CU form wins: both kernels are bound by instruction issue and by phases no other wave fills, and the pipelined one
-// issues ~1.9 x the instructions per chunk -- and graph D 22.10 ms with 0, 22.26 with 1, 23.07 with 2 in one process.  A forced 4-wave
-// form (dev knob sep_nw = 4) always means this file's kernel.
-static bool use_pipe2(const SepParams& p) {
-    if (p.gen_a || p.rg_stride || folded(p)) return false;
-    if (!g_knobs.sep_pipe2 || g_knobs.sep_ablate || g_knobs.sep_nw == 4 || !sep_pipe2_covers(p)) return false;
-    if (g_knobs.sep_pipe2 == 2) return true;
-    return p.N2 > 0 && (p.N > 64 || p.N2 > 64);
-}
-
-// The whole-chunk instance of sep_pipe2.hip (round 10; same bits): the two-output launches on the 256-column tile (deconv1_a + residual1_d of
-// graph D), by the layer's shape alone.  Dev knob sep_pipe2_chunk: 1 takes it, 0 keeps this file's lockstep kernel, -1 (default) = kChunkRule;
-// the older knob sep_pipe2 (run-time parity instances) and the forced forms go first.
-constexpr int kChunkRule = 1;
-static bool use_pipe2_chunk(const SepParams& p) {
-    const int on = g_knobs.sep_pipe2_chunk < 0 ? kChunkRule : g_knobs.sep_pipe2_chunk;
-    if (!on || g_knobs.sep_pipe2 || g_knobs.sep_ablate || g_knobs.sep_nw == 4 || g_knobs.sep_stamps) return false;
-    return sep_pipe2_chunk_covers(p);
-}
-
-int sep_pipe_launch(const SepParams& p, int B, hipStream_t st) {
-    if (use_pipe2(p)) return sep_pipe2_launch(p, B, st);
-    if (use_pipe2_chunk(p)) return sep_pipe2_chunk_launch(p, B, st);
-    SepParams q = p;
-    const bool s2 = p.stride == 2;
-    const int nw = (p.gen_a || folded(p) || (!s2 && use_nw4(p))) ? 4 : 8, tw = s2 ? 16 : 4 * nw, th = s2 ? 4 : 8;
-    const int Ho = p.H / (s2 ? 2 : 1), Wo = p.W / (s2 ? 2 : 1);
-    const int tiles_w = Wo / tw;
-    const long wgs1 = (long)tiles_w * (Ho / th) * B;
-    int tpw = 1;   // several tiles per workgroup (the DMA ring runs on across them) where >= 4 workgroups per CU remain
-    for (int t = 8; t >= 2; t >>= 1)
-        if (tiles_w % t == 0 && wgs1 / t >= 1024 * (8 / nw)) { tpw = t; break; }
-    if (g_knobs.sep_tpw > 0 && tiles_w % g_knobs.sep_tpw == 0) tpw = g_knobs.sep_tpw;
-    q.tpw = tpw;
-    q.stamps = g_knobs.sep_stamps;
-    q.ablate = g_knobs.sep_ablate;
-    const dim3 grid(tiles_w / tpw, Ho / th, B);
-    q.xcd = g_knobs.sep_xcd && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    // schedule (see the kernel): rule = the patch two steps ahead; one step ahead for two outputs, with a residual (its loads then
-    // queue behind one DMA group instead of two) and in the 4-wave form; the dev knob sep_mode (0 / 1) overrides
-    const int mode = g_knobs.sep_mode >= 0 ? g_knobs.sep_mode : ((nw == 4 || p.res) ? 1 : 0);
-    // epilogue (see the kernel): per-channel dword stores, 2.7 % over graph D's twelve shapes (tools/sep_epi_bench.py; the two-output
-    // launches 5 %) -- except with a residual on more than 128 columns (cnn2_last: 445 against 430 us for the transposed 16-byte form)
-    if (folded(p)) {   // one epilogue form (the knob epi_width does not apply); both schedules
-        if (mode == 1) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 1, false, false, true>), grid, dim3(256), 0, st, q);
+// The plan's waves, schedule and epilogue width -> the instance (sep_entry.hip made the plan and filled q from it).
+int emd::sep_pipe_launch(const SepParams& q, const SepPlan& plan, hipStream_t st) {
+    const dim3 grid = plan.grid;
+    if (folded(q)) {   // one epilogue form; both schedules
+        if (plan.mode == 1) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 1, false, false, true>), grid, dim3(256), 0, st, q);
         else hipLaunchKernelGGL((sep_pipe_kernel<64, false, 0, false, 4, 1, 1, false, false, true>), grid, dim3(256), 0, st, q);
         return emd::check_launch("sep_pipe_kernel<folded final conv>");
     }
-    if (p.gen_a) {
-        if (g_knobs.epi_width == 4) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 4, true>), grid, dim3(256), 0, st, q);
+    if (q.gen_a) {
+        if (plan.epi == 4) hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 4, true>), grid, dim3(256), 0, st, q);
         else hipLaunchKernelGGL((sep_pipe_kernel<64, false, 1, false, 4, 1, 1, true>), grid, dim3(256), 0, st, q);
         return emd::check_launch("sep_pipe_kernel<generated input>");
     }
-    if (p.rg_stride) {   // one instance: the schedule and the epilogue the rule gives the same layer with a residual tensor (the knobs do not apply)
+    if (q.rg_stride) {   // one instance
         hipLaunchKernelGGL((sep_pipe_kernel<128, false, 1, false, 8, 2, 1, false, true>), grid, dim3(512), 0, st, q);
         return emd::check_launch("sep_pipe_kernel<stride 2, generated residual>");
     }
-    const int epi = g_knobs.epi_width ? g_knobs.epi_width : ((p.res && p.N > 128) ? 4 : 1);
-    return epi == 4 ? launch_epi<4>(p, q, grid, mode, nw, st) : launch_epi<1>(p, q, grid, mode, nw, st);
+    return plan.epi == 4 ? launch_epi<4>(q, grid, plan.mode, plan.nw, st) : launch_epi<1>(q, grid, plan.mode, plan.nw, st);
 }
-
-}  // namespace emd

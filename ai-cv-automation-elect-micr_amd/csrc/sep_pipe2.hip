@@ -1103,64 +1103,21 @@ int launch2(const SepParams& q, dim3 grid, hipStream_t st) {
 
 }  // namespace
 
-namespace emd {
-
-// Shapes the software-pipelined kernel has an instance for: stride 1, 8 x 32 tiles (H % 8 == 0, W % 32 == 0), split-bf16, one output of up
-// to 256 channels (fp32, or split32 from 128 channels on) or two of up to 128 each (no residual / second affine there).
-bool sep_pipe2_covers(const SepParams& p) {
-    if (p.stride != 1 || p.gen_a || p.H % 8 != 0 || p.W % 32 != 0 || p.Cin % 32 != 0 || p.Cin < 32 || p.Cin > 4064) return false;
-    if (p.N2 > 0) return p.N <= 128 && p.N2 <= 128 && !p.out_split && !p.res && !p.scale2;
-    if (p.out_split && p.N <= 64) return false;
-    return p.N <= 256;
-}
-
-int sep_pipe2_launch(const SepParams& p, int B, hipStream_t st) {
-    SepParams q = p;
-    const int tiles_w = p.W / 32;
-    const long wgs1 = (long)tiles_w * (p.H / 8) * B;
-    int tpw = 1;   // several tiles per workgroup (the DMA ring runs on across them) where >= 4 workgroups per CU remain
-    for (int t = 8; t >= 2; t >>= 1)
-        if (tiles_w % t == 0 && wgs1 / t >= 1024) { tpw = t; break; }
-    if (g_knobs.sep_tpw > 0 && tiles_w % g_knobs.sep_tpw == 0) tpw = g_knobs.sep_tpw;
-    q.tpw = tpw;
-    q.stamps = g_knobs.sep_stamps;
-    q.ablate = g_knobs.sep_stamp_wave & 7;
-    const dim3 grid(tiles_w / tpw, p.H / 8, B);
-    q.xcd = g_knobs.sep_xcd && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    const int epi = g_knobs.epi_width ? g_knobs.epi_width : ((p.res && p.N > 128) ? 4 : 1);
-    if (p.N2 > 0) {
-        if (p.N > 64 || p.N2 > 64) return launch2<256, true, false, 1>(q, grid, st);
-        return launch2<128, true, false, 1>(q, grid, st);
+// The plan's route and epilogue width -> the instance (sep_entry.hip made the plan and filled q from it).  Only the 256-column one-output
+// instances of sep_pipe2_kernel come in both widths.
+int emd::sep_pipe2_launch(const SepParams& q, const SepPlan& plan, hipStream_t st) {
+    const dim3 grid = plan.grid;
+    if (plan.route == kSepPipe2) {
+        if (q.N2 > 0) {
+            if (q.N > 64 || q.N2 > 64) return launch2<256, true, false, 1>(q, grid, st);
+            return launch2<128, true, false, 1>(q, grid, st);
+        }
+        if (q.N <= 64) return launch2<64, false, false, 1>(q, grid, st);
+        if (q.N <= 128) return q.out_split ? launch2<128, false, true, 1>(q, grid, st) : launch2<128, false, false, 1>(q, grid, st);
+        if (q.out_split) return plan.epi == 4 ? launch2<256, false, true, 4>(q, grid, st) : launch2<256, false, true, 1>(q, grid, st);
+        return plan.epi == 4 ? launch2<256, false, false, 4>(q, grid, st) : launch2<256, false, false, 1>(q, grid, st);
     }
-    if (p.N <= 64) return launch2<64, false, false, 1>(q, grid, st);
-    if (p.N <= 128) return p.out_split ? launch2<128, false, true, 1>(q, grid, st) : launch2<128, false, false, 1>(q, grid, st);
-    if (p.out_split) return epi == 4 ? launch2<256, false, true, 4>(q, grid, st) : launch2<256, false, true, 1>(q, grid, st);
-    return epi == 4 ? launch2<256, false, false, 4>(q, grid, st) : launch2<256, false, false, 1>(q, grid, st);
-}
-
-// The whole-chunk instance (sep_pipe2_chunk_kernel): two fp32 outputs, more than 64 columns in one of them (the 256-column tile), stride 1,
-// 8 x 32 tiles.  A rule of the layer's shape alone.
-bool sep_pipe2_chunk_covers(const SepParams& p) {
-    if (p.stride != 1 || p.gen_a || p.rg_stride || p.H % 8 != 0 || p.W % 32 != 0 || p.Cin % 32 != 0 || p.Cin < 32 || p.Cin > 4064) return false;
-    return p.N2 > 0 && p.N <= 128 && p.N2 <= 128 && (p.N > 64 || p.N2 > 64) && !p.out_split && !p.res && !p.scale2;
-}
-
-int sep_pipe2_chunk_launch(const SepParams& p, int B, hipStream_t st) {
-    SepParams q = p;
-    const int tiles_w = p.W / 32;
-    const long wgs1 = (long)tiles_w * (p.H / 8) * B;
-    int tpw = 1;   // as sep_pipe2_launch
-    for (int t = 8; t >= 2; t >>= 1)
-        if (tiles_w % t == 0 && wgs1 / t >= 1024) { tpw = t; break; }
-    if (g_knobs.sep_tpw > 0 && tiles_w % g_knobs.sep_tpw == 0) tpw = g_knobs.sep_tpw;
-    q.tpw = tpw;
-    q.stamps = nullptr;
-    q.ablate = 0;
-    const dim3 grid(tiles_w / tpw, p.H / 8, B);
-    q.xcd = g_knobs.sep_xcd && ((long)grid.x * grid.y * grid.z) % 8 == 0;
-    if (g_knobs.epi_width == 4) hipLaunchKernelGGL((sep_pipe2_chunk_kernel<4>), grid, dim3(512), 0, st, q);
+    if (plan.epi == 4) hipLaunchKernelGGL((sep_pipe2_chunk_kernel<4>), grid, dim3(512), 0, st, q);
     else hipLaunchKernelGGL((sep_pipe2_chunk_kernel<1>), grid, dim3(512), 0, st, q);
     return emd::check_launch("sep_pipe2_chunk_kernel");
 }
-
-}  // namespace emd

@@ -7,10 +7,13 @@
  * here (tests/test_abi.py checks both directions).
  *
  * Nothing in the library reads the environment.  The kernel-selection knobs are fields of one struct (csrc/emd_common.hpp, emd::Knobs),
- * set by name through emd_debug_knob; defaults = the measured-best path:
+ * set by name through emd_debug_knob; defaults = the measured-best path (the sep_* knobs, epi_width and nt_mask bit 1 are read by
+ * csrc/sep_entry.hip, which routes the fused separable conv; emd_debug_sep_plan below shows what they choose):
  *   sep_pipe (1)        1: the LDS-DMA pipelined fused separable conv (csrc/sep_pipe.hip) where it covers the shape, 0: csrc/sep_fused.hip
  *   sep_pipe2_chunk (-1) two fp32 outputs on the 256-column tile (more than 64 channels in one of them; H % 8 == 0, W % 32 == 0): 1 = the whole-chunk
  *                       instance of csrc/sep_pipe2.hip, 0 = csrc/sep_pipe.hip's lockstep kernel (same bits), -1 = the rule (the faster one)
+ *   sep_pipe2 (0)       csrc/sep_pipe2.hip's run-time parity instances: 0 never, 1 two outputs of more than 64 columns, 2 wherever it has an instance
+ *   sep_gen_pipe (0)    generated-input fused separable conv: 1 = csrc/sep_pipe.hip's 4-wave instance, 0 = csrc/sep_fused.hip (same bits)
  *   sep_mode (-1)       sep_pipe schedule of the one-output instances: -1 = rule, 0 / 1 = the patch requested two / one steps ahead
  *   sep_nw (0)          sep_pipe waves per workgroup: 0 = rule (4 wherever there is an instance), 8 (8 x 32 pixel tiles, one workgroup per CU)
  *                       or 4 (8 x 16 tiles, two per CU: up to 128 output columns, 64 | 64 for two outputs)
@@ -60,6 +63,14 @@ int emd_debug_reduce_final_cl(int nslab);
 /* Host only, no state: 1 where emd_sep3x3_dual_f32 has the whole-chunk instance of csrc/sep_pipe2.hip for the layer's shape (what the knob
  * sep_pipe2_chunk switches; the rule has no batch argument), else 0. */
 int emd_debug_sep_pipe2_chunk_covers(int H, int W, int Cin, int Cout, int Cout2);
+/* Host only, reads the knobs, touches no device: the plan csrc/sep_entry.hip makes for a fused separable conv of this shape and form --
+ * which kernel, on which tiles, with which grid (tests/test_sep_plan.py pins it).  flags: bit 0 REFLECT border, 1 residual, 2 second
+ * affine, 3 split32 output, 4 generated input, 5 the same from the image (gen9), 6 generated residual, 7 folded final conv; Cout2 > 0: two
+ * outputs.  Returns the route, 0 where no kernel takes the shape (out is then left alone): 1 sep_fused, 2 sep_fused with resident
+ * weights, 3 its 256-column form, 4 its two-output form, 5 sep_gen9, 6 sep_pipe, 7 sep_pipe2, 8 sep_pipe2's whole-chunk instance.
+ * out = {route, waves per workgroup, tiles per workgroup, grid.x, grid.y, grid.z, sep_pipe schedule, epilogue width (0: sep_fused has
+ * one form), xcd, nt}. */
+int emd_debug_sep_plan(int B, int H, int W, int Cin, int Cout, int Cout2, int stride, int precision, unsigned flags, int out[10]);
 /* Force the pipeline variant of emd_conv1x1_split32_f32 (csrc/gemm_split.hip); -1 restores the dispatch rule. */
 void emd_debug_split_variant(int v);
 /* Device buffer that the split32 GEMM writes s_memtime phase stamps into (NULL = off). */
