@@ -3,9 +3,6 @@
 // table in the reference's variable-creation order (TF names under "GAN/Gen" and "GAN/Gen/reg"), both batch norms of every separable conv
 // folded into one affine (float64), weight packing, and the launch sequence of the library's own entry points -- the kernel choices of
 // emdenoise.gan.GeneratorEngine in its split-bf16 mode, single stream: bit-identical to it (tests/test_graph_exec_gpu.py).
-#include <cstdlib>
-#include <cstring>
-
 #include "graph_common.hpp"
 
 namespace emd {
@@ -25,18 +22,6 @@ struct GDecl {
     bool reflect = true;
 };
 
-// tf.variable_scope name uniquifier with a scope stack (emdenoise.gan._Scope)
-struct GScope {
-    std::vector<std::string> stack{"GAN/Gen"};
-    std::map<std::string, int> counts;
-    std::string unique(const std::string& base) {
-        std::string parent = stack[0];
-        for (size_t i = 1; i < stack.size(); ++i) parent += "/" + stack[i];
-        const int k = counts[parent + "|" + base]++;
-        return k == 0 ? parent + "/" + base : parent + "/" + base + "_" + std::to_string(k);
-    }
-};
-
 struct GTable {
     std::vector<GDecl> L;
     std::string conv_scope, in_shift, in_scale;
@@ -44,13 +29,13 @@ struct GTable {
 
 // the generator's parameterised layers in creation order (:341-372; mirror of emdenoise.gan.declare_layers)
 GTable declare_g() {
-    GScope sc;
+    Scope sc("GAN/Gen");
     GTable T;
     auto sep = [&](const std::string& key, int cin, int cout, int k = 3, int stride = 1, bool reflect = true) {
         GDecl d;
         d.key = key; d.cin = cin; d.cout = cout; d.k = k; d.stride = stride; d.reflect = reflect;
-        d.scope = sc.unique("SeparableConv2d");
-        d.outer_bn = sc.unique("BatchNorm");
+        d.scope = sc("SeparableConv2d");
+        d.outer_bn = sc("BatchNorm");
         T.L.push_back(d);
     };
     auto middle = [&](const std::string& prefix, int f) {
@@ -70,9 +55,9 @@ GTable declare_g() {
     sep("up", GF2, GF3, 3, 1, false);
     sep("last_sep", GF3, GF3);
     sc.stack.pop_back();
-    T.conv_scope = sc.unique("Conv");
-    T.in_shift = sc.unique("Variable");
-    T.in_scale = sc.unique("Variable");
+    T.conv_scope = sc("Conv");
+    T.in_shift = sc("Variable");
+    T.in_scale = sc("Variable");
     return T;
 }
 
@@ -83,33 +68,28 @@ struct GParams {
     float *w49 = nullptr, *a = nullptr;                          // enc0: 7x7 taps; pointwise weights x folded scale
 };
 
-}  // namespace
-
-struct GGraph {
+struct GGraph : Graph {
     std::map<std::string, GParams> P;
     float *unit4 = nullptr, *zero4 = nullptr, *w_last = nullptr;
     float b_last = 0.f;
+    bool side_ok(int S) const override { return S >= 32; }
+    const char* side_error() const override { return "emd_graph_run: graph G takes square crops with side a multiple of 16, >= 32"; }
+    int forward(Arena* ar, hipStream_t st, bool dry, bool two_streams, const float* in, float* out, int B, int S) override;
 };
 
-GGraph* g_create(const WeightMap& w, std::vector<void*>& allocs, std::string* err) {
-    GGraph* g = new GGraph();
+}  // namespace
+
+std::unique_ptr<Graph> g_create(const WeightMap& w, std::vector<void*>& allocs, CreateError* err) {
+    std::unique_ptr<GGraph> g(new GGraph());
     const GTable T = declare_g();
     bool ok = true;
     for (const GDecl& d : T.L) {
         GParams p;
         p.d = d;
         const float *dw, *pw;
-        ok = fetch(w, d.scope + "/depthwise_weights", (long)d.k * d.k * d.cin, &dw, err) && fetch(w, d.scope + "/pointwise_weights", (long)d.cin * d.cout, &pw, err);
-        if (!ok) break;
-        std::vector<double> s(d.cout, 1.0), t(d.cout, 0.0);
-        for (const std::string& scope : {d.scope + "/BatchNorm", d.outer_bn}) {
-            std::vector<double> gs, hs;
-            if (!(ok = bn_affine(w, scope, d.cout, BN_EPS_GEN, &gs, &hs, err))) break;
-            for (int c = 0; c < d.cout; ++c) {
-                s[c] *= gs[c];
-                t[c] = t[c] * gs[c] + hs[c];
-            }
-        }
+        std::vector<double> s, t;
+        ok = fetch(w, d.scope + "/depthwise_weights", (long)d.k * d.k * d.cin, &dw, err) && fetch(w, d.scope + "/pointwise_weights", (long)d.cin * d.cout, &pw, err) &&
+             fold_affine(w, nullptr, {d.scope + "/BatchNorm", d.outer_bn}, d.cout, BN_EPS_GEN, &s, &t, err);
         if (!ok) break;
         if (d.cin == 1) {
             std::vector<double> a(d.cout);
@@ -125,16 +105,14 @@ GGraph* g_create(const WeightMap& w, std::vector<void*>& allocs, std::string* er
             ok = p.dw && p.scale && p.shift && pack(allocs, pw, 1, d.cin, d.cout, 0, &p.pw);
         }
         if (!ok) break;
-        g->P[d.key] = p;
+        g->P.emplace(d.key, p);
     }
     if (ok) {
         const float *wl, *bl, *sh, *sc;
         ok = fetch(w, T.conv_scope + "/weights", 9L * GF3, &wl, err) && fetch(w, T.conv_scope + "/biases", 1, &bl, err) &&
              fetch(w, T.in_shift, 1, &sh, err) && fetch(w, T.in_scale, 1, &sc, err);
-        if (ok && (sh[0] != 0.f || sc[0] != 1.f)) {
-            *err = "emd_graph_create: the instance norm's shift / scale variables are frozen at 0 / 1 in the reference (gan-infilling-100.py:144-145)";
-            ok = false;
-        }
+        if (ok && (sh[0] != 0.f || sc[0] != 1.f))
+            ok = err->set(EMD_E_INVALID, "emd_graph_create: the instance norm's shift / scale variables are frozen at 0 / 1 in the reference (gan-infilling-100.py:144-145)");
         if (ok) {
             const float u4[4] = {1.f, 0.f, 0.f, 0.f}, z4[4] = {0.f, 0.f, 0.f, 0.f};
             g->w_last = upload(allocs, wl, 9 * (size_t)GF3);   // [3][3][Cin][1] == [9][Cin]
@@ -144,49 +122,22 @@ GGraph* g_create(const WeightMap& w, std::vector<void*>& allocs, std::string* er
             ok = g->w_last && g->unit4 && g->zero4;
         }
     }
-    if (!ok) {
-        if (err->empty()) *err = "emd_graph_create: device allocation or upload failed";
-        delete g;
-        return nullptr;
-    }
+    if (!ok) return nullptr;
     return g;
 }
 
-void g_destroy(GGraph* g) { delete g; }
-
 namespace {
 
-struct GRun {
+struct GRun : RunBase {
     GGraph* g;
-    Arena* ar;
-    hipStream_t st;
-    bool dry;
     int B;
-    int rc = EMD_OK;
 
-    void* raw(size_t bytes) {
-        void* p = ar->alloc(bytes);
-        if (!p && rc == EMD_OK) rc = emd::fail(EMD_E_INVALID, "emd_graph_run: workspace too small");
-        return p;
-    }
-    T4 E(int H, int W, int C) {
-        T4 t;
-        t.B = B; t.H = H; t.W = W; t.C = C; t.ld = C;
-        t.buf = static_cast<float*>(raw((size_t)B * H * W * C * 4));
-        return t;
-    }
-    void drop(T4& t) {
-        ar->release(t.buf);
-        t.buf = nullptr;
-    }
-    void call(int code) {
-        if (code != EMD_OK && rc == EMD_OK) rc = code;
-    }
-    bool live() const { return !dry && rc == EMD_OK; }
+    T4 E(int H, int W, int C) { return RunBase::E(B, H, W, C); }
+    const GParams& param(const std::string& key) { return RunBase::param(g->P, key); }
 
     // strided_conv_block / deconv_block (gan-infilling-100.py:205-243): the route choices of GeneratorEngine._sep
     T4 sep(const std::string& key, const T4& x, const T4* res) {
-        const GParams& p = g->P[key];
+        const GParams& p = param(key);
         const GDecl& d = p.d;
         const int Ho = (x.H - 1) / d.stride + 1, Wo = (x.W - 1) / d.stride + 1;
         const long M = (long)B * Ho * Wo;
@@ -229,30 +180,30 @@ struct GRun {
             call(emd_conv1x1_f32(tmp.ptr(), tmp.ld, p.pw.hi, p.pw.lo, p.scale, p.shift, nullptr, nullptr, rp, rl, out.ptr(), out.ld, B, Ho, Wo, d.cin, d.cout,
                                  1, EMD_ACT_LEAKY, EMD_PREC_BF16X3, st));
         }
-        drop(tmp);
+        release(tmp);
         return out;
     }
     T4 middle(const std::string& prefix, T4& x) {   // consumes x
         T4 t0 = sep(prefix + "_0", x, nullptr);
         T4 t1 = sep(prefix + "_1", t0, nullptr);
-        drop(t0);
+        release(t0);
         T4 y = sep(prefix + "_2", t1, &x);
-        drop(t1);
-        drop(x);
+        release(t1);
+        release(x);
         return y;
     }
     T4 up(const std::string& key, T4& x, int size, const T4* res) {   // consumes x
         T4 u = E(size, size, x.C);
         if (live()) call(emd_resize_bilinear_f32(x.ptr(), x.ld, u.ptr(), u.ld, B, x.H, x.W, size, size, x.C, st));
-        drop(x);
+        release(x);
         T4 y = sep(key, u, res);
-        drop(u);
+        release(u);
         return y;
     }
 
     void forward(const float* in, float* out, int S) {
-        const GParams& p0 = g->P["enc0"];
-        const GParams& p1 = g->P["enc1"];
+        const GParams& p0 = param("enc0");
+        const GParams& p1 = param("enc1");
         const int So = (S - 1) / p1.d.stride + 1;
         T4 enc;
         if (p1.d.reflect && p1.d.stride == 2 && !emd_conv1x1_split32_supported((long)B * So * So, p1.d.cin, p1.d.cout)) {
@@ -265,28 +216,28 @@ struct GRun {
                 call(emd_conv1x1_f32(dd.ptr(), dd.ld, p1.pw.hi, p1.pw.lo, p1.scale, p1.shift, nullptr, nullptr, nullptr, 0, enc.ptr(), enc.ld, B, So, So,
                                      p1.d.cin, p1.d.cout, 1, EMD_ACT_LEAKY, EMD_PREC_BF16X3, st));
             }
-            drop(d4);
-            drop(dd);
+            release(d4);
+            release(dd);
         } else {
             T4 e0 = E(S, S, GF0);
             if (live()) call(emd_cin1_k7_reflect_f32(in, p0.w49, p0.a, p0.shift, e0.ptr(), e0.ld, B, S, S, GF0, 1, st));
             enc = sep("enc1", e0, nullptr);
-            drop(e0);
+            release(e0);
         }
         T4 n0 = sep("nin_down0", enc, nullptr);
         T4 n1 = sep("nin_down1", n0, nullptr);
-        drop(n0);
+        release(n0);
         T4 n = sep("nin_down2", n1, nullptr);
-        drop(n1);
+        release(n1);
         for (int i = 0; i < N_GLOBAL; ++i) n = middle("nin_mid" + std::to_string(i), n);
         n = up("nin_up0", n, S / 8, nullptr);
         n = up("nin_up1", n, S / 4, nullptr);
         T4 e = up("nin_up2", n, S / 2, &enc);                  // enc += network_in_network(enc)  (:355)
-        drop(enc);
+        release(enc);
         for (int i = 0; i < N_LOCAL; ++i) e = middle("local" + std::to_string(i), e);
         e = up("up", e, S, nullptr);
         T4 last = sep("last_sep", e, nullptr);
-        drop(e);
+        release(e);
         // tf.pad(REFLECT, 1) + 3x3 VALID conv to one channel + bias (:362-369), instance norm + tanh (:140-148, :372)
         const long npix = (long)S * S;
         float* rawimg = static_cast<float*>(raw((size_t)B * npix * 4));
@@ -299,15 +250,15 @@ struct GRun {
             call(emd_bn_stats_images_f32(rawimg, 1, B, npix, 1, mean, var, ws, st));
             call(emd_instnorm_tanh_f32(rawimg, mean, var, out, B, npix, IN_EPS, st));
         }
-        drop(last);
+        release(last);
         ar->release(rawimg); ar->release(mean); ar->release(var); ar->release(ws);
     }
 };
 
 }  // namespace
 
-int g_forward(GGraph* g, Arena* ar, hipStream_t st, bool dry, const float* in, float* out, int B, int S) {
-    GRun r{g, ar, st, dry, B};
+int GGraph::forward(Arena* ar, hipStream_t st, bool dry, bool, const float* in, float* out, int B, int S) {
+    GRun r{{ar, st, dry}, this, B};
     r.forward(in, out, S);
     return r.rc;
 }

@@ -5,9 +5,6 @@
 // the same kernel choices as emdenoise.xception.XceptionEngine in its split-bf16 mode, single stream: bit-identical to it
 // (tests/test_graph_exec_gpu.py).  Batch statistics (the separable convs' norms, :302-323) are taken over the batch handed to
 // emd_graph_run, as the reference takes them per tower.
-#include <cstdlib>
-#include <cstring>
-
 #include "graph_common.hpp"
 
 namespace emd {
@@ -28,18 +25,9 @@ struct XDecl {
     std::string scope, bn;   // conv / separable / transposed conv scope; the moving-statistics norm that follows (conv, deconv, bn)
 };
 
-// tf.variable_scope default-name uniquifier inside scope 'pellet' (modified_Xception.py:794)
-struct XScope {
-    std::map<std::string, int> n;
-    std::string operator()(const std::string& base) {
-        const int k = n[base]++;
-        return k == 0 ? "pellet/" + base : "pellet/" + base + "_" + std::to_string(k);
-    }
-};
-
 // layers of architecture() in graph-construction order (mirror of emdenoise.xception.declare_layers)
 std::vector<XDecl> declare_x() {
-    XScope sc;
+    Scope sc("pellet");   // modified_Xception.py:794
     std::vector<XDecl> L;
     auto conv = [&](int cin, int cout, int k = 1, int stride = 1, int rate = 1, const char* name = nullptr, bool bn = true) {
         XDecl d{XCONV, cin, cout, k, stride, rate};
@@ -105,14 +93,17 @@ struct XParams {
     float pre_bias = 0.f, scale_f = 1.f, shift_f = 0.f;
 };
 
-}  // namespace
-
-struct XGraph {
-    std::vector<XParams> P;
+struct XGraph : Graph {
+    std::vector<XParams> layers;   // in table order: the launch sequence takes them by position (XRun::next)
+    bool side_ok(int S) const override { return S % 64 == 0; }
+    const char* side_error() const override { return "emd_graph_run: graph X takes square crops with side a multiple of 64"; }
+    int forward(Arena* ar, hipStream_t st, bool dry, bool two_streams, const float* in, float* out, int B, int S) override;
 };
 
-XGraph* x_create(const WeightMap& w, std::vector<void*>& allocs, std::string* err) {
-    XGraph* x = new XGraph();
+}  // namespace
+
+std::unique_ptr<Graph> x_create(const WeightMap& w, std::vector<void*>& allocs, CreateError* err) {
+    std::unique_ptr<XGraph> x(new XGraph());
     bool ok = true;
     for (const XDecl& d : declare_x()) {
         XParams p;
@@ -150,22 +141,13 @@ XGraph* x_create(const WeightMap& w, std::vector<void*>& allocs, std::string* er
             }
         } else if (d.kind == XDECONV) {
             const float *wt, *bias;
-            std::vector<double> g, h;
+            std::vector<double> s, t;   // s = 1 * g, t = bias * g + h
             ok = fetch(w, d.scope + "/kernel", 9L * d.cout * d.cin, &wt, err) && fetch(w, d.scope + "/bias", d.cout, &bias, err) &&
-                 bn_affine(w, d.bn, d.cout, BN_EPS_X, &g, &h, err);
+                 fold_affine(w, bias, {d.bn}, d.cout, BN_EPS_X, &s, &t, err);
             if (!ok) break;
-            for (int ph = 0; ph < 4 && ok; ++ph) {   // [3][3][Cout][Cin] -> per output phase [taps][Cout][Cin]
-                int ky[4], kx[4];
-                const int nt = emd_deconv_phase_taps(ph, ky, kx);
-                std::vector<float> sub((size_t)nt * d.cout * d.cin);
-                for (int t = 0; t < nt; ++t)
-                    memcpy(sub.data() + (size_t)t * d.cout * d.cin, wt + (size_t)(ky[t] * 3 + kx[t]) * d.cout * d.cin, sizeof(float) * d.cout * d.cin);
-                ok = pack(allocs, sub.data(), nt, d.cin, d.cout, 1, &p.phase[ph]);
-            }
-            std::vector<double> sh(d.cout);
-            for (int c = 0; c < d.cout; ++c) sh[c] = (double)bias[c] * g[c] + h[c];
-            p.scale = upload_f(allocs, g);
-            p.shift = upload_f(allocs, sh);
+            ok = pack_deconv_phases(allocs, wt, d.cin, d.cout, p.phase);
+            p.scale = upload_f(allocs, s);
+            p.shift = upload_f(allocs, t);
             ok = ok && p.scale && p.shift;
         } else if (d.kind == XSEP) {
             const float *dw, *pw, *beta;
@@ -186,21 +168,12 @@ XGraph* x_create(const WeightMap& w, std::vector<void*>& allocs, std::string* er
             p.shift = upload_f(allocs, h);
             ok = p.scale && p.shift;
         }
-        if (!ok) {
-            if (err->empty()) *err = "emd_graph_create: device allocation or upload failed";
-            break;
-        }
-        x->P.push_back(p);
+        if (!ok) break;
+        x->layers.push_back(p);
     }
-    if (!ok) {
-        if (err->empty()) *err = "emd_graph_create: device allocation or upload failed";
-        delete x;
-        return nullptr;
-    }
+    if (!ok) return nullptr;
     return x;
 }
-
-void x_destroy(XGraph* x) { delete x; }
 
 namespace {
 
@@ -214,27 +187,13 @@ struct XT {
     float *pre_s = nullptr, *pre_t = nullptr;
 };
 
-struct XRun {
+struct XRun : RunBase {
     XGraph* g;
-    Arena* ar;
-    hipStream_t st;
-    bool dry;
     int B;
-    int rc = EMD_OK;
     size_t pos = 0;
 
-    void* raw(size_t bytes) {
-        void* p = ar->alloc(bytes);
-        if (!p && rc == EMD_OK) rc = emd::fail(EMD_E_INVALID, "emd_graph_run: workspace too small");
-        return p;
-    }
     float* vec(int n) { return static_cast<float*>(raw((size_t)n * 4)); }
-    T4 E(int H, int W, int C) {
-        T4 t;
-        t.B = B; t.H = H; t.W = W; t.C = C; t.ld = C;
-        t.buf = static_cast<float*>(raw((size_t)B * H * W * C * 4));
-        return t;
-    }
+    T4 E(int H, int W, int C) { return RunBase::E(B, H, W, C); }
     XT F(int H, int W, int C) {
         XT x;
         x.t = E(H, W, C);
@@ -254,11 +213,13 @@ struct XRun {
         ar->release(x.pre_t);
         x.sp = nullptr; x.t.buf = nullptr; x.pre_s = x.pre_t = nullptr;
     }
-    void call(int code) {
-        if (code != EMD_OK && rc == EMD_OK) rc = code;
+    // the next layer of the table; past its end: reported (once), an empty record, so a dry pass still ends
+    const XParams& next() {
+        static const XParams none{};
+        if (pos < g->layers.size()) return g->layers[pos++];
+        if (rc == EMD_OK) rc = emd::fail(EMD_E_INVALID, "emd_graph_run: graph X: no layer past the end of the table");
+        return none;
     }
-    bool live() const { return !dry && rc == EMD_OK; }
-    const XParams& next() { return g->P[pos++]; }
 
     // this conv / deconv layer runs on the LDS-DMA split32 kernels (xception.split_ok)
     static bool split_ok(const XDecl& d, long npix_in) {
@@ -267,17 +228,12 @@ struct XRun {
         const int bn = d.cout <= 64 ? 64 : 128;
         return d.cout >= 32 && d.cin >= 32 && ((m + 255) / 256) * ((d.cout + bn - 1) / bn) >= 192;
     }
-    bool next_takes_split(long npix_out) const { return pos < g->P.size() && split_ok(g->P[pos].d, npix_out); }
+    bool next_takes_split(long npix_out) const { return pos < g->layers.size() && split_ok(g->layers[pos].d, npix_out); }
 
     // a as a split32 tensor (converted when it is fp32); *tmp receives a buffer to release afterwards
     const void* as_split(const XT& a, int* ld, void** tmp) {
-        *tmp = nullptr;
-        if (a.split) { *ld = a.ld; return a.sp; }
-        *ld = emd_split32_ld(a.t.C);
-        const long npix = (long)B * a.t.H * a.t.W;
-        *tmp = raw((size_t)npix * *ld * 4);
-        if (live()) call(emd_to_split32_f32(a.t.ptr(), a.t.ld, *tmp, *ld, npix, a.t.C, st));
-        return *tmp;
+        *ld = a.ld;
+        return as_split32(*this, &a.t, a.split ? a.sp : nullptr, (long)B * a.t.H * a.t.W, a.t.C, ld, tmp);
     }
 
     // tf.layers.conv2d (+ bias) -> batch_then_activ: one launch (xception.conv_bn_relu)
@@ -343,15 +299,14 @@ struct XRun {
         const XDecl& d = p.d;
         const int H = a.t.H, W = a.t.W;
         const long npix = (long)B * H * W;
-        const uint16_t* hi[4] = {p.phase[0].hi, p.phase[1].hi, p.phase[2].hi, p.phase[3].hi};
-        const uint16_t* lo[4] = {p.phase[0].lo, p.phase[1].lo, p.phase[2].lo, p.phase[3].lo};
+        const PhasePtrs w(p.phase);
         if (split_ok(d, npix)) {
             XT r = next_takes_split(4 * npix) ? SP(2 * H, 2 * W, d.cout) : F(2 * H, 2 * W, d.cout);
             int ldx;
             void* tmp;
             const void* xs = as_split(a, &ldx, &tmp);
             if (live())
-                call(emd_deconv3x3s2_fused_split32_f32(xs, ldx, hi, lo, p.scale, p.shift, r.split ? r.sp : static_cast<void*>(r.t.ptr()),
+                call(emd_deconv3x3s2_fused_split32_f32(xs, ldx, w.hi, w.lo, p.scale, p.shift, r.split ? r.sp : static_cast<void*>(r.t.ptr()),
                                                        r.split ? r.ld : r.t.ld, B, H, W, d.cin, d.cout, EMD_ACT_RELU, r.split ? 1 : 0, st));
             ar->release(tmp);
             return r;
@@ -359,7 +314,7 @@ struct XRun {
         XT r = F(2 * H, 2 * W, d.cout);
         if (a.split && rc == EMD_OK) rc = emd::fail(EMD_E_UNSUPPORTED, "emd_graph_run: graph X: a split32 tensor reached an fp32 transposed conv");
         if (live())
-            call(emd_deconv3x3s2_f32(a.t.ptr(), a.t.ld, hi, lo, p.scale, p.shift, r.t.ptr(), r.t.ld, B, H, W, d.cin, d.cout, EMD_ACT_RELU, EMD_PREC_BF16X3, st));
+            call(emd_deconv3x3s2_f32(a.t.ptr(), a.t.ld, w.hi, w.lo, p.scale, p.shift, r.t.ptr(), r.t.ld, B, H, W, d.cin, d.cout, EMD_ACT_RELU, EMD_PREC_BF16X3, st));
         return r;
     }
 
@@ -500,14 +455,14 @@ struct XRun {
         if (live())
             call(emd_conv3x3_cout1_f32(d.t.ptr(), d.t.ld, p.wfin, p.scale_f, p.shift_f, out, B, d.t.H, d.t.W, p.d.cin, 2, p.pre_bias, 1, st));
         drop(d);
-        if (pos != g->P.size() && rc == EMD_OK) rc = emd::fail(EMD_E_INVALID, "emd_graph_run: graph X: layer table and launch sequence disagree");
+        if (pos != g->layers.size() && rc == EMD_OK) rc = emd::fail(EMD_E_INVALID, "emd_graph_run: graph X: layer table and launch sequence disagree");
     }
 };
 
 }  // namespace
 
-int x_forward(XGraph* x, Arena* ar, hipStream_t st, bool dry, const float* in, float* out, int B, int S) {
-    XRun r{x, ar, st, dry, B};
+int XGraph::forward(Arena* ar, hipStream_t st, bool dry, bool, const float* in, float* out, int B, int S) {
+    XRun r{{ar, st, dry}, this, B};
     r.forward(in, out, S);
     return r.rc;
 }

@@ -941,7 +941,7 @@ int emd_gen_lq_f32(const float* img, const float* scale, float* lq, float* truth
                    unsigned long long seed, unsigned long long first_image, void* workspace, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Graph D as a native executor (csrc/graph_exec.hip): architecture() of machine_learning/denoiser.py:58-398 for
+ * Graph D as a native executor (csrc/graph_exec.hip, graph_exec_d.hip): architecture() of machine_learning/denoiser.py:58-398 for
  * a host that is not Python.  emd_graph_create takes the weights as HOST float32 arrays keyed by TensorFlow variable name
  * (the names tf.train.Saver stores under scope 'nn', :514: nn/SeparableConv2d[_k]/{depthwise_weights,pointwise_weights},
  * nn/SeparableConv2d[_k]/BatchNorm/{beta,gamma,moving_mean,moving_variance}, nn/BatchNorm[_k]/..., nn/Conv[_k]/{weights,biases},
@@ -962,7 +962,7 @@ int emd_gen_lq_f32(const float* img, const float* scale, float* lq, float* truth
  * A handle is NOT re-entrant: emd_graph_run calls on one handle must be serialised by the caller (one stream, one thread at a
  * time) -- the fork / join events and the side streams of the two-streams form belong to the handle; use one handle per
  * concurrent stream (the weights are ~100 MB).  emd_graph_workspace_bytes returns the larger of the two launch forms' needs, so a
- * size asked for before emd_graph_set_two_streams stays valid after it.  emd_graph_create returns EMD_E_ALLOC when a device
+ * size asked for before emd_graph_set_two_streams stays valid after it; the query writes nothing to the handle.  emd_graph_create returns EMD_E_ALLOC when a device
  * allocation or upload fails (EMD_E_INVALID: a missing / mis-sized variable). */
 typedef struct emd_graph emd_graph_t;
 int emd_graph_create(emd_graph_t** graph, int variant, int n_vars, const char* const* names, const float* const* host_data,

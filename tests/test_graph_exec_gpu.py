@@ -26,6 +26,140 @@ def test_create_reports_a_missing_or_misshapen_variable():
     assert lib.emd_graph_workspace_bytes(None, 1, 64) == 0
 
 
+_CREATE_CASES = [(v, k) for v in ("D", "Dprime", "X", "G") for k in ("dw", "bias", "deconv", "bn") if (v, k) != ("G", "deconv")]   # G: no transposed conv
+_weights_cache = {}
+
+
+def _weights(variant):
+    """synthetic_weights of a variant, made once and never modified (the tests copy the dict)."""
+    if variant not in _weights_cache:
+        import emdenoise
+        from emdenoise import gan, xception
+
+        _weights_cache[variant] = (xception.synthetic_weights() if variant == "X" else gan.synthetic_weights() if variant == "G"
+                                   else emdenoise.synthetic_weights(variant=variant))
+    return _weights_cache[variant]
+
+
+def _variables_by_layer_kind(variant):
+    """One variable per layer kind of the variant's table (named through the Python twin of the table): separable depthwise weights,
+    a conv bias, a transposed-conv kernel, a lone batch norm's moving_variance.  Graph G has no transposed conv and no lone norm: the
+    norm that follows a separable conv (batch_then_activ) stands in; its one conv's bias is a single element."""
+    from emdenoise import denoiser, gan, xception
+
+    if variant in ("D", "Dprime"):
+        L = denoiser.declare_layers(variant)
+        return {"dw": L["cnn1"].scope + "/depthwise_weights", "bias": L["residual1"].scope + "/" + L["residual1"].bname,
+                "deconv": L["deconv2to1"].scope + "/" + L["deconv2to1"].wname, "bn": L["aspp_pooling_bn"].bn[0] + "/moving_variance"}
+    if variant == "X":
+        L = xception.declare_layers()
+        first = lambda kind: next(l for l in L if l.kind == kind)
+        return {"dw": first("sep").scope + "/depthwise_weights", "bias": L[1].scope + "/bias", "deconv": first("deconv").scope + "/kernel",
+                "bn": first("bn").bn + "/moving_variance"}
+    L, conv_scope, _ = gan.declare_layers()
+    return {"dw": L["nin_down0"].scope + "/depthwise_weights", "bias": conv_scope + "/biases", "bn": L["enc1"].outer_bn + "/moving_variance"}
+
+
+def _create_fails(weights, variant, text):
+    from emdenoise import _lib
+    from emdenoise.graph_exec import NativeGraph
+
+    with pytest.raises(_lib.EmdError) as e:
+        NativeGraph(weights, torch.device("cuda", 0), variant=variant)
+    msg = str(e.value)
+    assert "(code -1)" in msg, msg                                   # EMD_E_INVALID
+    assert text in msg, msg
+
+
+def _create_succeeds(variant):
+    """A correct create after a failed one: the failure freed what it had allocated and left nothing half-built."""
+    from emdenoise.graph_exec import NativeGraph
+
+    nat = NativeGraph(_weights(variant), torch.device("cuda", 0), variant=variant)
+    assert nat.workspace_bytes(1, 64) > 0
+    nat.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,kind", _CREATE_CASES)
+def test_create_names_a_removed_variable(variant, kind):
+    names = _variables_by_layer_kind(variant)
+    bad = dict(_weights(variant))
+    del bad[names[kind]]
+    _create_fails(bad, variant, "emd_graph_create: missing variable " + names[kind])
+    _create_succeeds(variant)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,kind", _CREATE_CASES)
+def test_create_names_a_truncated_variable(variant, kind):
+    name = _variables_by_layer_kind(variant)[kind]
+    if variant == "G" and kind == "bias":
+        name = name.replace("/biases", "/weights")                   # the bias has one element; an empty variable is another error
+    bad = dict(_weights(variant))
+    m = bad[name].size
+    bad[name] = np.ascontiguousarray(bad[name].ravel()[:-1])
+    _create_fails(bad, variant, f"emd_graph_create: {name}: {m - 1} elements, expected {m}")
+    _create_succeeds(variant)
+
+
+@pytest.mark.gpu
+def test_create_g_rejects_an_instance_norm_that_is_not_frozen():
+    from emdenoise import gan
+
+    shift = gan.declare_layers()[2][0]
+    bad = dict(_weights("G"))
+    bad[shift] = np.ones(1, np.float32)
+    _create_fails(bad, "G", "frozen")
+    _create_succeeds("G")
+
+
+@pytest.mark.gpu
+def test_workspace_query_leaves_the_handle_alone():
+    """emd_graph_workspace_bytes is a query: the same answer whatever emd_graph_set_two_streams says, and the runs around it are
+    untouched.  (B, S) = (2, 64); the smallest even B at which the two-streams form is taken at S = 64,
+    emd_conv1x1_split32_supported((B/2) * 16, 728, 728), is 2 as well (the predicate looks at the channel counts only)."""
+    from emdenoise import _lib
+    from emdenoise.graph_exec import NativeGraph
+
+    lib = _lib.load()
+    S = 64
+    B = next(b for b in range(2, 66, 2) if lib.emd_conv1x1_split32_supported(C.c_long(b // 2 * (S // 16) ** 2), 728, 728))
+    assert B == 2
+    dev = torch.device("cuda", 0)
+    nat = NativeGraph(_weights("D"), dev)
+    x = torch.from_numpy(synthetic_lq(B, S, S, seed=11)).to(dev)
+    need = nat.workspace_bytes(B, S)
+    first = nat.forward(x)
+    torch.cuda.synchronize()
+    for on in (True, False):
+        nat.set_two_streams(on)
+        assert nat.workspace_bytes(B, S) == need
+        y = nat.forward(x)
+        torch.cuda.synchronize()
+        assert torch.equal(y, first)
+    nat.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,S,text", [
+    ("D", 40, "emd_graph_run: square crops with side a multiple of 16, B >= 1"),
+    ("X", 48, "emd_graph_run: graph X takes square crops with side a multiple of 64"),
+    ("G", 16, "emd_graph_run: graph G takes square crops with side a multiple of 16, >= 32")])
+def test_invalid_side_is_reported(variant, S, text):
+    from emdenoise.graph_exec import NativeGraph
+
+    dev = torch.device("cuda", 0)
+    nat = NativeGraph(_weights(variant), dev, variant=variant)
+    assert nat.workspace_bytes(1, S) == 0
+    x = torch.zeros(1, S, S, 1, device=dev)
+    y = torch.empty_like(x)
+    ws = torch.empty(1 << 20, dtype=torch.uint8, device=dev)
+    rc = nat.lib.emd_graph_run(nat._h, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), 1, S, C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), None)
+    assert rc == -1 and nat.lib.emd_last_error().decode() == text
+    nat.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,S", [(2, 64), (1, 48), (4, 512), (16, 512)])   # 16 x 512^2: set_two_streams runs the 1/16-resolution flow as two halves
 def test_native_graph_equals_the_python_engine(B, S):
