@@ -569,6 +569,8 @@ DEV_SIGNATURES = {
     "emd_debug_sep_pipe2_chunk_covers": (C.c_int, [C.c_int] * 5),
     # B H W Cin Cout Cout2 stride precision flags out[10]
     "emd_debug_sep_plan": (C.c_int, [C.c_int] * 8 + [C.c_uint, C.POINTER(C.c_int)]),
+    # op B H W Cin Cout stride rate precision flags ldx ldy out[12]
+    "emd_debug_conv_plan": (C.c_int, [C.c_int] * 9 + [C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "emd_debug_split_variant": (None, [C.c_int]),
     "emd_debug_split_stamps": (None, [C.c_void_p]),
     "emd_debug_sep_stamps": (None, [C.c_void_p]),

@@ -1,4 +1,4 @@
-// Parameter block of the patch-resident dense 3x3 convolution (conv3_pipe.hip), shared with its dispatcher (conv_split.hip).
+// Parameter block of the patch-resident dense 3x3 convolution (conv3_pipe.hip), shared with conv_entry.hip, which fills it.
 #pragma once
 
 #include "mfma_common.hpp"
@@ -33,11 +33,5 @@ struct DeconvPipeParams {
     int tpw, n_ntiles;
     int ablate;               // dev (knob sep_ablate; results wrong on purpose): 2 no MFMAs, 4 no stores, 8 no patch DMA, 16 no weight DMA
 };
-
-bool deconv_pipe_covers(const DeconvPipeParams& p);
-int deconv_pipe_launch(const DeconvPipeParams& p, int B, int out_split, hipStream_t st);
-
-bool conv3_pipe_covers(const Conv3Params& p);
-int conv3_pipe_launch(const Conv3Params& p, int B, int out_split, hipStream_t st);
 
 }  // namespace emd

@@ -21,7 +21,7 @@
 // Epilogue from the accumulators (quad transpose, 16-byte non-temporal stores), fp32 or split32 output, two-stage affine.
 #include <type_traits>
 
-#include "conv3_params.hpp"
+#include "conv_plan.hpp"
 
 namespace {
 
@@ -348,34 +348,15 @@ __global__ __launch_bounds__(512, 1) void conv3_pipe_kernel(const Conv3Params p)
 
 }  // namespace
 
-namespace emd {
-
-bool conv3_pipe_covers(const Conv3Params& p) {
-    // (column tiles of 64: the packed weight planes are padded to a multiple of 128 rows, so a last partial tile stays inside them)
-    return g_knobs.conv3_pipe && p.H % 8 == 0 && p.W % 32 == 0 && p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 4064 && p.N % 4 == 0 &&
-           p.N <= (g_knobs.conv3_pipe >= 2 ? 1024 : 256);   // measured (tools/conv3_bench.py): faster up to 192 columns, 3-4 % at 256
-}
-
-int conv3_pipe_launch(const Conv3Params& p, int B, int out_split, hipStream_t st) {
-    Conv3Params q = p;
-    const int tiles_w = p.W / 32;
-    q.n_ntiles = (p.N + 63) / 64;
-    const long wgs1 = (long)tiles_w * (p.H / 8) * B * q.n_ntiles;
-    int tpw = 1;
-    for (int t : {8, 4, 2})
-        if (tiles_w % t == 0 && wgs1 / t >= 1024) { tpw = t; break; }
-    if (g_knobs.sep_tpw > 0 && tiles_w % g_knobs.sep_tpw == 0) tpw = g_knobs.sep_tpw;   // dev knob (shared with the separable kernels)
-    q.tpw = tpw;
-    const dim3 grid(tiles_w / tpw * q.n_ntiles, p.H / 8, B);
-    // epilogue: per-channel dword stores; four or more column tiles (>= 256 columns) do better with the transposed 16-byte form
-    if (g_knobs.epi_width ? g_knobs.epi_width == 4 : q.n_ntiles >= 4) {
-        if (out_split) hipLaunchKernelGGL((conv3_pipe_kernel<true, 4>), grid, dim3(512), 0, st, q);
-        else hipLaunchKernelGGL((conv3_pipe_kernel<false, 4>), grid, dim3(512), 0, st, q);
+// plan -> instance (conv_entry.hip made the plan and filled q.tpw / q.n_ntiles from it)
+int emd::conv3_pipe_launch(const ConvPlan& pl, const Conv3Params& q, hipStream_t st) {
+    const bool out_split = pl.form != 0;
+    if (pl.epi == 4) {
+        if (out_split) hipLaunchKernelGGL((conv3_pipe_kernel<true, 4>), pl.grid, dim3(512), 0, st, q);
+        else hipLaunchKernelGGL((conv3_pipe_kernel<false, 4>), pl.grid, dim3(512), 0, st, q);
     } else {
-        if (out_split) hipLaunchKernelGGL((conv3_pipe_kernel<true, 1>), grid, dim3(512), 0, st, q);
-        else hipLaunchKernelGGL((conv3_pipe_kernel<false, 1>), grid, dim3(512), 0, st, q);
+        if (out_split) hipLaunchKernelGGL((conv3_pipe_kernel<true, 1>), pl.grid, dim3(512), 0, st, q);
+        else hipLaunchKernelGGL((conv3_pipe_kernel<false, 1>), pl.grid, dim3(512), 0, st, q);
     }
     return emd::check_launch("conv3_pipe_kernel");
 }
-
-}  // namespace emd

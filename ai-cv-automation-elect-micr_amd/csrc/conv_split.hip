@@ -4,8 +4,7 @@
 // their routing to the patch-resident kernels conv3_pipe.hip / deconv_pipe.hip).
 #include <cstdlib>
 
-#include "split_params.hpp"
-#include "conv3_params.hpp"
+#include "conv_plan.hpp"
 
 namespace {
 
@@ -817,222 +816,26 @@ __global__ __launch_bounds__(256, 2) void deconv4_half_kernel(const SplitConvPar
 
 }  // namespace
 
-// ---------------------------------------------------------------------------------------------- convolutions on split32 input
-namespace {
-
-void set_taps(SplitConvParams& c, int n, const int* dy, const int* dx) {
-    c.ntaps = n;
-    c.dyp = c.dxp = 0;
-    for (int t = 0; t < n; ++t) {
-        c.dyp |= (unsigned long long)((dy ? dy[t] : 0) + 64) << (7 * t);
-        c.dxp |= (unsigned long long)((dx ? dx[t] : 0) + 64) << (7 * t);
-    }
-}
-
-int conv_checks(const void* xs, int ldx, const uint16_t* whi, const uint16_t* wlo, const float* scale1, const float* shift1,
-                const float* scale2, const float* shift2, const float* res, int ldres, void* y, int ldy, int Cin, int Cout,
-                int out_split) {
-    EMD_REQUIRE(xs && whi && wlo && scale1 && shift1 && y, EMD_E_INVALID, "split32 conv: null pointer");
-    EMD_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), EMD_E_INVALID, "split32 conv: scale2/shift2 must come together");
-    EMD_REQUIRE(Cin >= 1 && Cin <= 2048 && Cout >= 4 && Cout % 4 == 0, EMD_E_INVALID, "split32 conv: 1 <= Cin <= 2048, Cout a multiple of 4");
-    EMD_REQUIRE(ldx % 32 == 0 && ldx >= emd_split32_ld(Cin) && (reinterpret_cast<uintptr_t>(xs) & 127u) == 0, EMD_E_ALIGN,
-                "split32 conv: xs 128-byte aligned, ldx a multiple of 32, >= ceil32(Cin)");
-    if (out_split)
-        EMD_REQUIRE(ldy % 32 == 0 && ldy >= emd_split32_ld(Cout) && (reinterpret_cast<uintptr_t>(y) & 127u) == 0, EMD_E_ALIGN,
-                    "split32 conv: split32 output needs y 128-byte aligned, ldy a multiple of 32, >= ceil32(Cout)");
-    else
-        EMD_REQUIRE(ldy % 4 == 0 && ldy >= Cout && emd::aligned16(y), EMD_E_ALIGN, "split32 conv: ldy a multiple of 4, >= Cout; y 16-byte aligned");
-    EMD_REQUIRE(!res || (ldres % 4 == 0 && ldres >= Cout && emd::aligned16(res)), EMD_E_ALIGN, "split32 conv: res alignment");
-    EMD_REQUIRE(emd::aligned16(scale1) && emd::aligned16(shift1) && (!scale2 || (emd::aligned16(scale2) && emd::aligned16(shift2))) &&
-                    emd::aligned16(whi) && emd::aligned16(wlo),
-                EMD_E_ALIGN, "split32 conv: weight planes and scale/shift vectors must be 16-byte aligned");
-    return EMD_OK;
-}
-
-int launch_conv(SplitConvParams& c, hipStream_t st, bool four = false) {
-    SplitGemmParams& p = c.g;
-    c.Cpad = (p.Cin + kBK - 1) / kBK * kBK;
-    c.nkc = (p.Cin + SBK - 1) / SBK;
-    p.Ktot = c.ntaps * c.Cpad;
-    const int bn = p.N <= 64 ? 64 : 128;
-    p.n_mtiles = (int)((p.M + 255) / 256);
-    p.n_ntiles = (p.N + bn - 1) / bn;
-    p.stamps = nullptr;
-    p.nt = split_nt(0);
-    const long nblk = (long)p.n_mtiles * p.n_ntiles;
-    if (nblk <= 0 || nblk > 0x7fffffffL) return emd::fail(EMD_E_UNSUPPORTED, "split32 conv: grid too large");
-    if (p.M > 0x7fffffffL || (!c.flat && (long)(p.M / ((long)c.Hg * c.Wg)) * c.Ha * c.Wa > 0x7fffffffL))
-        return emd::fail(EMD_E_UNSUPPORTED, "split32 conv: more than 2^31 pixels");   // the kernel keeps pixel indices in 32 bits
-    if (four && !c.out_split && !p.res && !p.scale2 && emd::g_knobs.deconv_direct == 2) {   // 128-row tiles, two workgroups per CU
-        p.n_mtiles = (int)((p.M + 127) / 128);
-        const long nb2 = (long)p.n_mtiles * p.n_ntiles;
-        if (nb2 > 0x7fffffffL) return emd::fail(EMD_E_UNSUPPORTED, "split32 conv: grid too large");
-        if (bn == 64) hipLaunchKernelGGL((deconv4_half_kernel<64>), dim3((unsigned)nb2), dim3(256), 0, st, c);
-        else hipLaunchKernelGGL((deconv4_half_kernel<128>), dim3((unsigned)nb2), dim3(256), 0, st, c);
+// plan -> instance (conv_entry.hip made the plan and filled the tile counts and nt from it)
+extern "C" int conv_split_launch(const emd::ConvPlan& pl, const SplitConvParams& c, hipStream_t st) {
+    const dim3 threads(pl.threads);
+    const bool n64 = pl.bn == 64;
+    switch (pl.route) {
+    case emd::kDeconvHalf:    // 128-row tiles, two workgroups per CU
+        if (n64) hipLaunchKernelGGL((deconv4_half_kernel<64>), pl.grid, threads, 0, st, c);
+        else hipLaunchKernelGGL((deconv4_half_kernel<128>), pl.grid, threads, 0, st, c);
         return emd::check_launch("deconv4_half_kernel");
-    }
-    if (four && !c.out_split && !p.res && !p.scale2 && emd::g_knobs.deconv_direct) {   // round 3: epilogue from the registers, next phase's DMA first
-        if (bn == 64) hipLaunchKernelGGL((deconv4_split_kernel<64>), dim3((unsigned)nblk), dim3(512), 0, st, c);
-        else hipLaunchKernelGGL((deconv4_split_kernel<128>), dim3((unsigned)nblk), dim3(512), 0, st, c);
+    case emd::kDeconvSplit:   // epilogue from the registers, next phase's DMA first
+        if (n64) hipLaunchKernelGGL((deconv4_split_kernel<64>), pl.grid, threads, 0, st, c);
+        else hipLaunchKernelGGL((deconv4_split_kernel<128>), pl.grid, threads, 0, st, c);
         return emd::check_launch("deconv4_split_kernel");
+    case emd::kDeconvFour:
+        if (n64) hipLaunchKernelGGL((gemm_split_conv_kernel<64, true>), pl.grid, threads, 0, st, c);
+        else hipLaunchKernelGGL((gemm_split_conv_kernel<128, true>), pl.grid, threads, 0, st, c);
+        break;
+    default:
+        if (n64) hipLaunchKernelGGL((gemm_split_conv_kernel<64>), pl.grid, threads, 0, st, c);
+        else hipLaunchKernelGGL((gemm_split_conv_kernel<128>), pl.grid, threads, 0, st, c);
     }
-    if (four) {
-        if (bn == 64) hipLaunchKernelGGL((gemm_split_conv_kernel<64, true>), dim3((unsigned)nblk), dim3(512), 0, st, c);
-        else hipLaunchKernelGGL((gemm_split_conv_kernel<128, true>), dim3((unsigned)nblk), dim3(512), 0, st, c);
-    } else if (bn == 64) hipLaunchKernelGGL((gemm_split_conv_kernel<64>), dim3((unsigned)nblk), dim3(512), 0, st, c);
-    else hipLaunchKernelGGL((gemm_split_conv_kernel<128>), dim3((unsigned)nblk), dim3(512), 0, st, c);
     return emd::check_launch("gemm_split_conv_kernel");
-}
-
-}  // namespace
-
-extern "C" int emd_conv3x3_split32_f32(const void* xs, int ldx, const uint16_t* whi, const uint16_t* wlo, const float* scale1,
-                                       const float* shift1, const float* scale2, const float* shift2, const float* res,
-                                       int ldres, void* y, int ldy, int B, int H, int W, int Cin, int Cout, int stride,
-                                       int rate, int act, int out_split, emd_stream_t stream) {
-    int rc = conv_checks(xs, ldx, whi, wlo, scale1, shift1, scale2, shift2, res, ldres, y, ldy, Cin, Cout, out_split);
-    if (rc != EMD_OK) return rc;
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_conv3x3_split32_f32: bad shape");
-    EMD_REQUIRE(stride == 1 || stride == 2, EMD_E_UNSUPPORTED, "emd_conv3x3_split32_f32: stride must be 1 or 2");
-    EMD_REQUIRE(rate >= 1 && rate <= 31 && (rate == 1 || stride == 1), EMD_E_UNSUPPORTED,
-                "emd_conv3x3_split32_f32: rate must be 1..31, and 1 when stride is 2");
-    if (B == 0) return EMD_OK;
-    if (stride == 1 && rate == 1 && !res && H >= 8 && B <= 65535 && 9L * W * ldy < (1L << 31)) {   // round 3: the patch-resident kernel (conv3_pipe.hip)
-        emd::Conv3Params q{};
-        q.x = static_cast<const unsigned char*>(xs); q.ldx_bytes = (long)ldx * 4; q.Whi = whi; q.Wlo = wlo; q.y = static_cast<float*>(y);
-        q.scale1 = scale1; q.shift1 = shift1; q.scale2 = scale2; q.shift2 = shift2;
-        q.H = H; q.W = W; q.Cin = (Cin + 31) / 32 * 32; q.Cpad = (Cin + kBK - 1) / kBK * kBK; q.Ktot = 9 * q.Cpad; q.N = Cout; q.ldy = ldy; q.act = act;
-        if (emd::conv3_pipe_covers(q)) return emd::conv3_pipe_launch(q, B, out_split, static_cast<hipStream_t>(stream));
-    }
-    SplitConvParams c{};
-    SplitGemmParams& p = c.g;
-    p.A = static_cast<const unsigned char*>(xs); p.Whi = whi; p.Wlo = wlo; p.C = static_cast<float*>(y); p.res = res;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = scale2; p.shift2 = shift2;
-    p.lda_bytes = (long)ldx * 4; p.N = Cout; p.Cin = Cin; p.ldc = ldy; p.ldres = ldres; p.act = act;
-    const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-    const int eff = 2 * rate + 1;
-    int pth = (Ho - 1) * stride + eff - H, ptw = (Wo - 1) * stride + eff - W;  // TF SAME: total padding
-    if (pth < 0) pth = 0;
-    if (ptw < 0) ptw = 0;
-    const int pt = pth / 2, pl = ptw / 2;
-    p.M = (long)B * Ho * Wo;
-    c.flat = 0; c.out_split = out_split ? 1 : 0;
-    c.Hg = Ho; c.Wg = Wo; c.Ha = H; c.Wa = W; c.Hc = Ho; c.Wc = Wo; c.sa = stride; c.sc = 1; c.py = c.px = 0;
-    int dy[9], dx[9];
-    for (int ky = 0; ky < 3; ++ky)
-        for (int kx = 0; kx < 3; ++kx) {
-            dy[ky * 3 + kx] = ky * rate - pt;
-            dx[ky * 3 + kx] = kx * rate - pl;
-        }
-    set_taps(c, 9, dy, dx);
-    return launch_conv(c, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int emd_deconv3x3s2_split32_f32(const void* xs, int ldx, const uint16_t* const whi[4], const uint16_t* const wlo[4],
-                                           const float* scale1, const float* shift1, void* y, int ldy, int B, int H, int W,
-                                           int Cin, int Cout, int act, int out_split, emd_stream_t stream) {
-    EMD_REQUIRE(whi && wlo, EMD_E_INVALID, "emd_deconv3x3s2_split32_f32: null weight table");
-    for (int ph = 0; ph < 4; ++ph) {
-        int rc = conv_checks(xs, ldx, whi[ph], wlo[ph], scale1, shift1, nullptr, nullptr, nullptr, 0, y, ldy, Cin, Cout, out_split);
-        if (rc != EMD_OK) return rc;
-    }
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_deconv3x3s2_split32_f32: bad shape");
-    if (B == 0) return EMD_OK;
-    for (int ph = 0; ph < 4; ++ph) {
-        SplitConvParams c{};
-        SplitGemmParams& p = c.g;
-        int ky[4], kx[4];
-        const int nt = emd_deconv_phase_taps(ph, ky, kx);
-        p.A = static_cast<const unsigned char*>(xs); p.Whi = whi[ph]; p.Wlo = wlo[ph]; p.C = static_cast<float*>(y); p.res = nullptr;
-        p.scale1 = scale1; p.shift1 = shift1; p.scale2 = p.shift2 = nullptr;
-        p.lda_bytes = (long)ldx * 4; p.N = Cout; p.Cin = Cin; p.ldc = ldy; p.ldres = 0; p.act = act;
-        p.M = (long)B * H * W;
-        c.flat = 0; c.out_split = out_split ? 1 : 0;
-        c.Hg = H; c.Wg = W; c.Ha = H; c.Wa = W; c.Hc = 2 * H; c.Wc = 2 * W; c.sa = 1; c.sc = 2;
-        c.py = ph >> 1; c.px = ph & 1;
-        int dy[4], dx[4];
-        for (int t = 0; t < nt; ++t) {  // kernel index 2 reads the previous input sample
-            dy[t] = ky[t] == 2 ? -1 : 0;
-            dx[t] = kx[t] == 2 ? -1 : 0;
-        }
-        set_taps(c, nt, dy, dx);
-        int rc = launch_conv(c, static_cast<hipStream_t>(stream));
-        if (rc != EMD_OK) return rc;
-    }
-    return EMD_OK;
-}
-
-// The same transposed convolution as ONE launch (gemm_split_conv_kernel<BN, true>): each workgroup computes the four output
-// phases of its 256 input pixels back to back, so the input is fetched from HBM once instead of once per phase launch (the 9 taps'
-// DMA re-reads hit L2).  Same products in the same order as the four-launch form: bit-identical results.
-// Where graph hosts should take the one-launch form (emd_deconv3x3s2_fused_split32_f32) rather than the register-staged four-phase GEMM:
-// always where the patch-resident kernel covers the layer (H % 8 == 0, W % 32 == 0, Cin % 32 == 0: it sums in another order than the GEMM
-// forms, so the choice must not depend on the batch size -- image b of a batch == the image alone, bit for bit), otherwise from 192
-// row tiles on (the GEMM forms agree with each other bit for bit, there the choice is speed only).
-// ONE predicate for "this layer runs on the patch-resident kernel" (deconv_pipe.hip), used by emd_deconv3x3s2_fused_preferred and by the
-// entry point alike, and a function of the LAYER only (H, W, Cin, Cout) -- never of the batch size or of the pitches: the kernel sums in
-// another order than the GEMM forms, so a route that flipped with B (or with the buffer a tensor happens to live in) would break "image b
-// of a batch == the image alone, bit for bit".  What the kernel additionally needs of a call (32-bit in-image offsets: H * W * ldx_bytes <
-// 2^32, 36 * W * ldy < 2^31) is checked by the entry point and REPORTED (EMD_E_UNSUPPORTED) instead of silently falling back to a kernel
-// with other bits; batches beyond the grid's 65535 images are cut into launches of the same kernel.
-static bool deconv_patch_route(int H, int W, int Cin, int Cout) {
-    emd::DeconvPipeParams q{};
-    q.H = H; q.W = W; q.Cin = (Cin + 31) / 32 * 32; q.N = Cout;   // (ldx_bytes = 0: the offset bound is the entry point's to check)
-    return Cin % 32 == 0 && H >= 8 && emd::deconv_pipe_covers(q);
-}
-
-extern "C" int emd_deconv3x3s2_fused_preferred(int B, int H, int W, int Cin, int Cout) {
-    if (deconv_patch_route(H, W, Cin, Cout)) return 1;
-    return (long)B * H * W >= 256L * 192 ? 1 : 0;
-}
-
-extern "C" int emd_deconv3x3s2_fused_split32_f32(const void* xs, int ldx, const uint16_t* const whi[4], const uint16_t* const wlo[4],
-                                                 const float* scale1, const float* shift1, void* y, int ldy, int B, int H, int W,
-                                                 int Cin, int Cout, int act, int out_split, emd_stream_t stream) {
-    EMD_REQUIRE(whi && wlo, EMD_E_INVALID, "emd_deconv3x3s2_fused_split32_f32: null weight table");
-    for (int ph = 0; ph < 4; ++ph) {
-        int rc = conv_checks(xs, ldx, whi[ph], wlo[ph], scale1, shift1, nullptr, nullptr, nullptr, 0, y, ldy, Cin, Cout, out_split);
-        if (rc != EMD_OK) return rc;
-    }
-    EMD_REQUIRE(B >= 0 && H >= 1 && W >= 1, EMD_E_INVALID, "emd_deconv3x3s2_fused_split32_f32: bad shape");
-    if (B == 0) return EMD_OK;
-    if (Cin % 32 == 0 && deconv_patch_route(H, W, Cin, Cout)) {   // the patch-resident kernel (deconv_pipe.hip), dev knob deconv_direct = 3
-        emd::DeconvPipeParams q{};
-        q.x = static_cast<const unsigned char*>(xs); q.ldx_bytes = (long)ldx * 4; q.y = static_cast<float*>(y);
-        for (int ph = 0; ph < 4; ++ph) { q.Whi[ph] = whi[ph]; q.Wlo[ph] = wlo[ph]; }
-        q.scale1 = scale1; q.shift1 = shift1;
-        q.H = H; q.W = W; q.Cin = (Cin + 31) / 32 * 32; q.Cpad = (Cin + kBK - 1) / kBK * kBK; q.N = Cout; q.ldy = ldy; q.act = act;
-        EMD_REQUIRE(emd::deconv_pipe_covers(q) && 36L * W * ldy < (1L << 31), EMD_E_UNSUPPORTED,
-                    "emd_deconv3x3s2_fused_split32_f32: this layer runs on the patch-resident kernel, whose in-image offsets are 32-bit "
-                    "(H * W * ldx * 4 < 2^32, 36 * W * ldy < 2^31): pitch too large (a fallback would change the summation order)");
-        const long in_img = (long)H * W * q.ldx_bytes, out_img = 4L * H * W * ldy * (long)sizeof(float);
-        for (int b0 = 0; b0 < B; b0 += 65535) {   // grid.z <= 65535: the same kernel on slices of the batch
-            const int nb = B - b0 < 65535 ? B - b0 : 65535;
-            q.x = static_cast<const unsigned char*>(xs) + (long)b0 * in_img;
-            q.y = reinterpret_cast<float*>(static_cast<unsigned char*>(y) + (long)b0 * out_img);
-            int rc = emd::deconv_pipe_launch(q, nb, out_split, static_cast<hipStream_t>(stream));
-            if (rc != EMD_OK) return rc;
-        }
-        return EMD_OK;
-    }
-    SplitConvParams c{};
-    SplitGemmParams& p = c.g;
-    p.A = static_cast<const unsigned char*>(xs); p.Whi = whi[0]; p.Wlo = wlo[0]; p.C = static_cast<float*>(y); p.res = nullptr;
-    p.scale1 = scale1; p.shift1 = shift1; p.scale2 = p.shift2 = nullptr;
-    p.lda_bytes = (long)ldx * 4; p.N = Cout; p.Cin = Cin; p.ldc = ldy; p.ldres = 0; p.act = act;
-    p.M = (long)B * H * W;
-    c.flat = 0; c.out_split = out_split ? 1 : 0;
-    c.Hg = H; c.Wg = W; c.Ha = H; c.Wa = W; c.Hc = 2 * H; c.Wc = 2 * W; c.sa = 1; c.sc = 2; c.py = c.px = 0;
-    for (int ph = 0; ph < 4; ++ph) {
-        int ky[4], kx[4], dy[4], dx[4];
-        const int nt = emd_deconv_phase_taps(ph, ky, kx);
-        for (int t = 0; t < nt; ++t) {  // kernel index 2 reads the previous input sample
-            dy[t] = ky[t] == 2 ? -1 : 0;
-            dx[t] = kx[t] == 2 ? -1 : 0;
-        }
-        set_taps(c, nt, dy, dx);
-        c.Whi4[ph] = whi[ph]; c.Wlo4[ph] = wlo[ph]; c.ntaps4[ph] = nt; c.dyp4[ph] = c.dyp; c.dxp4[ph] = c.dxp;
-    }
-    c.ntaps = 4;   // launch_conv derives Ktot from it; the kernel uses the per-phase counts
-    return launch_conv(c, static_cast<hipStream_t>(stream), true);
 }

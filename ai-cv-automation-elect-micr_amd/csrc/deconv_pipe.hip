@@ -6,7 +6,7 @@
 // other last bits.  Reached through emd_deconv3x3s2_fused_split32_f32 (conv_split.hip; dev knob deconv_direct = 3).
 #include <type_traits>
 
-#include "conv3_params.hpp"
+#include "conv_plan.hpp"
 
 namespace {
 
@@ -15,7 +15,7 @@ using namespace emd;
 __device__ __attribute__((aligned(128))) unsigned char g_zero_dc[16384];   // padding pixels: "+ chunk offset" stays inside for Cin <= 4064
 
 // Tap table of slim.conv2d_transpose(k = 3, s = 2, SAME) in the order the nine (phase, tap) weight tiles are brought in, three per step.
-// Phase = 2 py + px of the output pixel (2 i + py, 2 j + px); emd_deconv_phase_taps (gemm_conv.hip) fixes the tap order inside a phase:
+// Phase = 2 py + px of the output pixel (2 i + py, 2 j + px); emd_deconv_phase_taps (conv_entry.hip) fixes the tap order inside a phase:
 // phase 0: kernel (0,0) (0,2) (2,0) (2,2) reading input (i,j) (i,j-1) (i-1,j) (i-1,j-1); phase 1: (0,1) (2,1) reading (i,j) (i-1,j);
 // phase 2: (1,0) (1,2) reading (i,j) (i,j-1); phase 3: (1,1) reading (i,j).  The nine entries are ordered BY INPUT OFFSET -- (0,0) x 4,
 // (0,-1) x 2, (-1,0) x 2, (-1,-1) -- so that the taps of one offset share their A fragments (the four phases read the same input
@@ -425,35 +425,16 @@ __global__ __launch_bounds__(512, 1) void deconv_pipe_kernel(const DeconvPipePar
 
 }  // namespace
 
-namespace emd {
-
-bool deconv_pipe_covers(const DeconvPipeParams& p) {
-    return g_knobs.deconv_direct == 3 && p.H % 8 == 0 && p.W % 32 == 0 && p.Cin % 32 == 0 && p.Cin >= 32 && p.Cin <= 4064 && p.N % 4 == 0 &&
-           p.N <= 1024 && (long)p.H * p.W * p.ldx_bytes < (1L << 32);     // (patch sources are 32-bit offsets inside an image)
-}
-
-int deconv_pipe_launch(const DeconvPipeParams& p, int B, int out_split, hipStream_t st) {
-    DeconvPipeParams q = p;
-    q.ablate = g_knobs.sep_ablate;
-    const int tiles_w = p.W / 32;
-    q.n_ntiles = (p.N + 63) / 64;
-    const long wgs1 = (long)tiles_w * (p.H / 8) * B * q.n_ntiles;
-    int tpw = 1;
-    for (int t : {8, 4, 2})
-        if (tiles_w % t == 0 && wgs1 / t >= 1024) { tpw = t; break; }
-    if (g_knobs.sep_tpw > 0 && tiles_w % g_knobs.sep_tpw == 0) tpw = g_knobs.sep_tpw;
-    q.tpw = tpw;
-    const dim3 grid(tiles_w / tpw * q.n_ntiles, p.H / 8, B);
-    const int epi = g_knobs.epi_width ? g_knobs.epi_width : 1;
-    if (q.ablate) hipLaunchKernelGGL((deconv_pipe_kernel<false, true, 1>), grid, dim3(512), 0, st, q);
+// plan -> instance (conv_entry.hip made the plan and filled q.tpw / q.n_ntiles / q.ablate from it)
+int emd::deconv_pipe_launch(const ConvPlan& pl, const DeconvPipeParams& q, hipStream_t st) {
+    const bool out_split = pl.form != 0;
+    if (pl.ablate) hipLaunchKernelGGL((deconv_pipe_kernel<false, true, 1>), pl.grid, dim3(512), 0, st, q);
     else if (out_split) {
-        if (epi == 1) hipLaunchKernelGGL((deconv_pipe_kernel<true, false, 1>), grid, dim3(512), 0, st, q);
-        else hipLaunchKernelGGL((deconv_pipe_kernel<true, false, 4>), grid, dim3(512), 0, st, q);
+        if (pl.epi == 1) hipLaunchKernelGGL((deconv_pipe_kernel<true, false, 1>), pl.grid, dim3(512), 0, st, q);
+        else hipLaunchKernelGGL((deconv_pipe_kernel<true, false, 4>), pl.grid, dim3(512), 0, st, q);
     } else {
-        if (epi == 1) hipLaunchKernelGGL((deconv_pipe_kernel<false, false, 1>), grid, dim3(512), 0, st, q);
-        else hipLaunchKernelGGL((deconv_pipe_kernel<false, false, 4>), grid, dim3(512), 0, st, q);
+        if (pl.epi == 1) hipLaunchKernelGGL((deconv_pipe_kernel<false, false, 1>), pl.grid, dim3(512), 0, st, q);
+        else hipLaunchKernelGGL((deconv_pipe_kernel<false, false, 4>), pl.grid, dim3(512), 0, st, q);
     }
     return emd::check_launch("deconv_pipe_kernel");
 }
-
-}  // namespace emd

@@ -8,7 +8,9 @@
  *
  * Nothing in the library reads the environment.  The kernel-selection knobs are fields of one struct (csrc/emd_common.hpp, emd::Knobs),
  * set by name through emd_debug_knob; defaults = the measured-best path (the sep_* knobs, epi_width and nt_mask bit 1 are read by
- * csrc/sep_entry.hip, which routes the fused separable conv; emd_debug_sep_plan below shows what they choose):
+ * csrc/sep_entry.hip, which routes the fused separable conv; emd_debug_sep_plan below shows what they choose.  conv3_pipe, deconv_direct,
+ * nt_mask bit 0, and epi_width, sep_tpw and sep_ablate for conv3_pipe / deconv_pipe are read by csrc/conv_entry.hip, which routes the
+ * dense and transposed convs: emd_debug_conv_plan.  The split_* knobs and nt_mask bit 2 are read by csrc/gemm_split.hip):
  *   sep_pipe (1)        1: the LDS-DMA pipelined fused separable conv (csrc/sep_pipe.hip) where it covers the shape, 0: csrc/sep_fused.hip
  *   sep_pipe2_chunk (-1) two fp32 outputs on the 256-column tile (more than 64 channels in one of them; H % 8 == 0, W % 32 == 0): 1 = the whole-chunk
  *                       instance of csrc/sep_pipe2.hip, 0 = csrc/sep_pipe.hip's lockstep kernel (same bits), -1 = the rule (the faster one)
@@ -71,6 +73,19 @@ int emd_debug_sep_pipe2_chunk_covers(int H, int W, int Cin, int Cout, int Cout2)
  * out = {route, waves per workgroup, tiles per workgroup, grid.x, grid.y, grid.z, sep_pipe schedule, epilogue width (0: sep_fused has
  * one form), xcd, nt}. */
 int emd_debug_sep_plan(int B, int H, int W, int Cin, int Cout, int Cout2, int stride, int precision, unsigned flags, int out[10]);
+/* Host only, reads the knobs, touches no device: the plan csrc/conv_entry.hip makes for a dense or transposed conv, or a pointwise one
+ * on fp32 input -- which kernel, on which tiles, with which grid (tests/test_conv_plan.py pins it).  op: 0 emd_conv1x1_f32 (and its _up /
+ * _stats forms), 1 emd_conv3x3_f32, 2 emd_deconv3x3s2_f32, 3 emd_conv1x1_s2_bwd_data_f32, 4 emd_conv3x3_split32_f32,
+ * 5 emd_deconv3x3s2_split32_f32, 6 emd_deconv3x3s2_fused_split32_f32.  stride, rate: 1 where the entry has none.  flags: bit 0 residual,
+ * 1 second affine, 2 split32 output, 3 statistics, 4 upsampled shift.  ldx, ldy: the pixel pitches in the entry's units, 0 = dense (two
+ * routes depend on a pitch: conv3_pipe's 9 * W * ldy < 2^31 and deconv_pipe's 32-bit in-image offsets).  Returns the route, 0 where the
+ * entry would answer EMD_E_UNSUPPORTED for the grid or the pitch (out is then left alone): 1 gemm_conv_kernel, 2 its upsampled-shift
+ * instance, 3 gemm_split_conv_kernel, 4 conv3_pipe_kernel, 5 gemm_split_conv_kernel<., true>, 6 deconv4_split_kernel,
+ * 7 deconv4_half_kernel, 8 deconv_pipe_kernel.  out = {route, tile rows, tile columns, threads per workgroup, grid.x, grid.y, grid.z (of
+ * one launch), launches, tiles per workgroup, epilogue width (both 0 but on routes 4 and 8), nt, form}; form: route 1 / 2: 1 = the flat
+ * row map; 4 / 8: 1 = split32 output. */
+int emd_debug_conv_plan(int op, int B, int H, int W, int Cin, int Cout, int stride, int rate, int precision, unsigned flags, int ldx,
+                        int ldy, int out[12]);
 /* Force the pipeline variant of emd_conv1x1_split32_f32 (csrc/gemm_split.hip); -1 restores the dispatch rule. */
 void emd_debug_split_variant(int v);
 /* Device buffer that the split32 GEMM writes s_memtime phase stamps into (NULL = off). */

@@ -66,6 +66,7 @@ def t64(a):
     (2, 16, 16, 128, 128, 2),    # residual projection, stride 2
     (1, 7, 9, 256, 728, 2),      # stride 2 on odd sizes
     (1, 32, 32, 384, 128, 1),
+    (3, 64, 128, 8, 128, 1),     # 192 tiles of 128 rows: the 128-column instance (tests/test_conv_plan.py: tiles128 = 191 | 192)
 ])
 @pytest.mark.parametrize("prec", [3, 1])
 def test_conv1x1(B, H, W, ci, co, stride, prec):
