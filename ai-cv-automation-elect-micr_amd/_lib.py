@@ -495,6 +495,16 @@ SIGNATURES = {
     "emd_dose_cumulate_i32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # planes minmax B L H W mode out stream
     "emd_dose_rescale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # ---- dataset diversity: row norms, row-distance matrices, the pair statistic (csrc/diversity.hip)
+    # x B H W norms nonfinite stream
+    "emd_row_sq_norms_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "emd_row_distances_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x B H W D workspace ws_bytes stream
+    "emd_row_distances_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_gram_ssd_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # x B H W pairs P ssd status workspace ws_bytes stream
+    "emd_gram_ssd_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
     # ---- the 2-D FFT and the radial frequency profile (csrc/fft.hip)
     "emd_radial_bins": (C.c_int, [C.c_int]),
     "emd_rfft2_workspace_bytes": (C.c_size_t, [C.c_int] * 2),

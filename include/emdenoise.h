@@ -1641,6 +1641,52 @@ int emd_dose_cumulate_i32(int* planes, int B, int L, int H, int W, int* minmax, 
 int emd_dose_rescale(const int* planes, const int* minmax, int B, int L, int H, int W, int mode, void* out, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dataset diversity (csrc/diversity.hip): the arithmetic of misc_py/img_stats.py -- for every image the matrix of
+ * squared Euclidean distances between its rows (the script's `gram`), and for a pair of images the mean squared difference of their
+ * two matrices -- restated from the formulas.  Images are float32 [B,H,W], contiguous; rows are the points.
+ *
+ * Row norms: n[b][i] = sum_k x[b][i][k]^2 in double (every square is exact).  One wave per row: lane l adds the columns l, l + 64, ...
+ *   in ascending order, then the 64 lanes are added as an xor butterfly (offsets 32, 16, .., 1).  nonfinite[b] (int32) = the number of
+ *   pixels of image b that are NaN or +-inf, from the same read (integer adds onto a word that a small launch zeroes).
+ * Products: G[i][j] = sum_k x[i][k] x[j][k] on v_mfma_f32_32x32x2_f32, whose result is bit for bit the float32 fmaf chain over k in
+ *   ascending order.  A chain is at most EMD_DIVERSITY_CHAIN = 256 columns long (columns [256 c, 256 c + 256) of x); at its end the
+ *   float32 accumulators are added, in float32, to a float32 running total and cleared.  (One unbroken chain over W = 2048 lies
+ *   4.2 - 4.6 x further from the float64 product than numpy's float32 dot; chains of 256 lie 0.54 - 0.65 x as far.)  Columns >= W and
+ *   rows >= H enter as zeros and are never read.
+ * Distances (emd_row_distances_f32): D[b][i][j] = (float)((n_i + n_j) - 2 (double)G[i][j]), float32 [B][H][H].  Only the tiles of
+ *   EMD_DIVERSITY_TILE = 128 rows and columns with tj >= ti are computed; D[j][i] is the same float, so D equals its transpose as
+ *   bits.  The diagonal is whatever the arithmetic leaves (zero but for rounding).  H <= 4096.
+ * Pair statistic (emd_gram_ssd_f64): for the pair (a, b) the chains of the two images run in separate accumulators; at a chain's
+ *   end (acc_a - acc_b) is added in float32 to one running total Gd.  E[i][j] = (dn_i + dn_j) - 2 (double)Gd[i][j] with
+ *   dn = n_a - n_b in double; ssd = (sum_ij E[i][j]^2) / H^2.  None of the four H x H matrices is written.  The sum: each lane adds
+ *   E^2 over its own accumulators in double in a fixed order, then the wave (butterfly), then the four waves in order; a tile with
+ *   tj > ti counts twice (E is symmetric); a wave per pair adds the tile sums (lane l the tiles l, l + 64, ..; butterfly) and divides
+ *   by (double)H (double)H.  Hence ssd(a, a) == 0.0 exactly, ssd(a, b) and ssd(b, a) are equal as bits, and a pair's value depends
+ *   neither on the other pairs nor on B.  H <= 8192.
+ * Pair list: pairs is int32 [P][2], DEVICE memory, indices into the one resident stack x [B]; every image is normed once however
+ *   many pairs name it.  status[p]: EMD_DIVERSITY_OK; EMD_DIVERSITY_NONFINITE, a named image has a non-finite pixel (the reference
+ *   skips it); EMD_DIVERSITY_BAD_INDEX, an index outside [0, B).  For a status != 0 ssd[p] is NaN and nothing is read through a bad
+ *   index.  Pairs and images may be replaced between replays of a captured graph.
+ *
+ * No floating-point atomics, no host synchronisation, launches only: capturable on one stream and bitwise
+ * reproducible.  Every argument is checked before any launch: 0 <= B <= 65535, 1 <= W <= 32768, 1 <= H <= the limit
+ * above (8192 for the norms), 0 <= P <= 2^20 and P * T (T + 1) / 2 < 2^31 with T = ceil(H / 128); B == 0 or P == 0 is a no-op.  The
+ * workspace is the caller's, 16-byte aligned, its size from the _workspace_bytes functions (0 for arguments out of range); outputs and
+ * the workspace overlap nothing.  EMD_DIVERSITY_TILE_K = 32 columns are staged in LDS at a time. */
+#define EMD_DIVERSITY_TILE 128
+#define EMD_DIVERSITY_TILE_K 32
+#define EMD_DIVERSITY_CHAIN 256
+#define EMD_DIVERSITY_OK 0
+#define EMD_DIVERSITY_NONFINITE 1
+#define EMD_DIVERSITY_BAD_INDEX 2
+int emd_row_sq_norms_f64(const float* x, int B, int H, int W, double* norms, int* nonfinite, emd_stream_t stream);
+size_t emd_row_distances_workspace_bytes(int B, int H, int W);
+int emd_row_distances_f32(const float* x, int B, int H, int W, float* D, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_gram_ssd_workspace_bytes(int B, int H, int W, int P);
+int emd_gram_ssd_f64(const float* x, int B, int H, int W, const int* pairs, int P, double* ssd, int* status, void* workspace,
+                     size_t workspace_bytes, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Host utility (no GPU): CRC-32C (Castagnoli) of a HOST buffer, continuing from `crc` (0 to start).
  * Used by the TFRecord reader (emdenoise.input_pipeline) for the container that
  * misc_py/TFRecord_creator.py:57-85 writes with tf.python_io.TFRecordWriter. */
