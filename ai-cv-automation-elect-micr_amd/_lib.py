@@ -527,6 +527,18 @@ SIGNATURES = {
     # images N s pad_periods defocus wavelength px cs iterations flags E stack losses workspace ws_bytes stream
     "emd_exitwave_reconstruct_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                                C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_exitwave_candidates_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # images C N s pad_periods defocus_table wavelength px cs iterations flags losses worst E stack workspace ws_bytes stream
+    "emd_exitwave_candidates_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                              C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p]),
+    # method C N s pad_periods
+    "emd_exitwave_search_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
+    # images N s pad_periods ramp seed method C rounds wavelength px cs iterations flags result history_increments history_losses
+    # status E workspace ws_bytes stream
+    "emd_exitwave_search_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # ---- registration of a focal series (csrc/register.hip)
     # S w1 w2 stream
     "emd_hanning_window_f64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -15,6 +15,9 @@
 //                          image k, multiplies by H(-df_k) and accumulates in registers; then for every k it forms E^ H(+df_k) in LDS,
 //                          transforms back and stores transposed
 //   ew_mean_kernel, ew_modulus_kernel, ew_loss_*  the composed path's mean and modulus constraint, and the loss's two passes
+//   ew_recon_cols_cand_kernel, ew_pass_kernel<MODC>, ew_*_cand_kernel, ew_worst_kernel   the same reconstruction under C defocus
+//                          tables at once: the candidate is a grid dimension, the image of plane b is b mod N
+//   ew_search_*, ew_section_decide_kernel, ew_plateau_decide_kernel   the defocus search's table and decisions, one workgroup each
 //
 // No floating-point atomics, every sum in a fixed order: bitwise reproducible.  Launches only; the defocuses are read on the device.
 #include <cmath>
@@ -27,7 +30,7 @@ namespace {
 constexpr int kMinS = 8, kMaxS = 4096, kMaxN = 64, kMaxIter = 1000000;
 constexpr int kLines = 8;   // lines per workgroup of ew_pass_kernel: 8 x 16 bytes = one 128-byte run of a transposed store
 
-enum { OP_FWD = 0, OP_INV = 1, OP_PROP = 2, OP_MOD = 3 };
+enum { OP_FWD = 0, OP_INV = 1, OP_PROP = 2, OP_MOD = 3, OP_MODC = 4 };   // MODC: MOD over [C][N] planes, the image is b mod nimg
 
 bool size_ok(int S) { return S >= kMinS && S <= kMaxS && (S & (S - 1)) == 0; }
 // the padded side, or 0
@@ -96,14 +99,16 @@ struct PassArgs {
     const double* defocus;   // PROP: df = sign defocus[b]
     double sign;
     Optics o;
-    const float* amp;        // MOD: the image, [B][nlines][S]
+    const float* amp;        // MOD: the image, [B][nlines][S]; MODC: [nimg][nlines][S], image b mod nimg
     int from_intensity;
+    int nimg;                // MODC only (it sits in what was the struct's tail padding)
 };
 
 // grid (ceil(nlines / 8), B), S * 16 bytes of LDS.  A thread reads and rewrites only the elements tid + 256 u of the line outside
 // fft_line, whose first and last statements are barriers: no other barrier is needed between the lines of a workgroup.
 template <int OP>
 __global__ __launch_bounds__(256) void ew_pass_kernel(PassArgs a) {
+    constexpr bool kMod = OP == OP_MOD || OP == OP_MODC;
     extern __shared__ __align__(16) unsigned char smem[];
     cplx* line = reinterpret_cast<cplx*>(smem);
     const int tid = threadIdx.x, S = a.S;
@@ -118,7 +123,7 @@ __global__ __launch_bounds__(256) void ew_pass_kernel(PassArgs a) {
             const cplx* p = static_cast<const cplx*>(a.src) + b * a.src_batch + (long)l * a.src_line;
             for (int i = tid; i < S; i += 256) {
                 cplx v = i < a.n_in ? p[i] : make_double2(0.0, 0.0);
-                if (OP == OP_INV || OP == OP_MOD) v.y = -v.y;
+                if (OP == OP_INV || kMod) v.y = -v.y;
                 line[swz(i)] = v;
             }
         }
@@ -131,8 +136,8 @@ __global__ __launch_bounds__(256) void ew_pass_kernel(PassArgs a) {
             }
             fft_line(line, S, a.tw);
         }
-        if (OP == OP_MOD) {
-            const float* am = a.amp + (b * a.nlines + l) * S;
+        if (kMod) {
+            const float* am = a.amp + ((OP == OP_MODC ? b % a.nimg : b) * a.nlines + l) * S;
             for (int i = tid; i < S; i += 256) {
                 const cplx v = line[swz(i)];
                 line[swz(i)] = restore_amplitude(amplitude(am[i], a.from_intensity), make_double2(v.x * inv, -v.y * inv));
@@ -217,6 +222,85 @@ __global__ __launch_bounds__(256) void ew_recon_cols_kernel(const cplx* __restri
     }
 }
 
+// The same body as a device function, for the candidate form below (ew_recon_cols_kernel keeps its own text, and with it its code
+// object: tools/isa_digest.py).  Keep the two in step.
+template <int NU>
+__device__ __forceinline__ void recon_cols(const cplx* __restrict__ Wt, cplx* __restrict__ G, cplx* __restrict__ Eh, int N, int S,
+                                           const cplx* __restrict__ tw, const double* __restrict__ defocus, Optics o) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    cplx* line = reinterpret_cast<cplx*>(smem);
+    const int tid = threadIdx.x, kx = blockIdx.x;
+    const double inv = 1.0 / (double)S, n = (double)N;
+    cplx acc[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) acc[u] = make_double2(0.0, 0.0);
+    for (int k = 0; k < N; ++k) {   // E^ = sum_k psi^_k H(-df_k), ascending k
+        const cplx* src = Wt + ((long)k * S + kx) * S;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) line[swz(i)] = src[i];
+        }
+        fft_line(line, S, tw);
+        const double df = -defocus[k];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) acc[u] = cadd(acc[u], cmul(line[swz(i)], transfer_h(i, kx, S, df, o)));
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) acc[u] = make_double2(acc[u].x / n, acc[u].y / n);
+    if (Eh) {
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) line[swz(i)] = make_double2(acc[u].x, -acc[u].y);
+        }
+        fft_line(line, S, tw);
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) {
+                const cplx v = line[swz(i)];
+                Eh[(long)i * S + kx] = make_double2(v.x * inv, -v.y * inv);
+            }
+        }
+    }
+    for (int k = 0; k < N; ++k) {   // b^_k = E^ H(+df_k), back along y
+        const double df = defocus[k];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) {
+                const cplx v = cmul(acc[u], transfer_h(i, kx, S, df, o));
+                line[swz(i)] = make_double2(v.x, -v.y);
+            }
+        }
+        fft_line(line, S, tw);
+        cplx* dst = G + (long)k * S * S + kx;
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const int i = tid + 256 * u;
+            if (i < S) {
+                const cplx v = line[swz(i)];
+                dst[(long)i * S] = make_double2(v.x * inv, -v.y * inv);
+            }
+        }
+    }
+}
+
+// The candidate form, grid (S, C): workgroup (kx, c) does for candidate c what ew_recon_cols_kernel does for its one stack, with
+// defocus_table[c][.], W planes w_stride apart (0: every candidate reads the same planes, the images' own transforms in iteration
+// 0), G [C][N][y][kx] and Eh [C][y][kx] (or NULL).
+template <int NU>
+__global__ __launch_bounds__(256) void ew_recon_cols_cand_kernel(const cplx* __restrict__ Wt, long w_stride, cplx* __restrict__ G,
+                                                                 cplx* __restrict__ Eh, int N, int S, const cplx* __restrict__ tw,
+                                                                 const double* __restrict__ defocus_table, Optics o) {
+    const long c = blockIdx.y, plane = (long)S * S;
+    recon_cols<NU>(Wt + c * w_stride, G + c * N * plane, Eh ? Eh + c * plane : nullptr, N, S, tw, defocus_table + c * N, o);
+}
+
 // grid (ceil(n / 256)): E[j] = (sum_k P[k][j]) / N, ascending k
 __global__ __launch_bounds__(256) void ew_mean_kernel(const cplx* __restrict__ P, int N, long n, cplx* __restrict__ E) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
@@ -233,6 +317,15 @@ __global__ __launch_bounds__(256) void ew_modulus_kernel(const cplx* __restrict_
     if (j >= n) return;
     const long e = blockIdx.y * n + j;
     psi[e] = restore_amplitude(amplitude(img[e], from_intensity), Bw[e]);
+}
+
+// grid (ceil(n / 256), C N): the same over [C][N] planes, plane b against image b mod N
+__global__ __launch_bounds__(256) void ew_modulus_cand_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, long n, int N,
+                                                              int from_intensity, cplx* __restrict__ psi) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const long e = blockIdx.y * n + j;
+    psi[e] = restore_amplitude(amplitude(img[(blockIdx.y % N) * n + j], from_intensity), Bw[e]);
 }
 
 #pragma clang fp contract(off)   // the loss: every operation rounds on its own, as in the host restatement
@@ -279,6 +372,146 @@ __global__ __launch_bounds__(256) void ew_loss_final_kernel(const double* __rest
     __shared__ double sh[256];
     const double r = block_sum_fixed(resid + (long)blockIdx.x * s, s, 1, sh);
     if (threadIdx.x == 0) losses[blockIdx.x] = r / ((double)s * (double)s);
+}
+
+// The candidate forms of the two passes above, grid (s, C N): plane b = c N + k of Bw against image k = b mod N.  The same sums in
+// the same order.  (ew_loss_final_kernel reads no image: it runs on C N planes as it is.)
+__global__ __launch_bounds__(256) void ew_loss_rows_cand_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s, int N,
+                                                                double* __restrict__ part) {
+    __shared__ double sh[4];
+    const long row = (long)blockIdx.y * s + blockIdx.x, irow = (long)(blockIdx.y % N) * s + blockIdx.x;
+    double si = 0.0, sI = 0.0;
+    for (int i = threadIdx.x; i < s; i += 256) {
+        const cplx v = Bw[row * s + i];
+        si += (double)img[irow * s + i];
+        sI += v.x * v.x + v.y * v.y;
+    }
+    si = block_sum_thread0(si, sh);
+    sI = block_sum_thread0(sI, sh);
+    if (threadIdx.x == 0) {
+        part[2 * row] = si;
+        part[2 * row + 1] = sI;
+    }
+}
+
+__global__ __launch_bounds__(256) void ew_loss_resid_cand_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s, int N,
+                                                                 const double* __restrict__ part, double* __restrict__ resid) {
+    __shared__ double sh[256];
+    const long b = blockIdx.y, row = b * s + blockIdx.x, irow = (b % N) * s + blockIdx.x;
+    const double npx = (double)s * (double)s;
+    const double si = block_sum_fixed(part + 2 * b * s, s, 2, sh), sI = block_sum_fixed(part + 2 * b * s + 1, s, 2, sh);
+    const double c = (si / npx) / (sI / npx);
+    double r = 0.0;
+    for (int i = threadIdx.x; i < s; i += 256) {
+        const cplx v = Bw[row * s + i];
+        const double d = (double)img[irow * s + i] - c * (v.x * v.x + v.y * v.y);
+        r += d * d;
+    }
+    r = block_tree_sum(r, sh);
+    if (threadIdx.x == 0) resid[row] = r;
+}
+
+// grid (1), C <= 64 threads in use: worst[c] = the largest of losses[c][0..N), ascending k; a NaN loss makes it NaN (torch.max)
+__global__ __launch_bounds__(64) void ew_worst_kernel(const double* __restrict__ losses, int C, int N, double* __restrict__ worst) {
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    double w = losses[(long)c * N];
+    for (int k = 1; k < N; ++k) {
+        const double v = losses[(long)c * N + k];
+        if (w == w && (v != v || v > w)) w = v;
+    }
+    worst[c] = w;
+}
+
+// ---- the defocus search's decisions: one small workgroup between two reconstructions, nothing is read back ------
+
+enum { ST_LO = 0, ST_HI = 1, ST_BEST_INC = 2, ST_BEST_LOSS = 3, ST_PREV = 4, ST_COUNT = 5 };   // doubles of the search state
+enum { SI_STATUS = 0, SI_STEPS = 1, SI_DONE = 2, SI_COUNT = 4 };                               // ints behind them
+
+struct SearchState {
+    double d[ST_COUNT];
+    int i[SI_COUNT];
+};
+
+__device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
+
+// grid (1).  section: seed = (lo, hi); plateau: seed = (incr1, incr2, prev), kept in (lo, hi, prev)
+__global__ __launch_bounds__(64) void ew_search_init_kernel(const double* __restrict__ seed, int plateau, SearchState* __restrict__ st) {
+    if (threadIdx.x != 0) return;
+    st->d[ST_LO] = seed[0];
+    st->d[ST_HI] = seed[1];
+    st->d[ST_BEST_INC] = __longlong_as_double(0x7FF8000000000000ll);
+    st->d[ST_BEST_LOSS] = __longlong_as_double(0x7FF0000000000000ll);
+    st->d[ST_PREV] = plateau ? seed[2] : 0.0;
+    for (int j = 0; j < SI_COUNT; ++j) st->i[j] = 0;
+}
+
+// grid (1), C threads in use: inc_c = lo + c ((hi - lo) / (C - 1)), inc_{C-1} = hi; increments[c] = inc_c; table[c][k] = inc_c ramp[k].
+// C == 1 (a plateau step): the midpoint 0.5 (incr1 + incr2), or incr2 itself once the search is done.  C == -1: the result's row
+// (the best increment of a section search, incr2 of a plateau search); increments may be NULL.
+__global__ __launch_bounds__(64) void ew_search_table_kernel(const SearchState* __restrict__ st, const double* __restrict__ ramp, int C,
+                                                             int N, int plateau, double* __restrict__ increments,
+                                                             double* __restrict__ table) {
+    const int c = threadIdx.x;
+    if (c >= (C < 0 ? 1 : C)) return;
+    const double lo = st->d[ST_LO], hi = st->d[ST_HI];
+    double inc;
+    if (C < 0)
+        inc = plateau ? hi : st->d[ST_BEST_INC];
+    else if (plateau)
+        inc = st->i[SI_DONE] ? hi : 0.5 * (lo + hi);
+    else
+        inc = c == C - 1 ? hi : lo + (double)c * ((hi - lo) / (double)(C - 1));
+    if (increments) increments[c] = inc;
+    for (int k = 0; k < N; ++k) table[(long)c * N + k] = inc * ramp[k];
+}
+
+// grid (1), one thread: the section round's decision from its increments and worst losses [C]
+__global__ __launch_bounds__(64) void ew_section_decide_kernel(const double* __restrict__ increments, const double* __restrict__ worst, int C,
+                                                               SearchState* __restrict__ st) {
+    if (threadIdx.x != 0) return;
+    int best = -1;
+    for (int c = 0; c < C; ++c)
+        if (finite_d(worst[c]) && (best < 0 || worst[c] < worst[best])) best = c;
+    if (best < 0) {
+        st->i[SI_STATUS] |= EMD_SEARCH_NONFINITE;
+        return;
+    }
+    if (worst[best] < st->d[ST_BEST_LOSS]) {
+        st->d[ST_BEST_LOSS] = worst[best];
+        st->d[ST_BEST_INC] = increments[best];
+    }
+    st->d[ST_LO] = increments[best > 0 ? best - 1 : 0];
+    st->d[ST_HI] = increments[best < C - 1 ? best + 1 : C - 1];
+    st->i[SI_STEPS] += 1;
+}
+
+// grid (1), one thread: the plateau step's decision from its increment and loss
+__global__ __launch_bounds__(64) void ew_plateau_decide_kernel(const double* __restrict__ increment, const double* __restrict__ loss,
+                                                               SearchState* __restrict__ st) {
+    if (threadIdx.x != 0 || st->i[SI_DONE]) return;
+    const double l = loss[0];
+    if (!finite_d(l)) {
+        st->i[SI_STATUS] |= EMD_SEARCH_NONFINITE;
+        st->i[SI_DONE] = 1;
+    } else if (l < st->d[ST_PREV]) {
+        st->d[ST_LO] = st->d[ST_HI];
+        st->d[ST_HI] = increment[0];
+        st->d[ST_PREV] = l;
+        st->i[SI_STEPS] += 1;
+    } else {
+        st->i[SI_DONE] = 1;
+    }
+}
+
+// grid (1), one thread: result = (increment, loss), status = (status bits, steps)
+__global__ __launch_bounds__(64) void ew_search_finish_kernel(const SearchState* __restrict__ st, int plateau, double* __restrict__ result,
+                                                              int* __restrict__ status) {
+    if (threadIdx.x != 0) return;
+    result[0] = plateau ? st->d[ST_HI] : st->d[ST_BEST_INC];
+    result[1] = plateau ? st->d[ST_PREV] : st->d[ST_BEST_LOSS];
+    status[0] = st->i[SI_STATUS] | (plateau && !st->i[SI_DONE] ? EMD_SEARCH_UNFINISHED : 0);
+    status[1] = st->i[SI_STEPS];
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
@@ -436,6 +669,183 @@ ReconLayout recon_layout(int N, int s, int S) {
 
 bool batch_ok(int B) { return B >= 0 && B <= 65535; }
 
+// The composed reconstruction (pad_periods > 0, or the development knob): every iteration through the launches of propagate.
+// l is the composed recon_layout; the twiddle table at ws + l.tw is already written.
+void launch_composed(const float* images, int N, int s, int S, const double* defocus, Optics o, int iterations, int fi, cplx* Ew, cplx* stk,
+                     double* losses, char* ws, const ReconLayout& l, hipStream_t st) {
+    const cplx* tw = reinterpret_cast<const cplx*>(ws + l.tw);
+    cplx* A = reinterpret_cast<cplx*>(ws + l.A);
+    cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
+    cplx* T = reinterpret_cast<cplx*>(ws + l.T);
+    cplx* U = reinterpret_cast<cplx*>(ws + l.U);
+    const long ss = (long)s * s;
+    const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
+    for (int it = 0; it < iterations; ++it) {
+        const bool last = it == iterations - 1;
+        launch_propagate(it == 0 ? static_cast<const void*>(images) : A, it == 0 ? (fi ? 2 : 1) : 0, ss, N, s, S, defocus, -1.0, o, tw, T, U, Bf, st);
+        hipLaunchKernelGGL(ew_mean_kernel, dim3(tiles), dim3(256), 0, st, Bf, N, ss, Ew);
+        launch_propagate(Ew, 0, 0, N, s, S, defocus, 1.0, o, tw, T, U, Bf, st);
+        if (!last) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, images, ss, fi, A);
+    }
+    if (stk) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, images, ss, fi, stk);
+    if (losses) launch_losses(Bf, images, N, s, reinterpret_cast<double*>(ws + l.part), reinterpret_cast<double*>(ws + l.resid), losses, st);
+}
+
+// ---- candidates: one stack under C defocus tables ---------------------------------------------------------------
+
+constexpr int kMaxC = 64, kMaxRounds = 1024;
+constexpr int kMaxCandS = 4096;   // the largest side whose candidate column kernel compiles without scratch
+
+bool cand_ok(int C, int N) { return C >= 1 && C <= kMaxC && N >= 1 && N <= kMaxN && (long)C * N <= 65535; }
+bool cand_side_ok(int S) { return S <= kMaxCandS; }
+bool search_ok(int method, int C) {
+    return method == EMD_SEARCH_SECTION ? C >= 3 && C <= kMaxC : method == EMD_SEARCH_PLATEAU && C == 1;
+}
+
+// Fused: W and G are [C][N] stacks, Eh is [C] planes, the loss's sums are [C][N].  Composed: the layout of one reconstruction, which
+// the candidates use one after the other, and an exit wave for the callers that want none.
+struct CandLayout {
+    bool fused;
+    ReconLayout r;
+    size_t Ew, bytes;
+};
+
+CandLayout cand_layout(int C, int N, int s, int S) {
+    CandLayout l{};
+    l.fused = S == s && !emd::g_knobs.exitwave_composed;
+    if (l.fused) {
+        const size_t stack = emd::round256((size_t)C * N * s * s * sizeof(cplx));
+        size_t bytes = 0;
+        l.r.fused = true;
+        l.r.tw = bytes;
+        bytes += emd::round256((size_t)S * sizeof(cplx));
+        l.r.A = bytes;
+        bytes += stack;
+        l.r.Bf = bytes;
+        bytes += stack;
+        l.r.Eh = bytes;
+        bytes += emd::round256((size_t)C * S * S * sizeof(cplx));
+        l.r.part = bytes;
+        bytes += emd::round256((size_t)C * N * s * 2 * sizeof(double));
+        l.r.resid = bytes;
+        bytes += emd::round256((size_t)C * N * s * sizeof(double));
+        l.r.bytes = l.bytes = bytes;
+    } else {
+        l.r = recon_layout(N, s, S);
+        l.Ew = l.r.bytes;
+        l.bytes = l.r.bytes + emd::round256((size_t)s * s * sizeof(cplx));
+    }
+    return l;
+}
+
+// the refusals that emd_exitwave_candidates_f64 and emd_exitwave_search_f64 share, with the offending values
+bool cand_refused(const char* who, int C, int N, int s, int S, int pad_periods, double px, int iterations) {
+    if (!cand_ok(C, N) || !S || !(px > 0.0) || iterations < 1 || iterations > kMaxIter) {
+        emd::set_error("%s: bad shape (1..%d candidates, 1..%d images, candidates x images <= 65535, s (1 + pad_periods) a power of two in "
+                       "%d..%d, px > 0, 1..%d iterations; got %d candidates of %d x %d x %d, pad_periods %d, %d iterations)", who, kMaxC,
+                       kMaxN, kMinS, kMaxS, kMaxIter, C, N, s, s, pad_periods, iterations);
+        return true;
+    }
+    if (S == s && !emd::g_knobs.exitwave_composed && !cand_side_ok(S)) {
+        emd::set_error("%s: the candidate column kernel has no instance for a side of %d (largest: %d); reconstruct the candidates one by "
+                       "one with emd_exitwave_reconstruct_f64", who, S, kMaxCandS);
+        return true;
+    }
+    return false;
+}
+
+void launch_recon_cols_cand(const cplx* Wt, long w_stride, cplx* G, cplx* Eh, int C, int N, int S, const cplx* tw, const double* table,
+                            Optics o, hipStream_t st) {
+    const size_t lds = (size_t)S * sizeof(cplx);
+#define EW_COLS(NU) \
+    hipLaunchKernelGGL(ew_recon_cols_cand_kernel<NU>, dim3((unsigned)S, (unsigned)C), dim3(256), lds, st, Wt, w_stride, G, Eh, N, S, tw, table, o)
+    switch (S / 256) {
+        case 0:
+        case 1: EW_COLS(1); break;
+        case 2: EW_COLS(2); break;
+        case 4: EW_COLS(4); break;
+        case 8: EW_COLS(8); break;
+        default: EW_COLS(16); break;
+    }
+#undef EW_COLS
+}
+
+struct CandArgs {
+    const float* images;
+    int C, N, s, S;
+    const double* table;   // [C][N]
+    Optics o;
+    int iterations, fi;
+    cplx *E, *stack;       // [C][s][s], [C][N][s][s]; either may be NULL
+    double *losses, *worst;   // [C][N], [C]
+};
+
+// Fused: 2 iterations + 6 launches (+ 1 with E, + 1 with the stack) for all candidates together.  Composed: the candidates one after
+// the other through launch_composed, with no host work between them.
+void launch_candidates(const CandArgs& a, char* ws, const CandLayout& l, hipStream_t st) {
+    const int C = a.C, N = a.N, s = a.s, S = a.S, B = C * N;
+    const long ss = (long)s * s;
+    cplx* tw = reinterpret_cast<cplx*>(ws + l.r.tw);
+    launch_twiddle(tw, S, st);
+    if (l.fused) {
+        cplx* A = reinterpret_cast<cplx*>(ws + l.r.A);
+        cplx* Bf = reinterpret_cast<cplx*>(ws + l.r.Bf);
+        cplx* Eh = a.E ? reinterpret_cast<cplx*>(ws + l.r.Eh) : nullptr;
+        double* part = reinterpret_cast<double*>(ws + l.r.part);
+        double* resid = reinterpret_cast<double*>(ws + l.r.resid);
+        const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
+        // the rows of the images, transformed once into candidate 0's planes: psi_k starts as the image under every candidate, so
+        // iteration 0 reads them with candidate stride 0; the first MODC pass then fills every candidate's planes, these included
+        launch_pass<OP_FWD>(pass_args(a.images, a.fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), N, st);
+        for (int it = 0; it < a.iterations; ++it) {
+            const bool last = it == a.iterations - 1;
+            launch_recon_cols_cand(A, it == 0 ? 0 : (long)N * ss, Bf, last ? Eh : nullptr, C, N, S, tw, a.table, a.o, st);
+            if (!last) {
+                PassArgs m = pass_args(Bf, 0, ss, S, S, A, ss, 1, S, S, S, S, tw);
+                m.amp = a.images;
+                m.from_intensity = a.fi;
+                m.nimg = N;
+                launch_pass<OP_MODC>(m, B, st);
+            }
+        }
+        if (a.E) launch_pass<OP_INV>(pass_args(Eh, 0, ss, S, S, a.E, ss, S, 1, S, S, S, tw), C, st);
+        launch_pass<OP_INV>(pass_args(Bf, 0, ss, S, S, A, ss, S, 1, S, S, S, tw), B, st);   // b_k of the last iteration, [C][N][s][s]
+        if (a.stack) hipLaunchKernelGGL(ew_modulus_cand_kernel, dim3(tiles, (unsigned)B), dim3(256), 0, st, A, a.images, ss, N, a.fi, a.stack);
+        hipLaunchKernelGGL(ew_loss_rows_cand_kernel, dim3((unsigned)s, (unsigned)B), dim3(256), 0, st, A, a.images, s, N, part);
+        hipLaunchKernelGGL(ew_loss_resid_cand_kernel, dim3((unsigned)s, (unsigned)B), dim3(256), 0, st, A, a.images, s, N, part, resid);
+        hipLaunchKernelGGL(ew_loss_final_kernel, dim3((unsigned)B), dim3(256), 0, st, resid, s, a.losses);
+    } else {
+        for (int c = 0; c < C; ++c)
+            launch_composed(a.images, N, s, S, a.table + (size_t)c * N, a.o, a.iterations, a.fi,
+                            a.E ? a.E + c * ss : reinterpret_cast<cplx*>(ws + l.Ew), a.stack ? a.stack + (long)c * N * ss : nullptr,
+                            a.losses + (size_t)c * N, ws, l.r, st);
+    }
+    hipLaunchKernelGGL(ew_worst_kernel, dim3(1), dim3(64), 0, st, a.losses, C, N, a.worst);
+}
+
+// the search's state, its defocus table [C][N], the candidates' losses [C][N], a worst loss for the result's own reconstruction
+struct SearchLayout {
+    CandLayout cand;
+    size_t state, table, losses, worst, ws, bytes;
+};
+
+SearchLayout search_layout(int C, int N, int s, int S) {
+    SearchLayout l{};
+    l.cand = cand_layout(C, N, s, S);
+    size_t bytes = 0;
+    l.state = bytes;
+    bytes += emd::round256(sizeof(SearchState));
+    l.table = bytes;
+    bytes += emd::round256((size_t)C * N * sizeof(double));
+    l.losses = bytes;
+    bytes += emd::round256((size_t)C * N * sizeof(double));
+    l.worst = bytes;
+    bytes += emd::round256(sizeof(double));
+    l.ws = bytes;
+    l.bytes = bytes + l.cand.bytes;
+    return l;
+}
+
 }  // namespace
 
 extern "C" int emd_transfer_function_f64(int S, int n, const double* defocus, double wavelength, double px, double cs, double* H,
@@ -574,19 +984,95 @@ extern "C" int emd_exitwave_reconstruct_f64(const float* images, int N, int s, i
         if (stack || losses) launch_pass<OP_INV>(pass_args(Bf, 0, ss, S, S, A, ss, S, 1, S, S, S, tw), N, st);
         bwave = A;
     } else {
-        cplx* T = reinterpret_cast<cplx*>(ws + l.T);
-        cplx* U = reinterpret_cast<cplx*>(ws + l.U);
-        for (int it = 0; it < iterations; ++it) {
-            const bool last = it == iterations - 1;
-            launch_propagate(it == 0 ? static_cast<const void*>(images) : A, it == 0 ? (fi ? 2 : 1) : 0, ss, N, s, S, defocus, -1.0, o, tw, T, U, Bf, st);
-            hipLaunchKernelGGL(ew_mean_kernel, dim3(tiles), dim3(256), 0, st, Bf, N, ss, Ew);
-            launch_propagate(Ew, 0, 0, N, s, S, defocus, 1.0, o, tw, T, U, Bf, st);
-            if (!last) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, images, ss, fi, A);
-        }
-        bwave = Bf;
+        launch_composed(images, N, s, S, defocus, o, iterations, fi, Ew, stk, losses, ws, l, st);
+        return emd::check_launch("emd_exitwave_reconstruct_f64");
     }
     if (stack) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, bwave, images, ss, fi, stk);
     if (losses)
         launch_losses(bwave, images, N, s, reinterpret_cast<double*>(ws + l.part), reinterpret_cast<double*>(ws + l.resid), losses, st);
     return emd::check_launch("emd_exitwave_reconstruct_f64");
+}
+
+extern "C" size_t emd_exitwave_candidates_workspace_bytes(int C, int N, int s, int pad_periods) {
+    const int S = padded_side(s, pad_periods);
+    if (!cand_ok(C, N) || !S) return 0;
+    const CandLayout l = cand_layout(C, N, s, S);
+    return l.fused && !cand_side_ok(S) ? 0 : l.bytes;
+}
+
+extern "C" int emd_exitwave_candidates_f64(const float* images, int C, int N, int s, int pad_periods, const double* defocus_table,
+                                           double wavelength, double px, double cs, int iterations, int flags, double* losses,
+                                           double* worst, double* E, double* stack, void* workspace, size_t workspace_bytes,
+                                           emd_stream_t stream) {
+    const char* who = "emd_exitwave_candidates_f64";
+    const int S = padded_side(s, pad_periods);
+    if (cand_refused(who, C, N, s, S, pad_periods, px, iterations)) return EMD_E_INVALID;
+    const CandLayout l = cand_layout(C, N, s, S);
+    const size_t ne = (size_t)N * s * s, nt = (size_t)C * N * sizeof(double);
+    const Range all[] = {{workspace, l.bytes}, {images, ne * sizeof(float)}, {E, (size_t)C * s * s * sizeof(cplx)},
+                         {stack, C * ne * sizeof(cplx)}, {losses, nt}, {worst, (size_t)C * sizeof(double)}, {defocus_table, nt}};
+    const Range req[] = {all[0], all[1], all[4], all[5], all[6]};
+    const int rc = common_check(who, req, 5, workspace_bytes, all, 7, 4);   // losses, worst, the table: doubles
+    if (rc != EMD_OK) return rc;
+    CandArgs a{images, C, N, s, S, defocus_table, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
+               reinterpret_cast<cplx*>(E), reinterpret_cast<cplx*>(stack), losses, worst};
+    launch_candidates(a, static_cast<char*>(workspace), l, static_cast<hipStream_t>(stream));
+    return emd::check_launch(who);
+}
+
+extern "C" size_t emd_exitwave_search_workspace_bytes(int method, int C, int N, int s, int pad_periods) {
+    const int S = padded_side(s, pad_periods);
+    if (!search_ok(method, C) || !cand_ok(C, N) || !S) return 0;
+    const SearchLayout l = search_layout(C, N, s, S);
+    return l.cand.fused && !cand_side_ok(S) ? 0 : l.bytes;
+}
+
+extern "C" int emd_exitwave_search_f64(const float* images, int N, int s, int pad_periods, const double* ramp, const double* seed,
+                                       int method, int C, int rounds, double wavelength, double px, double cs, int iterations, int flags,
+                                       double* result, double* history_increments, double* history_losses, int* status, double* E,
+                                       void* workspace, size_t workspace_bytes, emd_stream_t stream) {
+    const char* who = "emd_exitwave_search_f64";
+    const int S = padded_side(s, pad_periods);
+    if (!search_ok(method, C) || rounds < 1 || rounds > kMaxRounds) {
+        emd::set_error("%s: bad search (method %d = section: 3..%d candidates; method %d = plateau: 1 candidate; 1..%d rounds or steps; got "
+                       "method %d, %d candidates, %d rounds)", who, EMD_SEARCH_SECTION, kMaxC, EMD_SEARCH_PLATEAU, kMaxRounds, method, C, rounds);
+        return EMD_E_INVALID;
+    }
+    if (cand_refused(who, C, N, s, S, pad_periods, px, iterations)) return EMD_E_INVALID;
+    const SearchLayout l = search_layout(C, N, s, S);
+    const int plateau = method == EMD_SEARCH_PLATEAU;
+    const size_t nh = (size_t)rounds * C * sizeof(double);
+    const Range all[] = {{workspace, l.bytes}, {images, (size_t)N * s * s * sizeof(float)}, {E, (size_t)s * s * sizeof(cplx)},
+                         {result, 2 * sizeof(double)}, {history_increments, nh}, {history_losses, nh}, {status, 2 * sizeof(int)},
+                         {ramp, (size_t)N * sizeof(double)}, {seed, (plateau ? 3 : 2) * sizeof(double)}};
+    const Range req[] = {all[0], all[1], all[3], all[4], all[5], all[6], all[7], all[8]};
+    const int rc = common_check(who, req, 8, workspace_bytes, all, 9, 3);
+    if (rc != EMD_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    SearchState* state = reinterpret_cast<SearchState*>(ws + l.state);
+    double* table = reinterpret_cast<double*>(ws + l.table);
+    double* losses = reinterpret_cast<double*>(ws + l.losses);
+    CandArgs a{images, C, N, s, S, table, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
+               nullptr, nullptr, losses, nullptr};
+    hipLaunchKernelGGL(ew_search_init_kernel, dim3(1), dim3(64), 0, st, seed, plateau, state);
+    for (int r = 0; r < rounds; ++r) {
+        double* inc = history_increments + (size_t)r * C;
+        a.worst = history_losses + (size_t)r * C;
+        hipLaunchKernelGGL(ew_search_table_kernel, dim3(1), dim3(64), 0, st, state, ramp, C, N, plateau, inc, table);
+        launch_candidates(a, ws + l.ws, l.cand, st);
+        if (plateau)
+            hipLaunchKernelGGL(ew_plateau_decide_kernel, dim3(1), dim3(64), 0, st, inc, a.worst, state);
+        else
+            hipLaunchKernelGGL(ew_section_decide_kernel, dim3(1), dim3(64), 0, st, inc, a.worst, C, state);
+    }
+    hipLaunchKernelGGL(ew_search_finish_kernel, dim3(1), dim3(64), 0, st, state, plateau, result, status);
+    if (E) {   // the exit wave at the result: one more reconstruction, of one candidate
+        hipLaunchKernelGGL(ew_search_table_kernel, dim3(1), dim3(64), 0, st, state, ramp, -1, N, plateau, static_cast<double*>(nullptr), table);
+        a.C = 1;
+        a.E = reinterpret_cast<cplx*>(E);
+        a.worst = reinterpret_cast<double*>(ws + l.worst);
+        launch_candidates(a, ws + l.ws, l.cand, st);
+    }
+    return emd::check_launch(who);
 }

@@ -13,7 +13,7 @@ Deviations from the reference: ``px`` (the pixel size) replaces its ``px_dim = 1
 ``|b_k| = 0`` the modulus constraint gives ``a_k`` (the reference: NaN); with ``from_intensity`` the amplitude is
 ``sqrt(max(image_k, 0))`` and ``psi_k`` starts as that amplitude, not as the image; with ``cs != 0`` the back-propagation multiplies
 by ``H(-df)`` as the reference does, which is not ``conj H(df)`` (the Cs term keeps its sign; at ``cs == 0`` the two are equal bit
-for bit); ``aperture_mask``, the bisection after the defocus sweep, ``refine_params``, TIFF reading and the display helpers are not
+for bit); ``aperture_mask``, ``refine_params``, TIFF reading and the display helpers are not
 here.  ``resize_stack`` (``cv2.resize`` of the crops) is ``emdenoise.resample.resize``.
 
 Registration (csrc/register.hip) is what the reference's ``EWREC.__init__`` does before it reconstructs:
@@ -25,6 +25,7 @@ bilinear (the reference weights the wrong tap and returns the integer crop)."""
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -36,6 +37,12 @@ FROM_INTENSITY = 1               # EMD_EXITWAVE_FROM_INTENSITY
 COMPOSED_KNOB = "exitwave_composed"   # include/emdenoise_dev.h: the composed path at pad_periods == 0, for measurements and tests
 PC_WINDOW, PC_CHAIN = 1, 2       # EMD_PC_WINDOW, EMD_PC_CHAIN
 MAX_PAIRS, MAX_CROPS = 64, 65535
+MAX_CANDIDATES, MAX_ROUNDS = 64, 1024   # emd_exitwave_candidates_f64, emd_exitwave_search_f64
+SEARCH_SECTION, SEARCH_PLATEAU = 0, 1   # EMD_SEARCH_SECTION, EMD_SEARCH_PLATEAU
+SEARCH_NONFINITE, SEARCH_UNFINISHED = 1, 2   # the status bits: a non-finite loss met; the plateau search never stopped
+CANDIDATES_WORKSPACE_CAP = 4 << 30      # bytes: reconstruct_candidates runs chunks of candidates above it
+BATCHED_SWEEP_MAX_SIDE = 1024           # defocus_sweep: one candidate-batched call up to this padded side (measured no slower up to
+                                        # it, profiles/exitwave_search_bench.json; not measured above), the sequential loop above it
 
 
 def _padded_side(name, s, pad_periods=0):
@@ -274,11 +281,14 @@ def focal_ramp(n, series_type="cubic", middle=None, alternating=True, increasing
 
 def defocus_sweep(images, wavelength, increments, ramp, **kw):
     """``reconstruction_loss`` for every increment, the defocuses being ``increment * ramp``: float64 ``[len(increments)]``.  The
-    defocuses of all increments are uploaded once, the reconstructions run one after the other on the device, and the losses are
-    read back once at the end (numpy out for numpy images, else a device tensor).  Keywords: ``px``, ``cs``, ``iterations``,
+    defocuses of all increments are uploaded once, the reconstructions run as one candidate-batched call (``reconstruct_candidates``;
+    the same bits) up to a padded side of ``BATCHED_SWEEP_MAX_SIDE``, above it one after the other, and the losses are read back
+    once at the end (numpy out for numpy images, else a device tensor).  Keywords: ``px``, ``cs``, ``iterations``,
     ``pad_periods``, ``from_intensity``; always the largest loss over the images, so ``per_image`` is refused."""
     import torch
 
+    kw = dict(kw)
+    sequential = kw.pop("_sequential", None)
     unknown = sorted(set(kw) - {"px", "cs", "iterations", "pad_periods", "from_intensity", "_composed"})
     if unknown:
         raise TypeError(f"defocus_sweep: unexpected keyword(s) {unknown}")
@@ -294,8 +304,255 @@ def defocus_sweep(images, wavelength, increments, ramp, **kw):
     device = _device(images)
     x, as_np = _wave(images, device, True)
     table = torch.from_numpy(inc[:, None] * ramp[None, :]).to(device)
-    out = torch.stack([reconstruction_loss(x, table[i], wavelength, **kw) for i in range(inc.size)])
+    S = shp[1] * (1 + int(kw.get("pad_periods", 0)))
+    if sequential is None:   # one candidate-batched call where that was measured to be no slower (tools/exitwave_search_bench.py)
+        sequential = S > BATCHED_SWEEP_MAX_SIDE or inc.size * ramp.shape[0] > 65535
+    if sequential:
+        out = torch.stack([reconstruction_loss(x, table[i], wavelength, **kw) for i in range(inc.size)])
+    else:
+        out = reconstruct_candidates(x, table, wavelength, **kw)
     return out.cpu().numpy() if as_np else out
+
+
+def _recon_kw(name, kw):
+    """The reconstruction's keywords with their defaults; anything else is refused."""
+    kw = dict(kw)
+    composed = bool(kw.pop("_composed", False))
+    args = {"px": 1.0, "cs": 0.0, "iterations": 50, "pad_periods": 0, "from_intensity": False}
+    unknown = sorted(set(kw) - set(args))
+    if unknown:
+        raise TypeError(f"{name}: unexpected keyword(s) {unknown}; it takes {sorted(args)}")
+    args.update(kw)
+    _positive(name, px=args["px"])
+    if int(args["iterations"]) != args["iterations"] or args["iterations"] < 1:
+        raise ValueError(f"{name}: iterations must be a positive integer (got {args['iterations']!r})")
+    return args, composed
+
+
+def _images(name, images, pad_periods):
+    shp = tuple(images.shape) if hasattr(images, "shape") else np.shape(images)
+    if len(shp) != 3 or shp[1] != shp[2]:
+        raise ValueError(f"{name}: images are [N,s,s], square (got a shape of {shp})")
+    N, s = int(shp[0]), int(shp[1])
+    if not 1 <= N <= MAX_IMAGES:
+        raise ValueError(f"{name}: 1..{MAX_IMAGES} images (got {N})")
+    _padded_side(name, s, pad_periods)
+    if hasattr(images, "is_complex") and images.is_complex() or not hasattr(images, "is_complex") and np.iscomplexobj(images):
+        raise ValueError(f"{name}: the images are real (float32)")
+    return N, s
+
+
+class _composed_knob:
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        if self.on:
+            _lib.knob(COMPOSED_KNOB, 1)
+
+    def __exit__(self, *exc):
+        if self.on:
+            _lib.knob(COMPOSED_KNOB, 0)
+
+
+def reconstruct_candidates(images, defocus_table, wavelength, px=1.0, cs=0.0, iterations=50, pad_periods=0, from_intensity=False,
+                           per_image=False, return_waves=False, return_stack=False, candidates_per_launch=None, _composed=False):
+    """One stack ``images`` ``[N,s,s]`` reconstructed under every row of ``defocus_table`` ``[C,N]`` in one call
+    (``emd_exitwave_candidates_f64``): the largest loss over the images of every candidate, float64 ``[C]``, or all of
+    them (``per_image``: ``[C,N]``); ``return_waves`` adds the exit waves ``[C,s,s]``, ``return_stack`` the last psi ``[C,N,s,s]`` (then
+    a tuple).  Every candidate's numbers are bit for bit those of ``reconstruct`` / ``reconstruction_loss`` with its row alone.  A
+    float64 CUDA table is used where it is (capturable); anything else is uploaded and must be finite.  When the workspace for all C
+    exceeds ``CANDIDATES_WORKSPACE_CAP`` bytes the candidates run in chunks, one call after the other on the stream with no
+    synchronisation between them; ``candidates_per_launch`` sets the chunk.  The bits are the same for any chunking."""
+    import torch
+
+    name = "reconstruct_candidates"
+    N, s = _images(name, images, pad_periods)
+    _recon_kw(name, {"px": px, "iterations": iterations})
+    _positive(name, wavelength=wavelength)
+    tshape = tuple(defocus_table.shape) if hasattr(defocus_table, "shape") else np.shape(defocus_table)
+    if len(tshape) != 2 or tshape[1] != N or tshape[0] < 1:
+        raise ValueError(f"{name}: the defocus table is [C,N] = [C,{N}], C >= 1 (got a shape of {tshape})")
+    Ct = int(tshape[0])
+    device = _device(images)
+    if isinstance(defocus_table, torch.Tensor) and defocus_table.is_cuda:
+        if defocus_table.dtype != torch.float64 or not defocus_table.is_contiguous():
+            raise ValueError(f"{name}: a device defocus table must be a contiguous float64 tensor")
+        table = defocus_table
+    else:
+        t = np.ascontiguousarray(defocus_table.cpu() if isinstance(defocus_table, torch.Tensor) else defocus_table, dtype=np.float64)
+        if not np.isfinite(t).all():
+            raise ValueError(f"{name}: the defocuses must be finite")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{name}: the defocus table is not on the device; pass a float64 CUDA tensor when capturing")
+        table = torch.from_numpy(t).to(device)
+    lib = _lib.load()
+    per = min(Ct, MAX_CANDIDATES, 65535 // N)
+    with _composed_knob(_composed):
+        if candidates_per_launch is None:
+            while per > 1 and lib.emd_exitwave_candidates_workspace_bytes(per, N, s, int(pad_periods)) > CANDIDATES_WORKSPACE_CAP:
+                per = (per + 1) // 2
+        else:
+            if int(candidates_per_launch) != candidates_per_launch or not 1 <= candidates_per_launch <= per:
+                raise ValueError(f"{name}: candidates_per_launch must be an integer, 1..{per} (got {candidates_per_launch!r})")
+            per = int(candidates_per_launch)
+        x, as_np = _wave(images, device, True)
+        losses = torch.empty((Ct, N), dtype=torch.float64, device=device)
+        worst = torch.empty((Ct,), dtype=torch.float64, device=device)
+        E = torch.empty((Ct, s, s), dtype=torch.complex128, device=device) if return_waves else None
+        stack = torch.empty((Ct, N, s, s), dtype=torch.complex128, device=device) if return_stack else None
+        nbytes = lib.emd_exitwave_candidates_workspace_bytes(per, N, s, int(pad_periods))
+        ws = _ws(nbytes, device)
+        flags = FROM_INTENSITY if from_intensity else 0
+        for c0 in range(0, Ct, per):
+            n = min(per, Ct - c0)
+            sub = lambda t: _p(t[c0:c0 + n]) if t is not None else None
+            _lib.check(lib.emd_exitwave_candidates_f64(_p(x), n, N, s, int(pad_periods), sub(table), float(wavelength), float(px), float(cs),
+                                                       int(iterations), flags, sub(losses), sub(worst), sub(E), sub(stack), _p(ws), nbytes,
+                                                       _lib.stream_ptr()), "emd_exitwave_candidates_f64")
+    outs = [losses if per_image else worst] + [o for o in (E, stack) if o is not None]
+    outs = [o.cpu().numpy() if as_np else o for o in outs]
+    return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def search_increments(search_range, num):
+    """The increments of the reference's initial sweep (ewrec_class.py:406-414): ``c + m 2^x / 2^num`` for x = 0..num-1 with
+    ``(c, m) = (search_range[0], search_range[1] - search_range[0])``, a geometric ramp from ``c + m / 2^num`` to ``c + m / 2``.
+    Deviation: the reference subtracts 1 from ``2^x / 2^num``, which puts every increment below the range."""
+    lo, hi = (float(v) for v in search_range)
+    if int(num) != num or num < 1 or not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"search_increments: a finite range and a positive integer number (got {search_range!r}, {num!r})")
+    x = np.arange(int(num), dtype=np.float64)
+    return lo + (hi - lo) * (2.0 ** x / 2.0 ** int(num))
+
+
+def plateau_seed(increments, losses):
+    """(incr1, incr2, prev) for the plateau search from a sweep: i = the first smallest loss; the neighbour is i + 1 at the left end,
+    i - 1 at the right end, else the one with the smaller loss (the left one on a tie); incr2 = the increment at i, incr1 = the
+    neighbour's, prev = the loss at i."""
+    inc, loss = np.asarray(increments, np.float64).reshape(-1), np.asarray(losses, np.float64).reshape(-1)
+    if inc.size < 2 or inc.shape != loss.shape or not np.isfinite(loss).all():
+        raise ValueError("plateau_seed: at least two increments, as many finite losses")
+    i = int(np.argmin(loss))
+    j = 1 if i == 0 else i - 1 if i == inc.size - 1 else (i - 1 if loss[i - 1] <= loss[i + 1] else i + 1)
+    return float(inc[j]), float(inc[i]), float(loss[i])
+
+
+class DefocusSearchResult(NamedTuple):
+    increment: object          # the result, and its (largest over the images) loss
+    loss: object
+    defocuses: object          # increment * ramp, [N]
+    history_increments: object   # [rounds, candidates] ("plateau": [max_steps]): every candidate that was reconstructed
+    history_losses: object
+    status: int                # SEARCH_NONFINITE | SEARCH_UNFINISHED
+    steps: int
+    wave: object               # E at the result with return_wave, else None
+
+
+def defocus_search(images, wavelength, ramp, bracket=None, method="section", candidates=8, rounds=4, sweep_increments=None, max_steps=16,
+                   return_wave=False, **kw):
+    """The defocus increment of a focal series whose defocuses are ``increment * ramp``, searched on the device
+    (``emd_exitwave_search_f64``; the reference's ``defocus_initial_estimate``, ewrec_class.py:382-434, repaired).
+
+    ``method="section"``: ``rounds`` rounds of ``candidates`` (3..64) equidistant increments over ``bracket`` = (lo, hi), reconstructed
+    together; every round narrows the bracket to the neighbours of its best candidate; the result is the best over all rounds.
+    ``method="plateau"``: the reference's bisection from the two best neighbours of a sweep over ``sweep_increments`` (run by
+    ``defocus_sweep`` and read back), or from ``bracket`` = (incr1, incr2, prev); at most ``max_steps`` reconstructions.
+
+    ``ramp`` ``[N]`` and ``bracket`` may be float64 CUDA tensors, which are used where they are: then the call is launches only, can be
+    captured, and reads new contents on replay.  Host values are uploaded, and a non-finite bracket is refused.  Keywords: ``px``,
+    ``cs``, ``iterations``, ``pad_periods``, ``from_intensity``.  numpy images: numpy / float fields in the result; CUDA images: device
+    tensors, and ``status`` / ``steps`` are read back unless the stream is capturing (then they are device tensors too)."""
+    import torch
+
+    name = "defocus_search"
+    args, composed = _recon_kw(name, kw)
+    N, s = _images(name, images, args["pad_periods"])
+    _positive(name, wavelength=wavelength)
+    if method not in ("section", "plateau"):
+        raise ValueError(f"{name}: method is 'section' or 'plateau' (got {method!r})")
+    plateau = method == "plateau"
+    C = 1 if plateau else candidates
+    R = max_steps if plateau else rounds
+    if not plateau and (int(C) != C or not 3 <= C <= MAX_CANDIDATES):
+        raise ValueError(f"{name}: 3..{MAX_CANDIDATES} candidates (got {C!r})")
+    if int(R) != R or not 1 <= R <= MAX_ROUNDS:
+        raise ValueError(f"{name}: 1..{MAX_ROUNDS} rounds or steps (got {R!r})")
+    if C * N > 65535:
+        raise ValueError(f"{name}: candidates x images <= 65535 (got {C} x {N})")
+
+    def checked(what, v, n):   # on the host, before anything moves
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            if v.dtype != torch.float64 or v.numel() != n or not v.is_contiguous():
+                raise ValueError(f"{name}: a device {what} must be a contiguous float64 tensor of {n} entries")
+            return v
+        a = np.asarray(v, np.float64).reshape(-1)
+        if a.shape != (n,) or not np.isfinite(a).all():
+            raise ValueError(f"{name}: the {what} has {n} finite entries (got {a!r})")
+        return np.ascontiguousarray(a)
+
+    def on_device(what, v):
+        if isinstance(v, torch.Tensor):
+            return v
+        if capturing:
+            raise RuntimeError(f"{name}: the {what} is not on the device; pass a float64 CUDA tensor when capturing")
+        return torch.from_numpy(v).to(device)
+
+    ramp = checked("ramp", ramp, N)
+    if bracket is not None:
+        bracket = checked("bracket", bracket, 3 if plateau else 2)
+    elif not plateau:
+        raise ValueError(f"{name}: the section search needs bracket = (lo, hi)")
+    elif sweep_increments is None:
+        raise ValueError(f"{name}: the plateau search starts from sweep_increments, or from bracket = (incr1, incr2, prev)")
+    device = _device(images)
+    x, as_np = _wave(images, device, True)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if bracket is None:
+        host_ramp = np.asarray(ramp.cpu() if isinstance(ramp, torch.Tensor) else ramp, np.float64).reshape(-1)
+        sweep = defocus_sweep(x, wavelength, sweep_increments, host_ramp, _composed=composed, **args)
+        bracket = np.array(plateau_seed(sweep_increments, sweep.cpu().numpy()), np.float64)
+    r = on_device("ramp", ramp)
+    seed = on_device("bracket", bracket)
+    lib = _lib.load()
+    result = torch.empty((2,), dtype=torch.float64, device=device)
+    hist_inc = torch.empty((int(R), int(C)), dtype=torch.float64, device=device)
+    hist_loss = torch.empty((int(R), int(C)), dtype=torch.float64, device=device)
+    status = torch.empty((2,), dtype=torch.int32, device=device)
+    E = torch.empty((s, s), dtype=torch.complex128, device=device) if return_wave else None
+    m = SEARCH_PLATEAU if plateau else SEARCH_SECTION
+    with _composed_knob(composed):
+        nbytes = lib.emd_exitwave_search_workspace_bytes(m, int(C), N, s, int(args["pad_periods"]))
+        ws = _ws(nbytes, device)
+        rc = lib.emd_exitwave_search_f64(_p(x), N, s, int(args["pad_periods"]), _p(r), _p(seed), m, int(C), int(R), float(wavelength),
+                                         float(args["px"]), float(args["cs"]), int(args["iterations"]),
+                                         FROM_INTENSITY if args["from_intensity"] else 0, _p(result), _p(hist_inc), _p(hist_loss),
+                                         _p(status), _p(E), _p(ws), nbytes, _lib.stream_ptr())
+    _lib.check(rc, "emd_exitwave_search_f64")
+    if plateau:
+        hist_inc, hist_loss = hist_inc.reshape(-1), hist_loss.reshape(-1)
+    defocuses = result[0] * r
+    if capturing:
+        return DefocusSearchResult(result[0], result[1], defocuses, hist_inc, hist_loss, status[0], status[1], E)
+    st = status.cpu().numpy()
+    if as_np:
+        res = result.cpu().numpy()
+        return DefocusSearchResult(float(res[0]), float(res[1]), defocuses.cpu().numpy(), hist_inc.cpu().numpy(), hist_loss.cpu().numpy(),
+                                   int(st[0]), int(st[1]), None if E is None else E.cpu().numpy())
+    return DefocusSearchResult(result[0], result[1], defocuses, hist_inc, hist_loss, int(st[0]), int(st[1]), E)
+
+
+def estimate_defocuses(stack, wavelength, series_type="cubic", middle=None, alternating=True, increasing=True, search_range=(0.0, 1e-7),
+                       sweep_num=8, max_steps=16, return_wave=False, **kw):
+    """``EWREC.defocus_initial_estimate`` (ewrec_class.py:382-434): ``focal_ramp`` of the series, a sweep over
+    ``search_increments(search_range, sweep_num)``, then the plateau search from its two best neighbours.  A ``DefocusSearchResult``;
+    its ``defocuses`` are the estimate."""
+    shp = tuple(stack.shape) if hasattr(stack, "shape") else np.shape(stack)
+    if len(shp) != 3:
+        raise ValueError(f"estimate_defocuses: the stack is [N,s,s] (got a shape of {shp})")
+    ramp = focal_ramp(shp[0], series_type, middle, alternating, increasing)
+    return defocus_search(stack, wavelength, ramp, method="plateau", sweep_increments=search_increments(search_range, sweep_num),
+                          max_steps=max_steps, return_wave=return_wave, **kw)
 
 
 # ---- registration and cropping (csrc/register.hip; DESIGN.md 3.21) -----------------------------------------------------------------

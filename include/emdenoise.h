@@ -1276,6 +1276,42 @@ int emd_exitwave_reconstruct_f64(const float* images, int N, int s, int pad_peri
                                  double cs, int iterations, int flags, double* E, double* stack, double* losses, void* workspace,
                                  size_t workspace_bytes, emd_stream_t stream);
 
+/* Candidates and the defocus search: ewrec_class.py:382-434, `defocus_initial_estimate`, repaired.
+ *
+ * candidates: one stack images [N][s][s] reconstructed under C defocus tables, defocus_table [C][N] (DEVICE doubles), 1 <= C <= 64,
+ *     C N <= 65535, everything else as emd_exitwave_reconstruct_f64.  losses [C][N]; worst [C] = the largest loss over k, taken in
+ *     ascending k, NaN if any loss is NaN; E [C][s][s] and stack [C][N][s][s] may be NULL.  For every c, losses[c], E[c] and
+ *     stack[c] are bit for bit what emd_exitwave_reconstruct_f64 gives for defocus_table[c] alone: a candidate's bits do not depend
+ *     on C or on the other candidates.  With pad_periods == 0 the candidates are a grid dimension (2 iterations + 6 launches, + 1
+ *     with E, + 1 with the stack, whatever C is); with pad_periods > 0 they run one after the other inside the call.
+ *
+ * search, over defocuses = increment * ramp; ramp [N] and seed are DEVICE doubles, every decision is made on the device, nothing
+ *     is read back: capturable, and a replay reads new images, ramp and seed.  Every operation below is rounded on its own.
+ *   EMD_SEARCH_SECTION, 3 <= C <= 64, `rounds` rounds, seed = (lo, hi).  A round: inc_c = lo + c ((hi - lo) / (C - 1)) for
+ *     c < C - 1, inc_{C-1} = hi; table[c][k] = inc_c ramp[k]; one candidates call; i = the first index of the smallest FINITE worst
+ *     loss; (best increment, best loss) is replaced by (inc_i, worst_i) only if worst_i is strictly smaller; the next bracket is
+ *     (inc[max(i-1, 0)], inc[min(i+1, C-1)]).  No finite candidate: the bracket stays and EMD_SEARCH_NONFINITE is set.  The
+ *     result is the best over ALL rounds (NaN, +inf if there never was one); steps = the rounds that had a finite candidate.
+ *   EMD_SEARCH_PLATEAU (the reference's loop), C = 1, `rounds` = the largest number of steps, seed = (incr1, incr2, prev).  A step:
+ *     inc = 0.5 (incr1 + incr2); one reconstruction; loss < prev: (incr1, incr2, prev) = (incr2, inc, loss); else the search is
+ *     done (a non-finite loss: done, with EMD_SEARCH_NONFINITE).  The launches of the later steps still run: they evaluate incr2
+ *     and change nothing.  The result is (incr2, prev); steps = the steps taken before done; EMD_SEARCH_UNFINISHED: never done.
+ *   result [2] = (increment, loss); history_increments, history_losses [rounds][C]: every candidate and its worst loss; status [2]
+ *     (ints) = (status bits, steps); E [s][s] (may be NULL): the exit wave at the result, by one more reconstruction. */
+#define EMD_SEARCH_SECTION 0
+#define EMD_SEARCH_PLATEAU 1
+#define EMD_SEARCH_NONFINITE 1  /* status bit 1 */
+#define EMD_SEARCH_UNFINISHED 2 /* status bit 2 */
+size_t emd_exitwave_candidates_workspace_bytes(int C, int N, int s, int pad_periods);
+int emd_exitwave_candidates_f64(const float* images, int C, int N, int s, int pad_periods, const double* defocus_table, double wavelength,
+                                double px, double cs, int iterations, int flags, double* losses, double* worst, double* E, double* stack,
+                                void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_exitwave_search_workspace_bytes(int method, int C, int N, int s, int pad_periods);
+int emd_exitwave_search_f64(const float* images, int N, int s, int pad_periods, const double* ramp, const double* seed, int method, int C,
+                            int rounds, double wavelength, double px, double cs, int iterations, int flags, double* result,
+                            double* history_increments, double* history_losses, int* status, double* E, void* workspace,
+                            size_t workspace_bytes, emd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Registration of a focal series (csrc/register.hip): what ewrec_class.py:140-177 does before it reconstructs --
  * the drift between consecutive images by phase correlation (:240-269), the chain of the shifts into one cropping centre per image,
