@@ -539,6 +539,19 @@ SIGNATURES = {
     "emd_exitwave_search_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- the 2-D FFT of any side (csrc/fft_any.hip)
+    "emd_fft_any_line": (C.c_int, [C.c_int]),
+    "emd_cfft2_any_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x x_is_real_f32 B H W inverse out workspace ws_bytes stream
+    "emd_cfft2_any_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    "emd_rfft2_any_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # x B H W spec workspace ws_bytes stream
+    "emd_rfft2_any_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "emd_propagate_any_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    # psi psi_is_real_f32 B H W defocus wavelength px cs out workspace ws_bytes stream
+    "emd_propagate_any_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     # ---- registration of a focal series (csrc/register.hip)
     # S w1 w2 stream
     "emd_hanning_window_f64": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

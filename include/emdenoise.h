@@ -1313,6 +1313,45 @@ int emd_exitwave_search_f64(const float* images, int N, int s, int pad_periods, 
                             size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2-D FFT of any side (csrc/fft_any.hip): numpy.fft.fft2 / ifft2 / rfft2 and Fresnel propagation of [B][H][W]
+ * with H and W independent, in double; complex arrays are interleaved (re, im) doubles.  The functions above keep their limit (a
+ * square whose side is a power of two) and their bits; these are separate entry points.
+ *
+ * A side n is served if it is a power of two, 8 <= n <= 4096, or any n in 2 <= n <= 2048 (2 and 4 included).
+ * Line transform of length n, forward, unnormalised: Y[k] = sum_j x[j] exp(-2 pi i j k / n).
+ *   n a power of two, 8..4096: the radix-4 Stockham line of emd_cfft2_f64, the same bits.
+ *   any other n: Bluestein.  M = max(8, the smallest power of two >= 2 n - 1) (M <= 4096).
+ *       chirp   w[k] = exp(-i pi k^2 / n), evaluated as t = k^2 mod 2 n in integers, w = (cospi(t / n), -sinpi(t / n));
+ *       a[j] = x[j] w[j] for j < n, 0 up to M;   b[j] = conj w[j] for 0 <= j < n, b[M - j] = conj w[j] for 1 <= j < n, 0 elsewhere;
+ *       Bf = FFT_M(b);   Y[k] = w[k] IFFT_M(FFT_M(a) Bf)[k], k < n, with IFFT_M(v) = conj(FFT_M(conj v)) / M (1 / M is exact).
+ *   inverse: x = conj(F(conj Y)) / n, one division per component.
+ * emd_fft_any_line(n): the length of the line a transform of n occupies: n, M, or 0 for an n that is not served.
+ * 2-D: lines along W first, stored transposed, then lines along H, stored transposed again (the order of emd_cfft2_f64); the
+ *   inverse divides by W after the rows and by H after the columns.
+ * cfft2_any: x [B][H][W] complex, or float32 (the real part) when x_is_real_f32 != 0; out [B][H][W].
+ * rfft2_any: spec [B][H][W/2 + 1] = fft2(x)[..., :W/2 + 1], numpy.fft.rfft2's layout.  Every real row is transformed as a complex
+ *   line of which W/2 + 1 elements are kept: twice the row work of emd_rfft2_f64's pair packing.
+ * propagate_any: out[b] = ifft2(fft2(psi[b]) Hf(defocus[b])), no padding.  Hf at the unshifted indices (iy, ix): j = i for
+ *   i < (n + 1) / 2, else i - n (numpy.fft.fftfreq); qy = (double)jy / ((double)H * px), qx = (double)jx / ((double)W * px);
+ *   q2 = qy qy + qx qx;  t = lam df q2 + 0.5 lam^3 Cs q2 q2 (left to right, lam^3 = lam lam lam, every operation rounded on its
+ *   own);  Hf = cospi(t) + i sinpi(t): emd_transfer_function_f64's expression on a rectangle.  Three launches after the tables':
+ *   rows forward; columns forward, times Hf, inverse, in one kernel; rows inverse.  `defocus` is a DEVICE pointer, one per image.
+ * The twiddles of M, the chirp and Bf are written into the workspace by kernels on every call, one set per distinct side: nothing
+ * persists between calls and nothing is uploaded.  No atomics, fixed orders: bitwise reproducible, and an image's bits depend
+ * neither on B nor on the other images.  0 <= B <= 65535 (B == 0 is a no-op).  The workspace is the caller's; it and the complex
+ * arrays are 16-byte aligned (float32 images: 4-byte, defocus: 8-byte); outputs and the workspace may overlap neither one another
+ * nor the inputs.  Launches only, on `stream`: capturable. */
+int emd_fft_any_line(int n);
+size_t emd_cfft2_any_workspace_bytes(int B, int H, int W);
+int emd_cfft2_any_f64(const void* x, int x_is_real_f32, int B, int H, int W, int inverse, double* out, void* workspace,
+                      size_t workspace_bytes, emd_stream_t stream);
+size_t emd_rfft2_any_workspace_bytes(int B, int H, int W);
+int emd_rfft2_any_f64(const float* x, int B, int H, int W, double* spec, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_propagate_any_workspace_bytes(int B, int H, int W);
+int emd_propagate_any_f64(const void* psi, int psi_is_real_f32, int B, int H, int W, const double* defocus, double wavelength, double px,
+                          double cs, double* out, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Registration of a focal series (csrc/register.hip): what ewrec_class.py:140-177 does before it reconstructs --
  * the drift between consecutive images by phase correlation (:240-269), the chain of the shifts into one cropping centre per image,
  * the sub-pixel crop around each centre (:190-229).  cv2 is not available: the formulas below are the specification.  Every pointer
