@@ -10,14 +10,20 @@
 //                          float32 as the real part; elements >= n_in are zeros that are never read), transform, store n_out elements
 //                          with strides of the caller's choice: straight, or TRANSPOSED, where the 8 lines of a workgroup make the
 //                          eight 16-byte pieces of every 128-byte run.  OP: FWD; INV; PROP (forward, times H, inverse, without leaving
-//                          LDS); MOD (inverse, psi = a b / |b|, forward: the fused reconstruction's row launch)
-//   ew_recon_cols_kernel   the fused reconstruction's column launch: a workgroup owns one kx; for k = 0..N-1 it transforms the line of
-//                          image k, multiplies by H(-df_k) and accumulates in registers; then for every k it forms E^ H(+df_k) in LDS,
-//                          transforms back and stores transposed
-//   ew_mean_kernel, ew_modulus_kernel, ew_loss_*  the composed path's mean and modulus constraint, and the loss's two passes
-//   ew_recon_cols_cand_kernel, ew_pass_kernel<MODC>, ew_*_cand_kernel, ew_worst_kernel   the same reconstruction under C defocus
-//                          tables at once: the candidate is a grid dimension, the image of plane b is b mod N
+//                          LDS); MOD (inverse, psi = a b / |b|, forward: the fused reconstruction's row launch); MODC (MOD with the
+//                          image b mod N)
+//   recon_cols             (a device function) the fused reconstruction's column launch: a workgroup owns one kx; for k = 0..N-1 it
+//                          transforms the line of image k, multiplies by H(-df_k) and accumulates in registers; then for every k it
+//                          forms E^ H(+df_k) in LDS, transforms back and stores transposed
+//   ew_recon_cols_cand_kernel, ew_recon_cols_kernel   recon_cols on grid (S, C) for C candidates, and on grid (S) for one
+//   ew_mean_kernel         the composed path's mean
+//   ew_modulus_cand_kernel, ew_loss_rows_cand_kernel, ew_loss_resid_cand_kernel, ew_loss_final_kernel, ew_worst_kernel   the modulus
+//                          constraint in real space, the loss's two passes and its end, the largest loss of a candidate
 //   ew_search_*, ew_section_decide_kernel, ew_plateau_decide_kernel   the defocus search's table and decisions, one workgroup each
+//
+// There is one reconstruction, of one stack under C defocus tables at once: the candidate is a grid dimension, the
+// image of plane b = c N + k is b mod N ("cand" in a name).  emd_exitwave_reconstruct_f64 is C = 1; its two launches
+// of an iteration take the instances without the candidate dimension (ew_recon_cols_kernel, MOD), which were measured faster.
 //
 // No floating-point atomics, every sum in a fixed order: bitwise reproducible.  Launches only; the defocuses are read on the device.
 #include <cmath>
@@ -153,77 +159,9 @@ __global__ __launch_bounds__(256) void ew_pass_kernel(PassArgs a) {
     }
 }
 
-// grid (S), S * 16 bytes of LDS; NU = max(S / 256, 1) elements of the line per thread.  Wt: [N][kx][y] (the rows' transforms,
-// transposed); G: [N][y][kx] (b_k, inverse-transformed along y only); Eh: [y][kx] (the exit wave, likewise), or NULL.
-template <int NU>
-__global__ __launch_bounds__(256) void ew_recon_cols_kernel(const cplx* __restrict__ Wt, cplx* __restrict__ G, cplx* __restrict__ Eh, int N,
-                                                            int S, const cplx* __restrict__ tw, const double* __restrict__ defocus,
-                                                            Optics o) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    cplx* line = reinterpret_cast<cplx*>(smem);
-    const int tid = threadIdx.x, kx = blockIdx.x;
-    const double inv = 1.0 / (double)S, n = (double)N;
-    cplx acc[NU];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) acc[u] = make_double2(0.0, 0.0);
-    for (int k = 0; k < N; ++k) {   // E^ = sum_k psi^_k H(-df_k), ascending k
-        const cplx* src = Wt + ((long)k * S + kx) * S;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = tid + 256 * u;
-            if (i < S) line[swz(i)] = src[i];
-        }
-        fft_line(line, S, tw);
-        const double df = -defocus[k];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = tid + 256 * u;
-            if (i < S) acc[u] = cadd(acc[u], cmul(line[swz(i)], transfer_h(i, kx, S, df, o)));
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < NU; ++u) acc[u] = make_double2(acc[u].x / n, acc[u].y / n);
-    if (Eh) {
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = tid + 256 * u;
-            if (i < S) line[swz(i)] = make_double2(acc[u].x, -acc[u].y);
-        }
-        fft_line(line, S, tw);
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = tid + 256 * u;
-            if (i < S) {
-                const cplx v = line[swz(i)];
-                Eh[(long)i * S + kx] = make_double2(v.x * inv, -v.y * inv);
-            }
-        }
-    }
-    for (int k = 0; k < N; ++k) {   // b^_k = E^ H(+df_k), back along y
-        const double df = defocus[k];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = tid + 256 * u;
-            if (i < S) {
-                const cplx v = cmul(acc[u], transfer_h(i, kx, S, df, o));
-                line[swz(i)] = make_double2(v.x, -v.y);
-            }
-        }
-        fft_line(line, S, tw);
-        cplx* dst = G + (long)k * S * S + kx;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = tid + 256 * u;
-            if (i < S) {
-                const cplx v = line[swz(i)];
-                dst[(long)i * S] = make_double2(v.x * inv, -v.y * inv);
-            }
-        }
-    }
-}
-
-// The same body as a device function, for the candidate form below (ew_recon_cols_kernel keeps its own text, and with it its code
-// object: tools/isa_digest.py).  Keep the two in step.
+// The column launch's work for one stack, S * 16 bytes of LDS; NU = max(S / 256, 1) elements of the line per thread.  Wt: [N][kx][y]
+// (the rows' transforms, transposed); G: [N][y][kx] (b_k, inverse-transformed along y only); Eh: [y][kx] (the exit wave, likewise),
+// or NULL.
 template <int NU>
 __device__ __forceinline__ void recon_cols(const cplx* __restrict__ Wt, cplx* __restrict__ G, cplx* __restrict__ Eh, int N, int S,
                                            const cplx* __restrict__ tw, const double* __restrict__ defocus, Optics o) {
@@ -290,9 +228,17 @@ __device__ __forceinline__ void recon_cols(const cplx* __restrict__ Wt, cplx* __
     }
 }
 
-// The candidate form, grid (S, C): workgroup (kx, c) does for candidate c what ew_recon_cols_kernel does for its one stack, with
-// defocus_table[c][.], W planes w_stride apart (0: every candidate reads the same planes, the images' own transforms in iteration
-// 0), G [C][N][y][kx] and Eh [C][y][kx] (or NULL).
+// grid (S): workgroup kx runs recon_cols for the one stack of C = 1.  The candidate form below does the same at C = 1, 0.6 us a
+// launch slower (profiles/exitwave_unify.txt); this instance costs three lines.
+template <int NU>
+__global__ __launch_bounds__(256) void ew_recon_cols_kernel(const cplx* __restrict__ Wt, cplx* __restrict__ G, cplx* __restrict__ Eh, int N,
+                                                            int S, const cplx* __restrict__ tw, const double* __restrict__ defocus,
+                                                            Optics o) {
+    recon_cols<NU>(Wt, G, Eh, N, S, tw, defocus, o);
+}
+
+// grid (S, C): workgroup (kx, c) runs recon_cols for candidate c, with defocus_table[c][.], W planes w_stride apart (0: every
+// candidate reads the same planes, the images' own transforms in iteration 0), G [C][N][y][kx] and Eh [C][y][kx] (or NULL).
 template <int NU>
 __global__ __launch_bounds__(256) void ew_recon_cols_cand_kernel(const cplx* __restrict__ Wt, long w_stride, cplx* __restrict__ G,
                                                                  cplx* __restrict__ Eh, int N, int S, const cplx* __restrict__ tw,
@@ -310,16 +256,7 @@ __global__ __launch_bounds__(256) void ew_mean_kernel(const cplx* __restrict__ P
     E[j] = make_double2(s.x / (double)N, s.y / (double)N);
 }
 
-// grid (ceil(n / 256), N): psi = a b / |b|
-__global__ __launch_bounds__(256) void ew_modulus_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, long n, int from_intensity,
-                                                         cplx* __restrict__ psi) {
-    const long j = (long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const long e = blockIdx.y * n + j;
-    psi[e] = restore_amplitude(amplitude(img[e], from_intensity), Bw[e]);
-}
-
-// grid (ceil(n / 256), C N): the same over [C][N] planes, plane b against image b mod N
+// grid (ceil(n / 256), C N): psi = a b / |b| over [C][N] planes, plane b against image b mod N
 __global__ __launch_bounds__(256) void ew_modulus_cand_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, long n, int N,
                                                               int from_intensity, cplx* __restrict__ psi) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
@@ -330,52 +267,7 @@ __global__ __launch_bounds__(256) void ew_modulus_cand_kernel(const cplx* __rest
 
 #pragma clang fp contract(off)   // the loss: every operation rounds on its own, as in the host restatement
 
-// grid (s, N): part[k][y] = (sum of the image's row, sum of I = |b|^2 over the row)
-__global__ __launch_bounds__(256) void ew_loss_rows_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s,
-                                                           double* __restrict__ part) {
-    __shared__ double sh[4];
-    const long row = (long)blockIdx.y * s + blockIdx.x;
-    double si = 0.0, sI = 0.0;
-    for (int i = threadIdx.x; i < s; i += 256) {
-        const cplx v = Bw[row * s + i];
-        si += (double)img[row * s + i];
-        sI += v.x * v.x + v.y * v.y;
-    }
-    si = block_sum_thread0(si, sh);
-    sI = block_sum_thread0(sI, sh);
-    if (threadIdx.x == 0) {
-        part[2 * row] = si;
-        part[2 * row + 1] = sI;
-    }
-}
-
-// grid (s, N): c = mean(image) / mean(I) from the rows' sums, then resid[k][y] = sum over the row of (image - c I)^2
-__global__ __launch_bounds__(256) void ew_loss_resid_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s,
-                                                            const double* __restrict__ part, double* __restrict__ resid) {
-    __shared__ double sh[256];
-    const long k = blockIdx.y, row = k * s + blockIdx.x;
-    const double npx = (double)s * (double)s;
-    const double si = block_sum_fixed(part + 2 * k * s, s, 2, sh), sI = block_sum_fixed(part + 2 * k * s + 1, s, 2, sh);
-    const double c = (si / npx) / (sI / npx);
-    double r = 0.0;
-    for (int i = threadIdx.x; i < s; i += 256) {
-        const cplx v = Bw[row * s + i];
-        const double d = (double)img[row * s + i] - c * (v.x * v.x + v.y * v.y);
-        r += d * d;
-    }
-    r = block_tree_sum(r, sh);
-    if (threadIdx.x == 0) resid[row] = r;
-}
-
-// grid (N)
-__global__ __launch_bounds__(256) void ew_loss_final_kernel(const double* __restrict__ resid, int s, double* __restrict__ losses) {
-    __shared__ double sh[256];
-    const double r = block_sum_fixed(resid + (long)blockIdx.x * s, s, 1, sh);
-    if (threadIdx.x == 0) losses[blockIdx.x] = r / ((double)s * (double)s);
-}
-
-// The candidate forms of the two passes above, grid (s, C N): plane b = c N + k of Bw against image k = b mod N.  The same sums in
-// the same order.  (ew_loss_final_kernel reads no image: it runs on C N planes as it is.)
+// grid (s, C N), plane b = c N + k of Bw against image k = b mod N: part[b][y] = (sum of the image's row, sum of I = |b|^2 over the row)
 __global__ __launch_bounds__(256) void ew_loss_rows_cand_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s, int N,
                                                                 double* __restrict__ part) {
     __shared__ double sh[4];
@@ -394,6 +286,7 @@ __global__ __launch_bounds__(256) void ew_loss_rows_cand_kernel(const cplx* __re
     }
 }
 
+// grid (s, C N): c = mean(image) / mean(I) from the rows' sums, then resid[b][y] = sum over the row of (image - c I)^2
 __global__ __launch_bounds__(256) void ew_loss_resid_cand_kernel(const cplx* __restrict__ Bw, const float* __restrict__ img, int s, int N,
                                                                  const double* __restrict__ part, double* __restrict__ resid) {
     __shared__ double sh[256];
@@ -409,6 +302,13 @@ __global__ __launch_bounds__(256) void ew_loss_resid_cand_kernel(const cplx* __r
     }
     r = block_tree_sum(r, sh);
     if (threadIdx.x == 0) resid[row] = r;
+}
+
+// grid (C N)
+__global__ __launch_bounds__(256) void ew_loss_final_kernel(const double* __restrict__ resid, int s, double* __restrict__ losses) {
+    __shared__ double sh[256];
+    const double r = block_sum_fixed(resid + (long)blockIdx.x * s, s, 1, sh);
+    if (threadIdx.x == 0) losses[blockIdx.x] = r / ((double)s * (double)s);
 }
 
 // grid (1), C <= 64 threads in use: worst[c] = the largest of losses[c][0..N), ascending k; a NaN loss makes it NaN (torch.max)
@@ -516,42 +416,10 @@ __global__ __launch_bounds__(64) void ew_search_finish_kernel(const SearchState*
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-struct Range {
-    const void* p;
-    size_t n;
-};
-
-bool any_overlap(const Range* r, int n) {
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (r[i].p && r[j].p && emd::overlap(r[i].p, r[i].n, r[j].p, r[j].n)) return true;
-    return false;
-}
-
-// The checks the entry points share, behind their shape checks: null pointers, the workspace's size, alignment, overlap.
-// all[0] is the workspace; the first nalign of all hold 16-byte elements, the others doubles (8-byte alignment); a range with
-// p == NULL is an optional argument that is absent.
-int common_check(const char* who, const Range* required, int nreq, size_t workspace_bytes, const Range* all, int nall, int nalign) {
-    for (int i = 0; i < nreq; ++i)
-        if (!required[i].p) {
-            emd::set_error("%s: null pointer", who);
-            return EMD_E_INVALID;
-        }
-    if (workspace_bytes < all[0].n) {
-        emd::set_error("%s: workspace too small (%zu bytes, needs %zu)", who, workspace_bytes, all[0].n);
-        return EMD_E_INVALID;
-    }
-    for (int i = 0; i < nall; ++i)
-        if (all[i].p && (reinterpret_cast<uintptr_t>(all[i].p) & (i < nalign ? 15u : 7u))) {
-            emd::set_error("%s: the inputs, the outputs and the workspace must be 16-byte aligned (arrays of doubles: 8-byte)", who);
-            return EMD_E_ALIGN;
-        }
-    if (any_overlap(all, nall)) {
-        emd::set_error("%s: the inputs, the outputs and the workspace may not overlap", who);
-        return EMD_E_INVALID;
-    }
-    return EMD_OK;
-}
+// The entry points' arguments go through emd::check_ranges behind their shape checks.  No range is marked as an input: every overlap
+// is refused, two inputs' included.  Complex doubles and the images are checked for 16-byte alignment, arrays of doubles for 8-byte.
+using emd::Range;
+constexpr const char* kAligned = "the inputs, the outputs and the workspace must be 16-byte aligned (arrays of doubles: 8-byte)";
 
 template <int OP>
 void launch_pass(const PassArgs& a, int B, hipStream_t st) {
@@ -595,9 +463,18 @@ void launch_propagate(const void* src, int src_real, long src_batch, int B, int 
     launch_pass<OP_INV>(pass_args(U, 0, (long)s * S, S, S, out, (long)s * s, s, 1, s, s, S, tw), B, st);
 }
 
-void launch_recon_cols(const cplx* Wt, cplx* G, cplx* Eh, int N, int S, const cplx* tw, const double* defocus, Optics o, hipStream_t st) {
+static_assert(kMaxS / 256 <= 16, "the column kernel has an instance for every side up to kMaxS: NU = 16 is the largest");
+
+// one stack (C = 1) on the kernel without the candidate dimension: the same work, measured faster
+void launch_recon_cols(const cplx* Wt, long w_stride, cplx* G, cplx* Eh, int C, int N, int S, const cplx* tw, const double* table, Optics o,
+                       hipStream_t st) {
     const size_t lds = (size_t)S * sizeof(cplx);
-#define EW_COLS(NU) hipLaunchKernelGGL(ew_recon_cols_kernel<NU>, dim3((unsigned)S), dim3(256), lds, st, Wt, G, Eh, N, S, tw, defocus, o)
+#define EW_COLS(NU)                                                                                                                     \
+    if (C == 1)                                                                                                                         \
+        hipLaunchKernelGGL(ew_recon_cols_kernel<NU>, dim3((unsigned)S), dim3(256), lds, st, Wt, G, Eh, N, S, tw, table, o);               \
+    else                                                                                                                                \
+        hipLaunchKernelGGL(ew_recon_cols_cand_kernel<NU>, dim3((unsigned)S, (unsigned)C), dim3(256), lds, st, Wt, w_stride, G, Eh, N, S, \
+                           tw, table, o)
     switch (S / 256) {
         case 0:
         case 1: EW_COLS(1); break;
@@ -607,12 +484,6 @@ void launch_recon_cols(const cplx* Wt, cplx* G, cplx* Eh, int N, int S, const cp
         default: EW_COLS(16); break;
     }
 #undef EW_COLS
-}
-
-void launch_losses(const cplx* Bw, const float* images, int N, int s, double* part, double* resid, double* losses, hipStream_t st) {
-    hipLaunchKernelGGL(ew_loss_rows_kernel, dim3((unsigned)s, (unsigned)N), dim3(256), 0, st, Bw, images, s, part);
-    hipLaunchKernelGGL(ew_loss_resid_kernel, dim3((unsigned)s, (unsigned)N), dim3(256), 0, st, Bw, images, s, part, resid);
-    hipLaunchKernelGGL(ew_loss_final_kernel, dim3((unsigned)N), dim3(256), 0, st, resid, s, losses);
 }
 
 struct PropLayout {
@@ -632,27 +503,37 @@ PropLayout prop_layout(int B, int s, int S) {
     return l;
 }
 
-// Fused (pad_periods == 0): W (the rows' transforms, transposed; b_k at the end), G, Eh.  Composed: psi, P (the propagated stack),
-// and the propagation's T and U.  Both: the loss's partial sums.
+constexpr int kMaxC = 64, kMaxRounds = 1024;
+
+bool batch_ok(int B) { return B >= 0 && B <= 65535; }
+bool cand_ok(int C, int N) { return C >= 1 && C <= kMaxC && N >= 1 && N <= kMaxN && (long)C * N <= 65535; }
+bool search_ok(int method, int C) {
+    return method == EMD_SEARCH_SECTION ? C >= 3 && C <= kMaxC : method == EMD_SEARCH_PLATEAU && C == 1;
+}
+
+// The workspace of a reconstruction of one stack under C defocus tables (one stack at its own defocuses is
+// C = 1).  Fused (pad_periods == 0): W [C][N] (the rows' transforms, transposed; b_k at the end), G [C][N], Eh [C], the loss's sums
+// [C][N].  Composed: psi, P (the propagated stack), the propagation's T and U and the loss's sums for one candidate, since the
+// candidates run one after the other; spare_wave: an exit wave for a caller that passes none (the candidates' entry points).
 struct ReconLayout {
     bool fused;
-    size_t tw, A, Bf, Eh, T, U, part, resid, bytes;
+    size_t tw, A, Bf, Eh, T, U, part, resid, Ew, bytes;
 };
 
-ReconLayout recon_layout(int N, int s, int S) {
+ReconLayout recon_layout(int C, int N, int s, int S, bool spare_wave) {
     ReconLayout l{};
     l.fused = S == s && !emd::g_knobs.exitwave_composed;
-    const size_t stack = emd::round256((size_t)N * s * s * sizeof(cplx));
+    const size_t planes = (size_t)(l.fused ? C : 1) * N;
     size_t bytes = 0;
     l.tw = bytes;
     bytes += emd::round256((size_t)S * sizeof(cplx));
     l.A = bytes;    // fused: W; composed: psi
-    bytes += stack;
+    bytes += emd::round256(planes * s * s * sizeof(cplx));
     l.Bf = bytes;   // fused: G; composed: P
-    bytes += stack;
+    bytes += emd::round256(planes * s * s * sizeof(cplx));
     if (l.fused) {
         l.Eh = bytes;
-        bytes += emd::round256((size_t)S * S * sizeof(cplx));
+        bytes += emd::round256((size_t)C * S * S * sizeof(cplx));
     } else {
         l.T = bytes;
         bytes += emd::round256((size_t)N * S * s * sizeof(cplx));
@@ -660,81 +541,14 @@ ReconLayout recon_layout(int N, int s, int S) {
         bytes += emd::round256((size_t)N * s * S * sizeof(cplx));
     }
     l.part = bytes;
-    bytes += emd::round256((size_t)N * s * 2 * sizeof(double));
+    bytes += emd::round256(planes * s * 2 * sizeof(double));
     l.resid = bytes;
-    bytes += emd::round256((size_t)N * s * sizeof(double));
+    bytes += emd::round256(planes * s * sizeof(double));
+    if (!l.fused && spare_wave) {
+        l.Ew = bytes;
+        bytes += emd::round256((size_t)s * s * sizeof(cplx));
+    }
     l.bytes = bytes;
-    return l;
-}
-
-bool batch_ok(int B) { return B >= 0 && B <= 65535; }
-
-// The composed reconstruction (pad_periods > 0, or the development knob): every iteration through the launches of propagate.
-// l is the composed recon_layout; the twiddle table at ws + l.tw is already written.
-void launch_composed(const float* images, int N, int s, int S, const double* defocus, Optics o, int iterations, int fi, cplx* Ew, cplx* stk,
-                     double* losses, char* ws, const ReconLayout& l, hipStream_t st) {
-    const cplx* tw = reinterpret_cast<const cplx*>(ws + l.tw);
-    cplx* A = reinterpret_cast<cplx*>(ws + l.A);
-    cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
-    cplx* T = reinterpret_cast<cplx*>(ws + l.T);
-    cplx* U = reinterpret_cast<cplx*>(ws + l.U);
-    const long ss = (long)s * s;
-    const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
-    for (int it = 0; it < iterations; ++it) {
-        const bool last = it == iterations - 1;
-        launch_propagate(it == 0 ? static_cast<const void*>(images) : A, it == 0 ? (fi ? 2 : 1) : 0, ss, N, s, S, defocus, -1.0, o, tw, T, U, Bf, st);
-        hipLaunchKernelGGL(ew_mean_kernel, dim3(tiles), dim3(256), 0, st, Bf, N, ss, Ew);
-        launch_propagate(Ew, 0, 0, N, s, S, defocus, 1.0, o, tw, T, U, Bf, st);
-        if (!last) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, images, ss, fi, A);
-    }
-    if (stk) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, images, ss, fi, stk);
-    if (losses) launch_losses(Bf, images, N, s, reinterpret_cast<double*>(ws + l.part), reinterpret_cast<double*>(ws + l.resid), losses, st);
-}
-
-// ---- candidates: one stack under C defocus tables ---------------------------------------------------------------
-
-constexpr int kMaxC = 64, kMaxRounds = 1024;
-constexpr int kMaxCandS = 4096;   // the largest side whose candidate column kernel compiles without scratch
-
-bool cand_ok(int C, int N) { return C >= 1 && C <= kMaxC && N >= 1 && N <= kMaxN && (long)C * N <= 65535; }
-bool cand_side_ok(int S) { return S <= kMaxCandS; }
-bool search_ok(int method, int C) {
-    return method == EMD_SEARCH_SECTION ? C >= 3 && C <= kMaxC : method == EMD_SEARCH_PLATEAU && C == 1;
-}
-
-// Fused: W and G are [C][N] stacks, Eh is [C] planes, the loss's sums are [C][N].  Composed: the layout of one reconstruction, which
-// the candidates use one after the other, and an exit wave for the callers that want none.
-struct CandLayout {
-    bool fused;
-    ReconLayout r;
-    size_t Ew, bytes;
-};
-
-CandLayout cand_layout(int C, int N, int s, int S) {
-    CandLayout l{};
-    l.fused = S == s && !emd::g_knobs.exitwave_composed;
-    if (l.fused) {
-        const size_t stack = emd::round256((size_t)C * N * s * s * sizeof(cplx));
-        size_t bytes = 0;
-        l.r.fused = true;
-        l.r.tw = bytes;
-        bytes += emd::round256((size_t)S * sizeof(cplx));
-        l.r.A = bytes;
-        bytes += stack;
-        l.r.Bf = bytes;
-        bytes += stack;
-        l.r.Eh = bytes;
-        bytes += emd::round256((size_t)C * S * S * sizeof(cplx));
-        l.r.part = bytes;
-        bytes += emd::round256((size_t)C * N * s * 2 * sizeof(double));
-        l.r.resid = bytes;
-        bytes += emd::round256((size_t)C * N * s * sizeof(double));
-        l.r.bytes = l.bytes = bytes;
-    } else {
-        l.r = recon_layout(N, s, S);
-        l.Ew = l.r.bytes;
-        l.bytes = l.r.bytes + emd::round256((size_t)s * s * sizeof(cplx));
-    }
     return l;
 }
 
@@ -746,92 +560,109 @@ bool cand_refused(const char* who, int C, int N, int s, int S, int pad_periods, 
                        kMaxN, kMinS, kMaxS, kMaxIter, C, N, s, s, pad_periods, iterations);
         return true;
     }
-    if (S == s && !emd::g_knobs.exitwave_composed && !cand_side_ok(S)) {
-        emd::set_error("%s: the candidate column kernel has no instance for a side of %d (largest: %d); reconstruct the candidates one by "
-                       "one with emd_exitwave_reconstruct_f64", who, S, kMaxCandS);
-        return true;
-    }
     return false;
 }
 
-void launch_recon_cols_cand(const cplx* Wt, long w_stride, cplx* G, cplx* Eh, int C, int N, int S, const cplx* tw, const double* table,
-                            Optics o, hipStream_t st) {
-    const size_t lds = (size_t)S * sizeof(cplx);
-#define EW_COLS(NU) \
-    hipLaunchKernelGGL(ew_recon_cols_cand_kernel<NU>, dim3((unsigned)S, (unsigned)C), dim3(256), lds, st, Wt, w_stride, G, Eh, N, S, tw, table, o)
-    switch (S / 256) {
-        case 0:
-        case 1: EW_COLS(1); break;
-        case 2: EW_COLS(2); break;
-        case 4: EW_COLS(4); break;
-        case 8: EW_COLS(8); break;
-        default: EW_COLS(16); break;
-    }
-#undef EW_COLS
-}
-
-struct CandArgs {
+struct ReconArgs {
     const float* images;
     int C, N, s, S;
     const double* table;   // [C][N]
     Optics o;
     int iterations, fi;
-    cplx *E, *stack;       // [C][s][s], [C][N][s][s]; either may be NULL
-    double *losses, *worst;   // [C][N], [C]
+    cplx *E, *stack;       // [C][s][s], [C][N][s][s]
+    double *losses, *worst;   // [C][N], [C]; any of the four outputs may be NULL (the composed path needs E, or the layout's spare wave)
 };
 
-// Fused: 2 iterations + 6 launches (+ 1 with E, + 1 with the stack) for all candidates together.  Composed: the candidates one after
-// the other through launch_composed, with no host work between them.
-void launch_candidates(const CandArgs& a, char* ws, const CandLayout& l, hipStream_t st) {
-    const int C = a.C, N = a.N, s = a.s, S = a.S, B = C * N;
+// The iterations of the composed reconstruction of one candidate (pad_periods > 0, or the development knob), every one through the
+// launches of propagate; b_k of the last iteration stays in P.  l is the composed layout; the twiddle table is already written.
+void launch_composed(const ReconArgs& a, const double* defocus, cplx* Ew, char* ws, const ReconLayout& l, hipStream_t st) {
+    const int N = a.N, s = a.s, S = a.S;
+    const cplx* tw = reinterpret_cast<const cplx*>(ws + l.tw);
+    cplx* A = reinterpret_cast<cplx*>(ws + l.A);
+    cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
+    cplx* T = reinterpret_cast<cplx*>(ws + l.T);
+    cplx* U = reinterpret_cast<cplx*>(ws + l.U);
     const long ss = (long)s * s;
-    cplx* tw = reinterpret_cast<cplx*>(ws + l.r.tw);
-    launch_twiddle(tw, S, st);
-    if (l.fused) {
-        cplx* A = reinterpret_cast<cplx*>(ws + l.r.A);
-        cplx* Bf = reinterpret_cast<cplx*>(ws + l.r.Bf);
-        cplx* Eh = a.E ? reinterpret_cast<cplx*>(ws + l.r.Eh) : nullptr;
-        double* part = reinterpret_cast<double*>(ws + l.r.part);
-        double* resid = reinterpret_cast<double*>(ws + l.r.resid);
-        const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
-        // the rows of the images, transformed once into candidate 0's planes: psi_k starts as the image under every candidate, so
-        // iteration 0 reads them with candidate stride 0; the first MODC pass then fills every candidate's planes, these included
-        launch_pass<OP_FWD>(pass_args(a.images, a.fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), N, st);
-        for (int it = 0; it < a.iterations; ++it) {
-            const bool last = it == a.iterations - 1;
-            launch_recon_cols_cand(A, it == 0 ? 0 : (long)N * ss, Bf, last ? Eh : nullptr, C, N, S, tw, a.table, a.o, st);
-            if (!last) {
-                PassArgs m = pass_args(Bf, 0, ss, S, S, A, ss, 1, S, S, S, S, tw);
-                m.amp = a.images;
-                m.from_intensity = a.fi;
-                m.nimg = N;
-                launch_pass<OP_MODC>(m, B, st);
-            }
-        }
-        if (a.E) launch_pass<OP_INV>(pass_args(Eh, 0, ss, S, S, a.E, ss, S, 1, S, S, S, tw), C, st);
-        launch_pass<OP_INV>(pass_args(Bf, 0, ss, S, S, A, ss, S, 1, S, S, S, tw), B, st);   // b_k of the last iteration, [C][N][s][s]
-        if (a.stack) hipLaunchKernelGGL(ew_modulus_cand_kernel, dim3(tiles, (unsigned)B), dim3(256), 0, st, A, a.images, ss, N, a.fi, a.stack);
-        hipLaunchKernelGGL(ew_loss_rows_cand_kernel, dim3((unsigned)s, (unsigned)B), dim3(256), 0, st, A, a.images, s, N, part);
-        hipLaunchKernelGGL(ew_loss_resid_cand_kernel, dim3((unsigned)s, (unsigned)B), dim3(256), 0, st, A, a.images, s, N, part, resid);
-        hipLaunchKernelGGL(ew_loss_final_kernel, dim3((unsigned)B), dim3(256), 0, st, resid, s, a.losses);
-    } else {
-        for (int c = 0; c < C; ++c)
-            launch_composed(a.images, N, s, S, a.table + (size_t)c * N, a.o, a.iterations, a.fi,
-                            a.E ? a.E + c * ss : reinterpret_cast<cplx*>(ws + l.Ew), a.stack ? a.stack + (long)c * N * ss : nullptr,
-                            a.losses + (size_t)c * N, ws, l.r, st);
+    const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
+    for (int it = 0; it < a.iterations; ++it) {
+        launch_propagate(it == 0 ? static_cast<const void*>(a.images) : A, it == 0 ? (a.fi ? 2 : 1) : 0, ss, N, s, S, defocus, -1.0, a.o, tw, T,
+                         U, Bf, st);
+        hipLaunchKernelGGL(ew_mean_kernel, dim3(tiles), dim3(256), 0, st, Bf, N, ss, Ew);
+        launch_propagate(Ew, 0, 0, N, s, S, defocus, 1.0, a.o, tw, T, U, Bf, st);
+        if (it < a.iterations - 1)
+            hipLaunchKernelGGL(ew_modulus_cand_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, Bf, a.images, ss, N, a.fi, A);
     }
-    hipLaunchKernelGGL(ew_worst_kernel, dim3(1), dim3(64), 0, st, a.losses, C, N, a.worst);
+}
+
+// The iterations of the fused reconstruction of all candidates together: 2 iterations launches, + 1 for E, + 1 for b_k of the last
+// iteration in real space, [C][N][s][s] over W, which is dead by then, if the stack or the losses are wanted.
+void launch_fused(const ReconArgs& a, char* ws, const ReconLayout& l, hipStream_t st) {
+    const int C = a.C, N = a.N, S = a.S;
+    const long ss = (long)S * S;
+    const cplx* tw = reinterpret_cast<const cplx*>(ws + l.tw);
+    cplx* A = reinterpret_cast<cplx*>(ws + l.A);
+    cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
+    cplx* Eh = a.E ? reinterpret_cast<cplx*>(ws + l.Eh) : nullptr;
+    // the rows of the images, transformed once into candidate 0's planes: psi_k starts as the image under every candidate, so
+    // iteration 0 reads them with candidate stride 0; the first row pass then fills every candidate's planes, these included
+    launch_pass<OP_FWD>(pass_args(a.images, a.fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), N, st);
+    for (int it = 0; it < a.iterations; ++it) {
+        const bool last = it == a.iterations - 1;
+        launch_recon_cols(A, it == 0 ? 0 : (long)N * ss, Bf, last ? Eh : nullptr, C, N, S, tw, a.table, a.o, st);
+        if (!last) {
+            PassArgs m = pass_args(Bf, 0, ss, S, S, A, ss, 1, S, S, S, S, tw);
+            m.amp = a.images;
+            m.from_intensity = a.fi;
+            m.nimg = N;
+            if (C == 1)   // b mod N == b: the instance without the division, 0.4 us a launch faster (profiles/exitwave_unify.txt)
+                launch_pass<OP_MOD>(m, N, st);
+            else
+                launch_pass<OP_MODC>(m, C * N, st);
+        }
+    }
+    if (a.E) launch_pass<OP_INV>(pass_args(Eh, 0, ss, S, S, a.E, ss, S, 1, S, S, S, tw), C, st);
+    if (a.stack || a.losses) launch_pass<OP_INV>(pass_args(Bf, 0, ss, S, S, A, ss, S, 1, S, S, S, tw), C * N, st);
+}
+
+// The one reconstruction path of emd_exitwave_reconstruct_f64 (C = 1, the defocuses as a table of one row),
+// emd_exitwave_candidates_f64 and emd_exitwave_search_f64.  Fused: every candidate in the same launches.  Composed: the candidates
+// one after the other, with no host work between them.  Then, from b_k of the last iteration, the outputs that are asked for: the
+// stack (1 launch), the losses (3) and the worst loss (1).
+void launch_recon(const ReconArgs& a, char* ws, const ReconLayout& l, hipStream_t st) {
+    const int C = a.C, N = a.N, s = a.s;
+    const long ss = (long)s * s;
+    const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
+    const cplx* bwave = reinterpret_cast<const cplx*>(ws + (l.fused ? l.A : l.Bf));   // b_k of the last iteration, [step][N][s][s]
+    double* part = reinterpret_cast<double*>(ws + l.part);
+    double* resid = reinterpret_cast<double*>(ws + l.resid);
+    launch_twiddle(reinterpret_cast<cplx*>(ws + l.tw), a.S, st);
+    const int step = l.fused ? C : 1;   // candidates per pass of this loop
+    for (int c = 0; c < C; c += step) {
+        const unsigned B = (unsigned)(step * N);
+        if (l.fused)
+            launch_fused(a, ws, l, st);
+        else
+            launch_composed(a, a.table + (size_t)c * N, a.E ? a.E + c * ss : reinterpret_cast<cplx*>(ws + l.Ew), ws, l, st);
+        if (a.stack)
+            hipLaunchKernelGGL(ew_modulus_cand_kernel, dim3(tiles, B), dim3(256), 0, st, bwave, a.images, ss, N, a.fi, a.stack + (long)c * N * ss);
+        if (a.losses) {
+            hipLaunchKernelGGL(ew_loss_rows_cand_kernel, dim3((unsigned)s, B), dim3(256), 0, st, bwave, a.images, s, N, part);
+            hipLaunchKernelGGL(ew_loss_resid_cand_kernel, dim3((unsigned)s, B), dim3(256), 0, st, bwave, a.images, s, N, part, resid);
+            hipLaunchKernelGGL(ew_loss_final_kernel, dim3(B), dim3(256), 0, st, resid, s, a.losses + (size_t)c * N);
+        }
+    }
+    if (a.worst) hipLaunchKernelGGL(ew_worst_kernel, dim3(1), dim3(64), 0, st, a.losses, C, N, a.worst);
 }
 
 // the search's state, its defocus table [C][N], the candidates' losses [C][N], a worst loss for the result's own reconstruction
 struct SearchLayout {
-    CandLayout cand;
+    ReconLayout cand;
     size_t state, table, losses, worst, ws, bytes;
 };
 
 SearchLayout search_layout(int C, int N, int s, int S) {
     SearchLayout l{};
-    l.cand = cand_layout(C, N, s, S);
+    l.cand = recon_layout(C, N, s, S, true);
     size_t bytes = 0;
     l.state = bytes;
     bytes += emd::round256(sizeof(SearchState));
@@ -856,9 +687,8 @@ extern "C" int emd_transfer_function_f64(int S, int n, const double* defocus, do
         return EMD_E_INVALID;
     }
     if (n == 0) return EMD_OK;
-    const Range req[] = {{defocus, (size_t)n * sizeof(double)}, {H, (size_t)n * S * S * sizeof(cplx)}};
-    const Range all[] = {{nullptr, 0}, req[1], req[0]};
-    const int rc = common_check("emd_transfer_function_f64", req, 2, 0, all, 3, 2);
+    const Range rg[] = {{H, (size_t)n * S * S * sizeof(cplx), 16}, {defocus, (size_t)n * sizeof(double), 8}};
+    const int rc = emd::check_ranges("emd_transfer_function_f64", rg, 2, kAligned);
     if (rc != EMD_OK) return rc;
     hipLaunchKernelGGL(ew_transfer_kernel, dim3((unsigned)emd::tiles_of(S * S, 256), (unsigned)n), dim3(256), 0,
                        static_cast<hipStream_t>(stream), reinterpret_cast<cplx*>(H), S, defocus, optics(wavelength, px, cs, S));
@@ -878,8 +708,8 @@ extern "C" int emd_cfft2_f64(const double* x, int B, int S, int inverse, double*
     }
     if (B == 0) return EMD_OK;
     const size_t nx = (size_t)B * S * S * sizeof(cplx);
-    const Range all[] = {{workspace, emd_cfft2_workspace_bytes(B, S)}, {x, nx}, {out, nx}};
-    const int rc = common_check("emd_cfft2_f64", all, 3, workspace_bytes, all, 3, 3);
+    const Range rg[] = {{workspace, emd_cfft2_workspace_bytes(B, S), 16}, {x, nx, 16}, {out, nx, 16}};
+    const int rc = emd::check_ranges("emd_cfft2_f64", rg, 3, kAligned, &workspace_bytes);
     if (rc != EMD_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     cplx* tw = static_cast<cplx*>(workspace);
@@ -917,9 +747,9 @@ extern "C" int emd_propagate_f64(const void* psi, int psi_is_real_f32, int B, in
     if (B == 0) return EMD_OK;
     const PropLayout l = prop_layout(B, s, S);
     const size_t ne = (size_t)B * s * s;
-    const Range all[] = {{workspace, l.bytes}, {psi, ne * (psi_is_real_f32 ? sizeof(float) : sizeof(cplx))}, {out, ne * sizeof(cplx)},
-                         {defocus, (size_t)B * sizeof(double)}};
-    const int rc = common_check("emd_propagate_f64", all, 4, workspace_bytes, all, 4, 3);   // the defocuses are doubles
+    const Range rg[] = {{workspace, l.bytes, 16}, {psi, ne * (psi_is_real_f32 ? sizeof(float) : sizeof(cplx)), 16}, {out, ne * sizeof(cplx), 16},
+                       {defocus, (size_t)B * sizeof(double), 8}};
+    const int rc = emd::check_ranges("emd_propagate_f64", rg, 4, kAligned, &workspace_bytes);
     if (rc != EMD_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
@@ -933,7 +763,7 @@ extern "C" int emd_propagate_f64(const void* psi, int psi_is_real_f32, int B, in
 extern "C" size_t emd_exitwave_workspace_bytes(int N, int s, int pad_periods) {
     const int S = padded_side(s, pad_periods);
     if (N < 1 || N > kMaxN || !S) return 0;
-    return recon_layout(N, s, S).bytes;
+    return recon_layout(1, N, s, S, false).bytes;
 }
 
 extern "C" int emd_exitwave_reconstruct_f64(const float* images, int N, int s, int pad_periods, const double* defocus, double wavelength,
@@ -946,58 +776,27 @@ extern "C" int emd_exitwave_reconstruct_f64(const float* images, int N, int s, i
                        pad_periods, iterations);
         return EMD_E_INVALID;
     }
-    const ReconLayout l = recon_layout(N, s, S);
+    const ReconLayout l = recon_layout(1, N, s, S, false);
     const size_t ne = (size_t)N * s * s;
-    const Range all[] = {{workspace, l.bytes},          {images, ne * sizeof(float)},        {E, (size_t)s * s * sizeof(cplx)},
-                         {stack, ne * sizeof(cplx)},    {losses, (size_t)N * sizeof(double)}, {defocus, (size_t)N * sizeof(double)}};
-    const Range req[] = {all[0], all[1], all[2], all[5]};
-    const int rc = common_check("emd_exitwave_reconstruct_f64", req, 4, workspace_bytes, all, 6, 4);   // losses, defocus: doubles
+    const Range rg[] = {{workspace, l.bytes, 16},
+                       {images, ne * sizeof(float), 16},
+                       {E, (size_t)s * s * sizeof(cplx), 16},
+                       {stack, ne * sizeof(cplx), 16, true},
+                       {losses, (size_t)N * sizeof(double), 8, true},
+                       {defocus, (size_t)N * sizeof(double), 8}};
+    const int rc = emd::check_ranges("emd_exitwave_reconstruct_f64", rg, 6, kAligned, &workspace_bytes);
     if (rc != EMD_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    cplx* tw = reinterpret_cast<cplx*>(ws + l.tw);
-    cplx* A = reinterpret_cast<cplx*>(ws + l.A);
-    cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
-    cplx* Ew = reinterpret_cast<cplx*>(E);
-    cplx* stk = reinterpret_cast<cplx*>(stack);
-    const Optics o = optics(wavelength, px, cs, S);
-    const int fi = (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0;
-    const long ss = (long)s * s;
-    const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
-    const cplx* bwave;   // b_k of the last iteration, [N][s][s]
-    launch_twiddle(tw, S, st);
-    if (l.fused) {
-        cplx* Eh = reinterpret_cast<cplx*>(ws + l.Eh);
-        // the rows of the images, transformed and written transposed: W[k][kx][y]
-        launch_pass<OP_FWD>(pass_args(images, fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), N, st);
-        for (int it = 0; it < iterations; ++it) {
-            const bool last = it == iterations - 1;
-            launch_recon_cols(A, Bf, last ? Eh : nullptr, N, S, tw, defocus, o, st);
-            if (!last) {
-                PassArgs m = pass_args(Bf, 0, ss, S, S, A, ss, 1, S, S, S, S, tw);
-                m.amp = images;
-                m.from_intensity = fi;
-                launch_pass<OP_MOD>(m, N, st);
-            }
-        }
-        launch_pass<OP_INV>(pass_args(Eh, 0, 0, S, S, Ew, 0, S, 1, S, S, S, tw), 1, st);
-        if (stack || losses) launch_pass<OP_INV>(pass_args(Bf, 0, ss, S, S, A, ss, S, 1, S, S, S, tw), N, st);
-        bwave = A;
-    } else {
-        launch_composed(images, N, s, S, defocus, o, iterations, fi, Ew, stk, losses, ws, l, st);
-        return emd::check_launch("emd_exitwave_reconstruct_f64");
-    }
-    if (stack) hipLaunchKernelGGL(ew_modulus_kernel, dim3(tiles, (unsigned)N), dim3(256), 0, st, bwave, images, ss, fi, stk);
-    if (losses)
-        launch_losses(bwave, images, N, s, reinterpret_cast<double*>(ws + l.part), reinterpret_cast<double*>(ws + l.resid), losses, st);
+    // one candidate, whose table is the defocuses; E always, no worst loss
+    const ReconArgs a{images, 1, N, s, S, defocus, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
+                      reinterpret_cast<cplx*>(E), reinterpret_cast<cplx*>(stack), losses, nullptr};
+    launch_recon(a, static_cast<char*>(workspace), l, static_cast<hipStream_t>(stream));
     return emd::check_launch("emd_exitwave_reconstruct_f64");
 }
 
 extern "C" size_t emd_exitwave_candidates_workspace_bytes(int C, int N, int s, int pad_periods) {
     const int S = padded_side(s, pad_periods);
     if (!cand_ok(C, N) || !S) return 0;
-    const CandLayout l = cand_layout(C, N, s, S);
-    return l.fused && !cand_side_ok(S) ? 0 : l.bytes;
+    return recon_layout(C, N, s, S, true).bytes;
 }
 
 extern "C" int emd_exitwave_candidates_f64(const float* images, int C, int N, int s, int pad_periods, const double* defocus_table,
@@ -1007,24 +806,27 @@ extern "C" int emd_exitwave_candidates_f64(const float* images, int C, int N, in
     const char* who = "emd_exitwave_candidates_f64";
     const int S = padded_side(s, pad_periods);
     if (cand_refused(who, C, N, s, S, pad_periods, px, iterations)) return EMD_E_INVALID;
-    const CandLayout l = cand_layout(C, N, s, S);
+    const ReconLayout l = recon_layout(C, N, s, S, true);
     const size_t ne = (size_t)N * s * s, nt = (size_t)C * N * sizeof(double);
-    const Range all[] = {{workspace, l.bytes}, {images, ne * sizeof(float)}, {E, (size_t)C * s * s * sizeof(cplx)},
-                         {stack, C * ne * sizeof(cplx)}, {losses, nt}, {worst, (size_t)C * sizeof(double)}, {defocus_table, nt}};
-    const Range req[] = {all[0], all[1], all[4], all[5], all[6]};
-    const int rc = common_check(who, req, 5, workspace_bytes, all, 7, 4);   // losses, worst, the table: doubles
+    const Range rg[] = {{workspace, l.bytes, 16},
+                       {images, ne * sizeof(float), 16},
+                       {E, (size_t)C * s * s * sizeof(cplx), 16, true},
+                       {stack, C * ne * sizeof(cplx), 16, true},
+                       {losses, nt, 8},
+                       {worst, (size_t)C * sizeof(double), 8},
+                       {defocus_table, nt, 8}};
+    const int rc = emd::check_ranges(who, rg, 7, kAligned, &workspace_bytes);
     if (rc != EMD_OK) return rc;
-    CandArgs a{images, C, N, s, S, defocus_table, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
-               reinterpret_cast<cplx*>(E), reinterpret_cast<cplx*>(stack), losses, worst};
-    launch_candidates(a, static_cast<char*>(workspace), l, static_cast<hipStream_t>(stream));
+    const ReconArgs a{images, C, N, s, S, defocus_table, optics(wavelength, px, cs, S), iterations,
+                      (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0, reinterpret_cast<cplx*>(E), reinterpret_cast<cplx*>(stack), losses, worst};
+    launch_recon(a, static_cast<char*>(workspace), l, static_cast<hipStream_t>(stream));
     return emd::check_launch(who);
 }
 
 extern "C" size_t emd_exitwave_search_workspace_bytes(int method, int C, int N, int s, int pad_periods) {
     const int S = padded_side(s, pad_periods);
     if (!search_ok(method, C) || !cand_ok(C, N) || !S) return 0;
-    const SearchLayout l = search_layout(C, N, s, S);
-    return l.cand.fused && !cand_side_ok(S) ? 0 : l.bytes;
+    return search_layout(C, N, s, S).bytes;
 }
 
 extern "C" int emd_exitwave_search_f64(const float* images, int N, int s, int pad_periods, const double* ramp, const double* seed,
@@ -1042,25 +844,30 @@ extern "C" int emd_exitwave_search_f64(const float* images, int N, int s, int pa
     const SearchLayout l = search_layout(C, N, s, S);
     const int plateau = method == EMD_SEARCH_PLATEAU;
     const size_t nh = (size_t)rounds * C * sizeof(double);
-    const Range all[] = {{workspace, l.bytes}, {images, (size_t)N * s * s * sizeof(float)}, {E, (size_t)s * s * sizeof(cplx)},
-                         {result, 2 * sizeof(double)}, {history_increments, nh}, {history_losses, nh}, {status, 2 * sizeof(int)},
-                         {ramp, (size_t)N * sizeof(double)}, {seed, (plateau ? 3 : 2) * sizeof(double)}};
-    const Range req[] = {all[0], all[1], all[3], all[4], all[5], all[6], all[7], all[8]};
-    const int rc = common_check(who, req, 8, workspace_bytes, all, 9, 3);
+    const Range rg[] = {{workspace, l.bytes, 16},
+                        {images, (size_t)N * s * s * sizeof(float), 16},
+                        {E, (size_t)s * s * sizeof(cplx), 16, true},
+                        {result, 2 * sizeof(double), 8},
+                        {history_increments, nh, 8},
+                        {history_losses, nh, 8},
+                        {status, 2 * sizeof(int), 8},
+                        {ramp, (size_t)N * sizeof(double), 8},
+                        {seed, (plateau ? 3 : 2) * sizeof(double), 8}};
+    const int rc = emd::check_ranges(who, rg, 9, kAligned, &workspace_bytes);
     if (rc != EMD_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     SearchState* state = reinterpret_cast<SearchState*>(ws + l.state);
     double* table = reinterpret_cast<double*>(ws + l.table);
     double* losses = reinterpret_cast<double*>(ws + l.losses);
-    CandArgs a{images, C, N, s, S, table, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
-               nullptr, nullptr, losses, nullptr};
+    ReconArgs a{images, C, N, s, S, table, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
+                nullptr, nullptr, losses, nullptr};
     hipLaunchKernelGGL(ew_search_init_kernel, dim3(1), dim3(64), 0, st, seed, plateau, state);
     for (int r = 0; r < rounds; ++r) {
         double* inc = history_increments + (size_t)r * C;
         a.worst = history_losses + (size_t)r * C;
         hipLaunchKernelGGL(ew_search_table_kernel, dim3(1), dim3(64), 0, st, state, ramp, C, N, plateau, inc, table);
-        launch_candidates(a, ws + l.ws, l.cand, st);
+        launch_recon(a, ws + l.ws, l.cand, st);
         if (plateau)
             hipLaunchKernelGGL(ew_plateau_decide_kernel, dim3(1), dim3(64), 0, st, inc, a.worst, state);
         else
@@ -1072,7 +879,7 @@ extern "C" int emd_exitwave_search_f64(const float* images, int N, int s, int pa
         a.C = 1;
         a.E = reinterpret_cast<cplx*>(E);
         a.worst = reinterpret_cast<double*>(ws + l.worst);
-        launch_candidates(a, ws + l.ws, l.cand, st);
+        launch_recon(a, ws + l.ws, l.cand, st);
     }
     return emd::check_launch(who);
 }

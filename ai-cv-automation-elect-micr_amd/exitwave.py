@@ -192,40 +192,26 @@ def propagate(psi, defocus, wavelength, px=1.0, cs=0.0, pad_periods=0):
     return _ret(out, ndim, as_np)
 
 
-def _reconstruct(name, images, defocuses, wavelength, px, cs, iterations, pad_periods, from_intensity, want_stack, want_losses, composed):
-    """-> (E [s,s], stack [N,s,s] or None, losses [N] or None) on the device, and was_numpy."""
+def _reconstruct(name, images, defocuses, wavelength, kw, want_stack, want_losses):
+    """-> (E [s,s], stack [N,s,s] or None, losses [N] or None) on the device, and was_numpy.  ``kw``: the keywords of ``_recon_kw``."""
     import torch
 
-    shp = tuple(images.shape) if hasattr(images, "shape") else np.shape(images)
-    if len(shp) != 3 or shp[1] != shp[2]:
-        raise ValueError(f"{name}: images are [N,s,s], square (got a shape of {shp})")
-    N, s = int(shp[0]), int(shp[1])
-    if not 1 <= N <= MAX_IMAGES:
-        raise ValueError(f"{name}: 1..{MAX_IMAGES} images (got {N})")
-    _padded_side(name, s, pad_periods)
-    _positive(name, wavelength=wavelength, px=px)
-    if int(iterations) != iterations or iterations < 1:
-        raise ValueError(f"{name}: iterations must be a positive integer (got {iterations!r})")
-    if isinstance(images, torch.Tensor) and images.is_complex() or not isinstance(images, torch.Tensor) and np.iscomplexobj(images):
-        raise ValueError(f"{name}: the images are real (float32)")
+    args, composed = _recon_kw(name, kw)
+    N, s = _images(name, images, args["pad_periods"])
+    _positive(name, wavelength=wavelength)
     device = _device(images)
     d = _defocus(name, defocuses, N, device)
     x, as_np = _wave(images, device, True)
     lib = _lib.load()
-    flags = FROM_INTENSITY if from_intensity else 0
     E = torch.empty((s, s), dtype=torch.complex128, device=device)
     stack = torch.empty((N, s, s), dtype=torch.complex128, device=device) if want_stack else None
     losses = torch.empty((N,), dtype=torch.float64, device=device) if want_losses else None
-    if composed:
-        _lib.knob(COMPOSED_KNOB, 1)
-    try:   # the knob is read by the size query and by the call (host side, at launch time), and is back at its default afterwards
-        nbytes = lib.emd_exitwave_workspace_bytes(N, s, int(pad_periods))
+    with _composed_knob(composed):   # read by the size query and by the call (host side, at launch time)
+        nbytes = lib.emd_exitwave_workspace_bytes(N, s, int(args["pad_periods"]))
         ws = _ws(nbytes, device)
-        rc = lib.emd_exitwave_reconstruct_f64(_p(x), N, s, int(pad_periods), _p(d), float(wavelength), float(px), float(cs),
-                                              int(iterations), flags, _p(E), _p(stack), _p(losses), _p(ws), nbytes, _lib.stream_ptr())
-    finally:
-        if composed:
-            _lib.knob(COMPOSED_KNOB, 0)
+        rc = lib.emd_exitwave_reconstruct_f64(_p(x), N, s, int(args["pad_periods"]), _p(d), float(wavelength), float(args["px"]),
+                                              float(args["cs"]), int(args["iterations"]), FROM_INTENSITY if args["from_intensity"] else 0,
+                                              _p(E), _p(stack), _p(losses), _p(ws), nbytes, _lib.stream_ptr())
     _lib.check(rc, "emd_exitwave_reconstruct_f64")
     return (E, stack, losses), as_np
 
@@ -239,8 +225,8 @@ def reconstruct(images, defocuses, wavelength, px=1.0, cs=0.0, iterations=50, pa
     ``reconstruction_loss``).  With ``pad_periods == 0`` an iteration is two launches for the whole stack (the iteration restated in
     the frequency domain); ``_composed`` (the library's development knob ``exitwave_composed``, for measurements and tests) runs it
     through the launches of ``propagate`` instead, as ``pad_periods > 0`` does."""
-    outs, as_np = _reconstruct("reconstruct", images, defocuses, wavelength, px, cs, iterations, pad_periods, from_intensity, return_stack,
-                               return_losses, _composed)
+    kw = {"px": px, "cs": cs, "iterations": iterations, "pad_periods": pad_periods, "from_intensity": from_intensity, "_composed": _composed}
+    outs, as_np = _reconstruct("reconstruct", images, defocuses, wavelength, kw, return_stack, return_losses)
     outs = [o.cpu().numpy() if as_np else o for o in outs if o is not None]
     return outs[0] if len(outs) == 1 else tuple(outs)
 
@@ -250,15 +236,7 @@ def reconstruction_loss(images, defocuses, wavelength, per_image=False, **kw):
     ``c = mean(image_k) / mean(I)``, ``loss_k = mean((image_k - c I)^2)`` (two-pass, in double); the largest over the images, as the
     reference returns it, or all of them (``per_image``: ``[N]``).  Keywords: ``px``, ``cs``, ``iterations``, ``pad_periods``,
     ``from_intensity``, as ``reconstruct`` has them."""
-    kw = dict(kw)
-    composed = kw.pop("_composed", False)
-    args = {"px": 1.0, "cs": 0.0, "iterations": 50, "pad_periods": 0, "from_intensity": False}
-    unknown = sorted(set(kw) - set(args))
-    if unknown:
-        raise TypeError(f"reconstruction_loss: unexpected keyword(s) {unknown}; it takes {sorted(args)}")
-    args.update(kw)
-    (_, _, losses), as_np = _reconstruct("reconstruction_loss", images, defocuses, wavelength, args["px"], args["cs"], args["iterations"],
-                                         args["pad_periods"], args["from_intensity"], False, True, composed)
+    (_, _, losses), as_np = _reconstruct("reconstruction_loss", images, defocuses, wavelength, kw, False, True)
     if not per_image:
         losses = losses.max()
     return (losses.cpu().numpy() if per_image else float(losses)) if as_np else losses
