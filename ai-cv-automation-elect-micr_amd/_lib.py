@@ -607,6 +607,10 @@ DEV_SIGNATURES = {
     # op B H W Cin Cout stride rate precision flags ldx ldy out[12]
     "emd_debug_conv_plan": (C.c_int, [C.c_int] * 9 + [C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "emd_debug_split_variant": (None, [C.c_int]),
+    # M Cin Cout flags out[8]
+    "emd_debug_split32_plan": (C.c_int, [C.c_long, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_int)]),
+    # kind B H W C out[6]
+    "emd_debug_dw_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
     "emd_debug_split_stamps": (None, [C.c_void_p]),
     "emd_debug_sep_stamps": (None, [C.c_void_p]),
     "emd_debug_sepgemm_stamps": (None, [C.c_void_p]),

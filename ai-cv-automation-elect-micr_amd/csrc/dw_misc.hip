@@ -972,16 +972,31 @@ inline int grid_for(long nthreads, unsigned* blocks) {
 
 // Strip height of the rolling stride-1 depthwise kernels (dev knob dw_th forces one).
 inline int dw_strip_height(int B, int H, int W, int C4t) {
-    const int th_force = emd::g_knobs.dw_th;
+    int th_force = emd::g_knobs.dw_th;
+    if (th_force != 4 && th_force != 8 && th_force != 16 && th_force != 32) th_force = 0;   // any other value: the rule, all of it
     // (round 3: 16 rows also on the short maps while that still leaves >= 1024 workgroups -- 32 x 32 x 728 at a batch of 32: 1536
     // workgroups, 2.38 -> 2.28 ms over graph D's 43 standalone launches)
     const long wg16 = (long)B * ((H + 15) / 16) * ((W + 15) / 16) * ((C4t + 15) / 16);
-    int TH = th_force == 4 || th_force == 8 || th_force == 16 || th_force == 32 ? th_force : ((H >= 64 || (H >= 16 && wg16 >= 1024)) ? 16 : 8);
+    int TH = th_force ? th_force : ((H >= 64 || (H >= 16 && wg16 >= 1024)) ? 16 : 8);
     // small batches of small maps (4 images of 32 x 32 x 728: 384 workgroups of 8 rows): a thread's 10 dependent row loads are the
     // kernel's whole life and most CUs hold one workgroup -- 4-row strips double the workgroups and halve the chain (same bits:
     // the three row contributions of an output are added in the same order at every strip height)
     if (!th_force && TH == 8 && (long)B * ((H + 7) / 8) * ((W + 15) / 16) * ((C4t + 15) / 16) < 1024) TH = 4;
     return TH;
+}
+
+// The launch plan of the rolling stride-1 depthwise kernels: every launcher below takes its strip height and its grid from here, and
+// emd_debug_dw_plan reports it (tests/test_split_plan.py pins the table).  C4t: channel quads per pixel that have a thread.  reflect:
+// the REFLECT-border launcher has a rule of its own (no 4-row strips, no knob) and runs in launch order.
+struct DwRollPlan { int TH, xcd, nstrip, cblocks; long nblocks; };
+inline DwRollPlan dw_roll_plan(int B, int H, int W, int C4t, bool reflect) {
+    DwRollPlan q;
+    q.TH = reflect ? (H >= 64 ? 16 : 8) : dw_strip_height(B, H, W, C4t);
+    q.xcd = reflect ? 0 : dw_xcd(H, W);
+    q.nstrip = (H + q.TH - 1) / q.TH;
+    q.cblocks = (C4t + 15) / 16;
+    q.nblocks = (long)B * q.nstrip * ((W + 15) / 16) * q.cblocks;
+    return q;
 }
 
 template <bool SPLIT, bool PRE = false>
@@ -1017,20 +1032,19 @@ int dw3x3_launch(const char* who, const float* x, int ldx, const float* w, float
     if (stride == 1 && rate == 1) {
         // strip height: 16 rows (input re-read factor 18/16) measured 1-4 % faster than 8 on the 256^2/512^2 layers;
         // short images keep 8 so that small maps still spread over the chip
-        const int TH = dw_strip_height(B, H, W, C4t);
-        const int nstrip = (H + TH - 1) / TH;
-        const long nblocks = (long)B * nstrip * ((W + 15) / 16) * ((C4t + 15) / 16);
-        const long nthreads = nblocks * 256;
+        const DwRollPlan q = dw_roll_plan(B, H, W, C4t, false);
+        const int TH = q.TH, nstrip = q.nstrip;
+        const long nthreads = q.nblocks * 256;
         int rc = grid_for(nthreads, &nb);
         if (rc != EMD_OK) return rc;
         if (TH == 32)
-            hipLaunchKernelGGL((dw3x3_s1_roll<32, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, dw_xcd(H, W), pre_ld, pre_hi);
+            hipLaunchKernelGGL((dw3x3_s1_roll<32, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, q.xcd, pre_ld, pre_hi);
         else if (TH == 16)
-            hipLaunchKernelGGL((dw3x3_s1_roll<16, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, dw_xcd(H, W), pre_ld, pre_hi);
+            hipLaunchKernelGGL((dw3x3_s1_roll<16, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, q.xcd, pre_ld, pre_hi);
         else if (TH == 4)
-            hipLaunchKernelGGL((dw3x3_s1_roll<4, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, dw_xcd(H, W), pre_ld, pre_hi);
+            hipLaunchKernelGGL((dw3x3_s1_roll<4, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, q.xcd, pre_ld, pre_hi);
         else
-            hipLaunchKernelGGL((dw3x3_s1_roll<8, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, dw_xcd(H, W), pre_ld, pre_hi);
+            hipLaunchKernelGGL((dw3x3_s1_roll<8, SPLIT, false, PRE>), dim3(nb), dim3(256), 0, st, x, ldx, w, y, ldy, H, W, C4, nthreads, nstrip, C4t, pre_s, pre_t, q.xcd, pre_ld, pre_hi);
         return emd::check_launch("dw3x3_s1_roll");
     }
     const long nthreads = (long)B * ((Ho + 3) / 4) * ((Wo + 3) / 4) * ((C4t + 15) / 16) * 256;
@@ -1087,9 +1101,9 @@ int emd::launch_conv3x3_cout1_reflect_roll(const float* x, int ldx, const float*
 int emd::launch_dw3x3_reflect_roll(const float* x, int ldx, const float* w, float* y, int ldy, int B, int H, int W, int C,
                                    bool split, hipStream_t st) {
     const int C4 = C / 4, C4t = split ? (C + 31) / 32 * 8 : C4;
-    const int TH = H >= 64 ? 16 : 8;
-    const int nstrip = (H + TH - 1) / TH;
-    const long nthreads = (long)B * nstrip * ((W + 15) / 16) * ((C4t + 15) / 16) * 256;
+    const DwRollPlan q = dw_roll_plan(B, H, W, C4t, true);
+    const int TH = q.TH, nstrip = q.nstrip;
+    const long nthreads = q.nblocks * 256;
     unsigned nb;
     int rc = grid_for(nthreads, &nb);
     if (rc != EMD_OK) return rc;
@@ -1133,10 +1147,10 @@ extern "C" int emd_dw3x3_up_split32_f32(const float* lo, int ldlo, int Hi, int W
     EMD_REQUIRE((long)Wi * ldlo < (1L << 31), EMD_E_UNSUPPORTED, "emd_dw3x3_up_split32_f32: a row of lo must span fewer than 2^31 floats");
     if (B == 0) return EMD_OK;
     const int C4 = C / 4, C4t = Cp / 4;
-    const int TH = dw_strip_height(B, H, W, C4t);
-    const int nstrip = (H + TH - 1) / TH;
+    const DwRollPlan q = dw_roll_plan(B, H, W, C4t, false);
+    const int TH = q.TH, nstrip = q.nstrip;
     unsigned nb;
-    int rc = grid_for((long)B * nstrip * ((W + 15) / 16) * ((C4t + 15) / 16) * 256, &nb);
+    int rc = grid_for(q.nblocks * 256, &nb);
     if (rc != EMD_OK) return rc;
     const float sy = (float)Hi / (float)H, sx = (float)Wi / (float)W;   // as emd_resize_bilinear_f32
     // the row schedule: fixed at compile time for the exact factor 4 (graph D's, the one measured; sy = 1/4: y0 = row / 4 exactly),
@@ -1144,7 +1158,7 @@ extern "C" int emd_dw3x3_up_split32_f32(const float* lo, int ldlo, int Hi, int W
     const int F = H == 4 * Hi ? 4 : 0;
 #define EMD_DW_UP(THV, FV)                                                                                                                 \
     hipLaunchKernelGGL((dw3x3_s1_roll_up<THV, FV>), dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), lo, ldlo, Hi, Wi, Cup / 4, sy, \
-                       sx, x, ldx, w, static_cast<float*>(y), ldy, H, W, C4, nstrip, C4t, dw_xcd(H, W))
+                       sx, x, ldx, w, static_cast<float*>(y), ldy, H, W, C4, nstrip, C4t, q.xcd)
 #define EMD_DW_UP_F(THV)                                                                        \
     do {                                                                                        \
         if (F == 4) EMD_DW_UP(THV, 4); else EMD_DW_UP(THV, 0);                                  \
@@ -1176,6 +1190,19 @@ extern "C" int emd_dw3x3_pre_split32_f32(const float* x, int ldx, const float* p
                                          void* y, int ldy, int B, int H, int W, int C, int stride, int rate, emd_stream_t stream) {
     return dw3x3_launch<true, true>("emd_dw3x3_pre_split32_f32", x, ldx, w, static_cast<float*>(y), ldy, B, H, W, C, stride, rate,
                                     stream, pre_scale, pre_shift);
+}
+
+// Host only: the plan of the stride-1, rate-1 launch of a depthwise entry under the knobs as they stand.  kind: 0 emd_dw3x3_f32,
+// 1 _split32, 2 _pre / _pre_act, 3 _pre_split32, 4 emd_dw3x3_reflect_f32, 5 emd_dw3x3_reflect_split32_f32, 6 emd_dw3x3_up_split32_f32.
+extern "C" int emd_debug_dw_plan(int kind, int B, int H, int W, int C, int out[6]) {
+    if (!out || kind < 0 || kind > 6 || B < 1 || H < 1 || W < 1 || C < 4 || C % 4) return 0;
+    const bool split = kind == 1 || kind == 3 || kind == 5 || kind == 6;
+    const int C4t = split ? (C + 31) / 32 * 8 : C / 4;
+    const DwRollPlan q = dw_roll_plan(B, H, W, C4t, kind == 4 || kind == 5);
+    if (q.nblocks > 0x7fffffffL) return 0;   // grid_for refuses
+    const int r[6] = {q.TH, q.xcd, (int)q.nblocks, q.nstrip, q.cblocks, C4t};
+    for (int i = 0; i < 6; ++i) out[i] = r[i];
+    return q.TH;
 }
 
 extern "C" int emd_cin1_f32(const float* x, const float* w9, const float* a, const float* shift, float* y, int ldy,

@@ -1256,6 +1256,62 @@ extern "C" int emd_conv1x1_split32_supported(long M, int Cin, int Cout) {
     return (Cin >= 512 || (Cin >= 256 && Cout >= 256)) ? 1 : 0;
 }
 
+// The launch rule: which kernel instance a pointwise GEMM of M rows gets, on which tiles.  conv1x1_split32_impl launches what this
+// says and emd_debug_split32_plan reports it (tests/test_split_plan.py pins the table).  One id per instance the launcher can start.
+enum SplitKernel {
+    SK_NONE = 0, SK_S3_PLAIN, SK_S2, SK_PERSIST, SK_128_S2, SK_WIDE4W, SK_WIDE8W, SK_16_128x64_LEAD2, SK_16_128_LEAD2, SK_16_256_LEAD2,
+    SK_16_128x64, SK_16_128, SK_16_256, SK_WREG, SK_DIRECT, SK_S3_PIPE
+};
+struct SplitPlan { int kernel, bm, bn, threads, n_mtiles, n_ntiles, wide, lead; long nblk; };
+
+// persist_ok: the weight planes lie as the persistent form (variant 4) addresses them, wlo less than 2^31 bytes behind whi
+static SplitPlan split32_plan(long M, int Cin, int Cout, bool out_split, bool stats, long lda_bytes, bool persist_ok) {
+    // kernel variant: 3 = 256-row tiles, 3 stages, pipelined K loop, 32x32x16 MFMAs; 5 = the same on 16x16x32 MFMAs;
+    // dev knobs for A/B runs: emd_debug_knob("split_variant") / emd_debug_split_variant = 0 (256 rows, 2 stages), 1 (256, 3, plain loop),
+    // 2 (128 rows, 2 stages, two workgroups per CU), 4 (persistent, epilogue stores inside the next tile's K loop),
+    // 6 (variant 3 with the W tile through registers instead of LDS-DMA: WREG), 7 (variant 3 with the epilogue straight from
+    // the registers: DIRECT)
+    int v = emd::g_knobs.split_variant;
+    if (g_variant_override >= 0) v = g_variant_override;
+    if ((stats || out_split) && v >= 0 && v != 3 && v != 5 && v != 6 && !(out_split && v == 7)) v = 3;   // the statistics epilogue and
+                                                // the split32 output live in the two default kernels (and the WREG / DIRECT dev forms)
+    // default (round 3): variant 5, the 16x16x32-MFMA kernel -- same cycles per K step, but the chip holds 1.86 instead of 1.73 GHz
+    // under it (97.9 vs 103.7 us on 32768 x 728 x 728; MI355X_MICROARCH.md, DVFS give-back 7).  It sums a K step in another order
+    // than the 32x32x16 kernels (2e-7 relative: the contract is the oracle at 1e-3, not identity with a sibling kernel); batch
+    // independence is kept by using it at EVERY M of the layers it serves (128-row tiles below 192 tiles of 256 rows).
+    if (v < 0) v = 5;
+    const bool small = v == 5 && !stats && ((M + 255) / 256) * ((Cout + SBN - 1) / SBN) < 192;   // (statistics partials: one per 256 rows)
+    // ... and 64-column tiles (two workgroups per CU) where even the 128-row tiles leave CUs idle: a batch of 4 at 512^2 is M = 4096,
+    // 192 tiles of 128 x 128 on 256 CUs, 384 of 128 x 64.  All forms give the same bits (same products, same K order).
+    const bool narrow = small && !out_split && ((M + 127) / 128) * ((Cout + SBN - 1) / SBN) < 256 && emd::g_knobs.split_narrow;
+    // ... and 256 x 192 tiles (gemm_split16_wide_kernel) where they fill the chip and stay inside the padded weight planes (N = 728, 384, 192, ...)
+    const int n192 = (Cout + 191) / 192;
+    const int wide = (v == 5 && !stats && !out_split && n192 * 192 <= (Cout + SBN - 1) / SBN * SBN && ((M + 255) / 256) * n192 >= 256)
+                         ? emd::g_knobs.split_wide : 0;
+    SplitPlan q{};
+    q.bm = (v == 2 || small) ? 128 : 256;
+    q.bn = wide ? 192 : (narrow ? 64 : SBN);
+    q.n_mtiles = (int)((M + q.bm - 1) / q.bm);
+    q.n_ntiles = (Cout + q.bn - 1) / q.bn;
+    q.nblk = (long)q.n_mtiles * q.n_ntiles;
+    q.wide = wide;
+    const bool lead2 = emd::g_knobs.split_lead == 2;
+    if (v == 1) q.kernel = SK_S3_PLAIN;
+    else if (v == 0) q.kernel = SK_S2;
+    else if (v == 4 && Cin >= 64 && M % 256 == 0 && persist_ok && (long)256 * lda_bytes < 0x7fffffffL) q.kernel = SK_PERSIST;
+    else if (v == 2) q.kernel = SK_128_S2;
+    else if (wide == 2) q.kernel = SK_WIDE4W;
+    else if (wide) q.kernel = SK_WIDE8W;
+    else if (v == 5 && lead2) q.kernel = narrow ? SK_16_128x64_LEAD2 : (small ? SK_16_128_LEAD2 : SK_16_256_LEAD2);
+    else if (v == 5) q.kernel = narrow ? SK_16_128x64 : (small ? SK_16_128 : SK_16_256);
+    else if (v == 6) q.kernel = SK_WREG;
+    else if (v == 7) q.kernel = SK_DIRECT;
+    else q.kernel = SK_S3_PIPE;
+    q.threads = (q.kernel == SK_128_S2 || q.kernel == SK_WIDE4W || (v == 5 && !wide && small)) ? 256 : 512;
+    q.lead = (v == 5 && !wide) ? (lead2 ? 2 : 1) : 0;
+    return q;
+}
+
 static int conv1x1_split32_impl(const void* xs, int ldx, const uint16_t* whi, const uint16_t* wlo,
                                 const float* scale1, const float* shift1, const float* scale2,
                                 const float* shift2, const float* res, int ldres, float* y, int ldy, long M,
@@ -1280,60 +1336,37 @@ static int conv1x1_split32_impl(const void* xs, int ldx, const uint16_t* whi, co
     p.M = M; p.lda_bytes = (long)ldx * 4; p.N = Cout; p.Cin = Cin; p.Ktot = (Cin + kBK - 1) / kBK * kBK;
     p.ldc = ldy; p.ldres = ldres; p.act = act; p.stats_part = stats_part; p.out_split = out_split ? 1 : 0;
     p.nt = split_nt(2);
-    // kernel variant: 3 = 256-row tiles, 3 stages, pipelined K loop, 32x32x16 MFMAs; 5 = the same on 16x16x32 MFMAs;
-    // dev knobs for A/B runs: emd_debug_knob("split_variant") / emd_debug_split_variant = 0 (256 rows, 2 stages), 1 (256, 3, plain loop),
-    // 2 (128 rows, 2 stages, two workgroups per CU), 4 (persistent, epilogue stores inside the next tile's K loop),
-    // 6 (variant 3 with the W tile through registers instead of LDS-DMA: WREG), 7 (variant 3 with the epilogue straight from
-    // the registers: DIRECT)
-    int v = emd::g_knobs.split_variant;
-    if (g_variant_override >= 0) v = g_variant_override;
-    if ((stats_part || out_split) && v >= 0 && v != 3 && v != 5 && v != 6 && !(out_split && v == 7)) v = 3;   // the statistics epilogue and
-                                                // the split32 output live in the two default kernels (and the WREG / DIRECT dev forms)
-    // default (round 3): variant 5, the 16x16x32-MFMA kernel -- same cycles per K step, but the chip holds 1.86 instead of 1.73 GHz
-    // under it (97.9 vs 103.7 us on 32768 x 728 x 728; MI355X_MICROARCH.md, DVFS give-back 7).  It sums a K step in another order
-    // than the 32x32x16 kernels (2e-7 relative: the contract is the oracle at 1e-3, not identity with a sibling kernel); batch
-    // independence is kept by using it at EVERY M of the layers it serves (128-row tiles below 192 tiles of 256 rows).
-    if (v < 0) v = 5;
     p.stamps = g_stamps;
-    const bool small = v == 5 && !stats_part && ((M + 255) / 256) * ((Cout + SBN - 1) / SBN) < 192;   // (statistics partials: one per 256 rows)
-    // ... and 64-column tiles (two workgroups per CU) where even the 128-row tiles leave CUs idle: a batch of 4 at 512^2 is M = 4096,
-    // 192 tiles of 128 x 128 on 256 CUs, 384 of 128 x 64.  All forms give the same bits (same products, same K order).
-    const bool narrow = small && !out_split && ((M + 127) / 128) * ((Cout + SBN - 1) / SBN) < 256 && emd::g_knobs.split_narrow;
-    // ... and 256 x 192 tiles (gemm_split16_wide_kernel) where they fill the chip and stay inside the padded weight planes (N = 728, 384, 192, ...)
-    const int n192 = (Cout + 191) / 192;
-    const int wide = (v == 5 && !stats_part && !out_split && n192 * 192 <= (Cout + SBN - 1) / SBN * SBN && ((M + 255) / 256) * n192 >= 256)
-                         ? emd::g_knobs.split_wide : 0;
-    const int bm = (v == 2 || small) ? 128 : 256, bn = wide ? 192 : (narrow ? 64 : SBN);
-    p.n_mtiles = (int)((M + bm - 1) / bm);
-    p.n_ntiles = (Cout + bn - 1) / bn;
-    const long nblk = (long)p.n_mtiles * p.n_ntiles;
+    const bool persist_ok = wlo > whi && (reinterpret_cast<uintptr_t>(wlo) - reinterpret_cast<uintptr_t>(whi)) < 0x7fffffffu;
+    const SplitPlan q = split32_plan(M, Cin, Cout, out_split != 0, stats_part != nullptr, p.lda_bytes, persist_ok);
+    p.n_mtiles = q.n_mtiles;
+    p.n_ntiles = q.n_ntiles;
+    const long nblk = q.nblk;
     if (nblk > 0x7fffffffL) return emd::fail(EMD_E_UNSUPPORTED, "emd_conv1x1_split32_f32: grid too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (v == 1) hipLaunchKernelGGL((gemm_split_kernel<256, 3>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-    else if (v == 0) hipLaunchKernelGGL((gemm_split_kernel<256, 2>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-    else if (v == 4 && Cin >= 64 && M % 256 == 0 && wlo > whi &&
-             (reinterpret_cast<uintptr_t>(wlo) - reinterpret_cast<uintptr_t>(whi)) < 0x7fffffffu && (long)256 * p.lda_bytes < 0x7fffffffL) {
+    const dim3 grid((unsigned)nblk), block(q.threads);
+    switch (q.kernel) {
+    case SK_S3_PLAIN: hipLaunchKernelGGL((gemm_split_kernel<256, 3>), grid, block, 0, st, p); break;
+    case SK_S2: hipLaunchKernelGGL((gemm_split_kernel<256, 2>), grid, block, 0, st, p); break;
+    case SK_PERSIST: {
         p.wlo_delta = (unsigned)(reinterpret_cast<uintptr_t>(wlo) - reinterpret_cast<uintptr_t>(whi));
-        int ncu = 256;
         static const int cus = [] { int d = 0, n = 0; if (hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) return n; return 256; }();
-        ncu = cus;
-        const unsigned grid = (unsigned)(nblk < ncu ? nblk : ncu);
-        hipLaunchKernelGGL(gemm_split_persist_kernel, dim3(grid), dim3(512), 0, st, p);
+        hipLaunchKernelGGL(gemm_split_persist_kernel, dim3((unsigned)(nblk < cus ? nblk : cus)), block, 0, st, p);
+        break;
     }
-    else if (v == 2) hipLaunchKernelGGL((gemm_split_kernel<128, 2>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (wide == 2) hipLaunchKernelGGL((gemm_split16_wide_kernel<2>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (wide) hipLaunchKernelGGL((gemm_split16_wide_kernel<4>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-    else if (v == 5 && emd::g_knobs.split_lead == 2) {
-        if (narrow) hipLaunchKernelGGL((gemm_split16_kernel<128, 64, true>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-        else if (small) hipLaunchKernelGGL((gemm_split16_kernel<128, SBN, true>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((gemm_split16_kernel<256, SBN, true>), dim3((unsigned)nblk), dim3(512), 0, st, p);
+    case SK_128_S2: hipLaunchKernelGGL((gemm_split_kernel<128, 2>), grid, block, 0, st, p); break;
+    case SK_WIDE4W: hipLaunchKernelGGL((gemm_split16_wide_kernel<2>), grid, block, 0, st, p); break;
+    case SK_WIDE8W: hipLaunchKernelGGL((gemm_split16_wide_kernel<4>), grid, block, 0, st, p); break;
+    case SK_16_128x64_LEAD2: hipLaunchKernelGGL((gemm_split16_kernel<128, 64, true>), grid, block, 0, st, p); break;
+    case SK_16_128_LEAD2: hipLaunchKernelGGL((gemm_split16_kernel<128, SBN, true>), grid, block, 0, st, p); break;
+    case SK_16_256_LEAD2: hipLaunchKernelGGL((gemm_split16_kernel<256, SBN, true>), grid, block, 0, st, p); break;
+    case SK_16_128x64: hipLaunchKernelGGL((gemm_split16_kernel<128, 64>), grid, block, 0, st, p); break;
+    case SK_16_128: hipLaunchKernelGGL(gemm_split16_kernel<128>, grid, block, 0, st, p); break;
+    case SK_16_256: hipLaunchKernelGGL(gemm_split16_kernel<256>, grid, block, 0, st, p); break;
+    case SK_WREG: hipLaunchKernelGGL((gemm_split_kernel<256, 3, true, true>), grid, block, 0, st, p); break;
+    case SK_DIRECT: hipLaunchKernelGGL((gemm_split_kernel<256, 3, true, false, true>), grid, block, 0, st, p); break;
+    default: hipLaunchKernelGGL((gemm_split_kernel<256, 3, true>), grid, block, 0, st, p); break;
     }
-    else if (v == 5 && narrow) hipLaunchKernelGGL((gemm_split16_kernel<128, 64>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (v == 5 && small) hipLaunchKernelGGL(gemm_split16_kernel<128>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (v == 5) hipLaunchKernelGGL(gemm_split16_kernel<256>, dim3((unsigned)nblk), dim3(512), 0, st, p);
-    else if (v == 6) hipLaunchKernelGGL((gemm_split_kernel<256, 3, true, true>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-    else if (v == 7) hipLaunchKernelGGL((gemm_split_kernel<256, 3, true, false, true>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((gemm_split_kernel<256, 3, true>), dim3((unsigned)nblk), dim3(512), 0, st, p);
     return emd::check_launch("gemm_split_kernel");
 }
 
@@ -1393,4 +1426,15 @@ extern "C" int emd_conv1x1_split32_stats_fold_f32(const void* xs, int ldx, const
 
 // dev hooks (not in the header): kernel variant and stamp buffer for tools/gemm_split_bench.py
 extern "C" void emd_debug_split_variant(int v) { g_variant_override = v; }
+// Host only: what conv1x1_split32_impl would launch for this shape under the knobs and the forced variant as they stand (weight planes
+// laid out as emd_pack_weights_bf16 leaves them, a dense input).  flags: bit 0 split32 output, bit 1 statistics.
+extern "C" int emd_debug_split32_plan(long M, int Cin, int Cout, unsigned flags, int out[8]) {
+    const bool out_split = flags & 1u, stats = flags & 2u;
+    if (!out || M < 1 || Cin < 1 || Cout < 4 || Cout % 4 || (out_split && stats) || (flags & ~3u)) return 0;
+    const SplitPlan q = split32_plan(M, Cin, Cout, out_split, stats, (long)emd_split32_ld(Cin) * 4, true);
+    if (q.nblk > 0x7fffffffL) return 0;
+    const int r[8] = {q.kernel, q.bm, q.bn, q.threads, q.n_mtiles, q.n_ntiles, q.wide, q.lead};
+    for (int i = 0; i < 8; ++i) out[i] = r[i];
+    return q.kernel;
+}
 extern "C" void emd_debug_split_stamps(void* buf) { g_stamps = static_cast<long long*>(buf); }

@@ -32,7 +32,7 @@
  *                       from the accumulators; 2 = the same on 128-row tiles, two workgroups per CU; 0 = LDS-staged epilogue
  *   nt_mask (7)         non-temporal output stores: bit 0 split32 convolutions, bit 1 sep_fused, bit 2 pointwise split32 GEMM
  *   dw_xcd (1)          depthwise kernels: 0 = launch-order tiles, 1 = XCD-contiguous up to 128 x 128 maps, 2 = always
- *   dw_th (0)           strip height of the rolling depthwise kernel (0 = rule)
+ *   dw_th (0)           strip height of the rolling depthwise kernel: 4, 8, 16 or 32 (anything else = rule)
  *   split_narrow (1)    pointwise split32 GEMM: 128 x 64 tiles for the small batches whose 128 x 128 tiles leave CUs idle (0 = never)
  *   conv3_pipe (1)      dense 3x3 conv, stride 1, rate 1, H % 8 == 0, W % 32 == 0, <= 256 output channels (2: any width): the patch-resident kernel
  *                       (conv3_pipe.hip; sums chunk-major, taps inside: last-bit differences to the tap-major GEMM), 0 = gemm_split_conv_kernel
@@ -88,6 +88,27 @@ int emd_debug_conv_plan(int op, int B, int H, int W, int Cin, int Cout, int stri
                         int ldy, int out[12]);
 /* Force the pipeline variant of emd_conv1x1_split32_f32 (csrc/gemm_split.hip); -1 restores the dispatch rule. */
 void emd_debug_split_variant(int v);
+/* Host only, reads the knobs and the forced variant, touches no device: what the pointwise split32 GEMM (csrc/gemm_split.hip,
+ * emd_conv1x1_split32[_out|_stats|_stats_fold]_f32) launches for M rows -- the function the launcher itself calls (tests/test_split_plan.py
+ * pins it).  flags: bit 0 split32 output, bit 1 statistics.  The rule with default knobs, nt = ceil(Cout / 128): 256 x 128 tiles where
+ * ceil(M / 256) * nt >= 192 or statistics are asked for; else 128 x 128 where ceil(M / 128) * nt >= 256 or the output is split32; else
+ * 128 x 64 (split_narrow).  Returns the kernel id, 0 where nothing would be launched (M < 1, a shape the entry refuses, a grid too
+ * large; out is then left alone): 1 gemm_split_kernel<256, 3> (variant 1), 2 <256, 2> (0), 3 gemm_split_persist_kernel (4; weight planes
+ * as emd_pack_weights_bf16 lays them, a dense input), 4 <128, 2> (2), 5 gemm_split16_wide_kernel<2> (split_wide 2), 6 <4> (split_wide 1),
+ * 7 / 8 / 9 gemm_split16_kernel<128, 64, true> / <128, 128, true> / <256, 128, true> (the default: split_lead 2), 10 / 11 / 12 the same
+ * three one step ahead (split_lead 1), 13 gemm_split_kernel<256, 3, true, true> (6), 14 <256, 3, true, false, true> (7),
+ * 15 <256, 3, true> (3).  out = {kernel, tile rows, tile columns, threads per workgroup, row tiles, column tiles, split_wide form in use
+ * (0: none), K steps ahead (2 or 1 on kernels 7-12, else 0)}; the grid is row tiles x column tiles (kernel 3: at most one per CU). */
+int emd_debug_split32_plan(long M, int Cin, int Cout, unsigned flags, int out[8]);
+/* Host only, reads the knobs, touches no device: the plan of the rolling stride-1, rate-1 depthwise launch (csrc/dw_misc.hip,
+ * dw3x3_s1_roll / dw3x3_s1_roll_up) -- the function the launchers themselves call.  kind: 0 emd_dw3x3_f32, 1 emd_dw3x3_split32_f32,
+ * 2 emd_dw3x3_pre[_act]_f32, 3 emd_dw3x3_pre_split32_f32, 4 emd_dw3x3_reflect_f32, 5 emd_dw3x3_reflect_split32_f32,
+ * 6 emd_dw3x3_up_split32_f32.  With wg(t) = B * ceil(H / t) * ceil(W / 16) * ceil(Q / 16) workgroups of t rows, Q = channel quads with a
+ * thread (C / 4; ceil32(C) / 4 for a split32 output, whose padding is written too): 16 rows where H >= 64, or H >= 16 and
+ * wg(16) >= 1024; else 8, and 4 where wg(8) < 1024; dw_th forces 4, 8, 16 or 32.  REFLECT: 16 where H >= 64, else 8; no knob, launch
+ * order.  Returns the strip height, 0 where nothing would be launched (out is then left alone).  out = {strip height, XCD-contiguous
+ * tile order (1 / 0), workgroups, strips per image, channel blocks per pixel, Q}. */
+int emd_debug_dw_plan(int kind, int B, int H, int W, int C, int out[6]);
 /* Device buffer that the split32 GEMM writes s_memtime phase stamps into (NULL = off). */
 void emd_debug_split_stamps(void* device_buf);
 /* Device buffer that the fused separable conv writes s_memtime phase stamps into (NULL = off). */

@@ -178,13 +178,18 @@ def test_conv1x1_split32_full_size_identity():
     pw = ops.PackedWeights(w, False, dev())
     s, t = torch.ones(728, device=dev()), torch.zeros(728, device=dev())
     from emdenoise import _lib
+    from tests.test_split_plan import big, gemm_plan, narrow
 
+    # the forms d, d4, d8 and d1 run (32 * 6 = 192 tiles of 256 rows: 8 images are not below the threshold; the 128 x 128 form between
+    # 4 and 8 images is tests/test_split_forms_gpu.py's)
+    plans = [gemm_plan(_lib.load(), n * 1024, 728, 728) for n in (32, 4, 8, 1)]
+    assert plans == [big(128, 6), narrow(32, 12), big(32, 6), narrow(8, 12)]
     xa = ops.Act(x)
     xs = ops.to_split32(xa)
     b = ops.conv1x1(xa, pw, s, t, ops.Act.empty(32, 32, 32, 728, dev()))
     d = ops.conv1x1_split32(xs, pw, s, t, ops.Act.empty(32, 32, 32, 728, dev()))     # the default kernel: 16x16x32 MFMAs, 256-row tiles
     d4 = ops.conv1x1_split32(ops.to_split32(ops.Act(x[8:12].contiguous())), pw, s, t, ops.Act.empty(4, 32, 32, 728, dev()))   # 128 x 64 tiles
-    d8 = ops.conv1x1_split32(ops.to_split32(ops.Act(x[16:24].contiguous())), pw, s, t, ops.Act.empty(8, 32, 32, 728, dev()))  # 128 x 128 tiles
+    d8 = ops.conv1x1_split32(ops.to_split32(ops.Act(x[16:24].contiguous())), pw, s, t, ops.Act.empty(8, 32, 32, 728, dev()))  # 256 x 128 tiles
     d1 = ops.conv1x1_split32(ops.to_split32(ops.Act(x[31:32].contiguous())), pw, s, t, ops.Act.empty(1, 32, 32, 728, dev()))
     try:
         _lib.load().emd_debug_split_variant(3)                                        # the 32x32x16 form
@@ -201,7 +206,9 @@ def test_conv1x1_split32_full_size_identity():
     (16, 32, 32, 728, 728, True, False),     # 64 x 4 tiles of 256 x 192: the smallest grid that takes the wide form; residual
     (33, 23, 23, 728, 728, False, True),     # M = 17457: a ragged last row tile; second affine
     (32, 32, 32, 256, 384, True, True),      # two column tiles, K = 8 steps
-    (20, 32, 32, 96, 192, False, False),     # one column tile, K = 3 steps (fewer than the A ring has stages)
+    (20, 32, 32, 96, 192, False, False),     # K = 3 steps (fewer than the A ring has stages); 80 row tiles x one column tile < 256: the knob
+                                             # selects nothing, both sides run 128 x 128 tiles (the wide form with one column tile:
+                                             # tests/test_split_forms_gpu.py)
 ])
 @pytest.mark.parametrize("form", [1, 2])
 def test_conv1x1_split32_wide_tiles(B, H, W, ci, co, res, extra, form):
@@ -218,10 +225,19 @@ def test_conv1x1_split32_wide_tiles(B, H, W, ci, co, res, extra, form):
     s2, t2 = up(rnd((co,), 76, 0.2) + 1.0), up(rnd((co,), 77, 0.3))
     kw = dict(scale2=s2 if extra else None, shift2=t2 if extra else None, res=ops.Act(up(r)) if res else None)
     xs = ops.to_split32(ops.Act(up(x)))
+    from tests.test_split_plan import WIDE4W, WIDE8W, gemm_plan, small
+
+    M, takes = B * H * W, B != 20
     try:
         _lib.knob("split_wide", 0)
+        assert gemm_plan(_lib.load(), M, ci, co)[1:3] == ((128, 128) if not takes else (256, 128))
         ref = ops.conv1x1_split32(xs, pw, s1, t1, ops.Act.empty(B, H, W, co, dev()), **kw)
         _lib.knob("split_wide", form)
+        if takes:
+            kernel, threads = ((WIDE8W, 512), (WIDE4W, 256))[form - 1]
+            assert gemm_plan(_lib.load(), M, ci, co) == (kernel, 256, 192, threads, -(-M // 256), -(-co // 192), form, 0)
+        else:
+            assert gemm_plan(_lib.load(), M, ci, co) == small(160, 2)
         wide = torch.full((B, H, W, co + 8), float("nan"), dtype=torch.float32, device=dev())
         got = ops.conv1x1_split32(xs, pw, s1, t1, ops.Act(wide, co, 4), **kw)
         torch.cuda.synchronize()
@@ -234,9 +250,10 @@ def test_conv1x1_split32_wide_tiles(B, H, W, ci, co, res, extra, form):
 @pytest.mark.parametrize("B,H,W,ci,co,res", [
     (16, 32, 32, 728, 728, True),      # 256 x 128 tiles, 23 K steps, residual
     (4, 32, 32, 728, 728, False),      # 128 x 64 tiles (the small-batch form)
-    (2, 32, 32, 96, 192, False),       # 128 x 128 tiles, K = 3 steps: as many as the ring has stages
+    (2, 32, 32, 96, 192, False),       # 128 x 64 tiles (16 * 2 = 32 row tiles of 128 x 128 < 256), K = 3 steps: as many as the ring has stages
     (1, 16, 16, 32, 64, True),         # one K step: every younger DMA group is a surplus re-read of it
     (3, 23, 23, 64, 40, False),        # two K steps, ragged M, channel tail
+    (20, 32, 32, 96, 192, False),      # 128 x 128 tiles (80 * 2 = 160 row tiles of 256 rows < 192, 160 * 2 = 320 of 128 rows >= 256)
 ])
 def test_conv1x1_split32_two_steps_ahead(B, H, W, ci, co, res):
     """gemm_split16_kernel with the DMA of tile kt + 3 issued in step kt into the stage of tile kt (dev knob split_lead = 2, the default)
@@ -250,10 +267,15 @@ def test_conv1x1_split32_two_steps_ahead(B, H, W, ci, co, res):
     s1, t1 = up(rnd((co,), 84, 0.3) + 1.0), up(rnd((co,), 85, 0.5))
     kw = dict(res=ops.Act(up(r)) if res else None)
     xs = ops.to_split32(ops.Act(up(x)))
+    from tests.test_split_plan import N64, N64_L2, N128, N128_L2, N256, N256_L2, gemm_plan
+
+    one, two, form = {16: (N256, N256_L2, (256, 128)), 20: (N128, N128_L2, (128, 128))}.get(B, (N64, N64_L2, (128, 64)))
     try:
         _lib.knob("split_lead", 1)
+        assert gemm_plan(_lib.load(), B * H * W, ci, co)[:3] == (one,) + form
         ref = ops.conv1x1_split32(xs, pw, s1, t1, ops.Act.empty(B, H, W, co, dev()), **kw)
         _lib.knob("split_lead", 2)
+        assert gemm_plan(_lib.load(), B * H * W, ci, co)[:3] == (two,) + form
         wide = torch.full((B, H, W, co + 8), float("nan"), dtype=torch.float32, device=dev())
         got = ops.conv1x1_split32(xs, pw, s1, t1, ops.Act(wide, co, 4), **kw)
         torch.cuda.synchronize()
