@@ -539,6 +539,20 @@ SIGNATURES = {
     "emd_exitwave_search_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # images N S0 centres_table C side pad_val out stream
+    "emd_crop_candidates_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "emd_exitwave_candidate_stacks_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # as emd_exitwave_candidates_f64, images [C][N][s][s]
+    "emd_exitwave_candidate_stacks_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                                    C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    # C N side pad_periods
+    "emd_exitwave_refine_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    # images N S0 side pad_periods pad_val centres0 defocus0 steps0 anchor C rounds wavelength px cs iterations flags result_centres
+    # result_defocus result status history_losses history_choice history_steps E workspace ws_bytes stream
+    "emd_exitwave_refine_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int] +
+                                [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
     # ---- the 2-D FFT of any side (csrc/fft_any.hip)
     "emd_fft_any_line": (C.c_int, [C.c_int]),
     "emd_cfft2_any_workspace_bytes": (C.c_size_t, [C.c_int] * 3),

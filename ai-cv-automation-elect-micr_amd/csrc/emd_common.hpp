@@ -37,6 +37,10 @@ int launch_dw3x3_reflect_roll(const float* x, int ldx, const float* w, float* y,
 int launch_conv3x3_cout1_reflect_roll(const float* x, int ldx, const float* w, float bias, float* y, int B, int H, int W, int Cin,
                                       hipStream_t st);
 
+// register.hip: emd_crop_candidates_f32's launch (out [C][N][side][side]), for a caller that has checked the arguments
+void launch_crop_candidates(const float* images, int N, int S, const double* centres_table, int C, int side, float pad_val, float* out,
+                            hipStream_t st);
+
 struct BnFoldArgs;   // bn_chain_dev.hpp
 struct BnPrepArgs;
 int bn_prep_args(const emd_bn_bwd_prep_t* p, BnPrepArgs* out);        // bn_train.hip: the public structs -> device argument blocks, checked

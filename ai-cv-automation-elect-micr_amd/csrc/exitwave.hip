@@ -20,10 +20,13 @@
 //   ew_modulus_cand_kernel, ew_loss_rows_cand_kernel, ew_loss_resid_cand_kernel, ew_loss_final_kernel, ew_worst_kernel   the modulus
 //                          constraint in real space, the loss's two passes and its end, the largest loss of a candidate
 //   ew_search_*, ew_section_decide_kernel, ew_plateau_decide_kernel   the defocus search's table and decisions, one workgroup each
+//   ew_refine_*            the refinement's state, poll tables and decisions, one workgroup each
 //
 // There is one reconstruction, of one stack under C defocus tables at once: the candidate is a grid dimension, the
 // image of plane b = c N + k is b mod N ("cand" in a name).  emd_exitwave_reconstruct_f64 is C = 1; its two launches
 // of an iteration take the instances without the candidate dimension (ew_recon_cols_kernel, MOD), which were measured faster.
+// Candidates that have their own images (emd_exitwave_candidate_stacks_f64, the refinement's polls) are C N images
+// to the same kernels: b mod (C N) = b, and iteration 0 reads with the candidate stride of the others.  No kernel instance is added.
 //
 // No floating-point atomics, every sum in a fixed order: bitwise reproducible.  Launches only; the defocuses are read on the device.
 #include <cmath>
@@ -414,6 +417,132 @@ __global__ __launch_bounds__(64) void ew_search_finish_kernel(const SearchState*
     status[1] = st->i[SI_STEPS];
 }
 
+// ---- the refinement of crop centres and defocuses: a compass search whose polls are the candidates ------------
+
+enum { RF_BEST = 0, RF_LOSS0 = 1, RF_STEP_XY = 2, RF_STEP_DF = 3, RF_COUNT = 4 };   // doubles of the refinement's state
+enum { RI_STATUS = 0, RI_MOVES = 1, RI_COUNT = 2 };                                  // ints behind them
+
+struct RefineState {
+    double d[RF_COUNT];
+    int i[RI_COUNT];
+};
+
+// Poll q of the compass search: parameter p = q / 2 = axis (N - 1) + j, the free images j in ascending k without the anchor; the
+// entry of the state it moves (centres [N][2] = (x, y), defocus [N]) and its value, the state's plus (q even) or minus (q odd) the
+// axis' step, one rounded operation.  The table and the decision both go through here, so the chosen candidate IS the polled one.
+__device__ __forceinline__ double refine_poll(int q, int N, int anchor, const RefineState* st, const double* centres, const double* defocus,
+                                              int& axis, int& k) {
+#pragma clang fp contract(off)
+    const int p = q >> 1, j = p % (N - 1);
+    axis = p / (N - 1);
+    k = j < anchor ? j : j + 1;
+    const double v = axis == 2 ? defocus[k] : centres[2 * k + axis];
+    const double step = st->d[axis == 2 ? RF_STEP_DF : RF_STEP_XY];
+    return (q & 1) ? v - step : v + step;
+}
+
+// grid (1): the state starts as the seed
+__global__ __launch_bounds__(64) void ew_refine_init_kernel(const double* __restrict__ centres0, const double* __restrict__ defocus0,
+                                                            const double* __restrict__ steps0, int N, RefineState* __restrict__ st,
+                                                            double* __restrict__ centres, double* __restrict__ defocus) {
+    const int t = threadIdx.x;
+    if (t < N) {
+        centres[2 * t] = centres0[2 * t];
+        centres[2 * t + 1] = centres0[2 * t + 1];
+        defocus[t] = defocus0[t];
+    }
+    if (t != 0) return;
+    st->d[RF_BEST] = st->d[RF_LOSS0] = __longlong_as_double(0x7FF0000000000000ll);
+    st->d[RF_STEP_XY] = steps0[0];
+    st->d[RF_STEP_DF] = steps0[1];
+    for (int j = 0; j < RI_COUNT; ++j) st->i[j] = 0;
+}
+
+// grid (1), n <= 64 threads in use: row c of the tables is the state with poll q0 + c applied; q0 < 0 (n = 1): the state itself.
+// steps_out (may be NULL): the steps this round polls with.
+__global__ __launch_bounds__(64) void ew_refine_table_kernel(const RefineState* __restrict__ st, const double* __restrict__ centres,
+                                                             const double* __restrict__ defocus, int N, int anchor, int q0, int n,
+                                                             double* __restrict__ centres_table, double* __restrict__ defocus_table,
+                                                             double* __restrict__ steps_out) {
+    const int c = threadIdx.x;
+    if (c == 0 && steps_out) {
+        steps_out[0] = st->d[RF_STEP_XY];
+        steps_out[1] = st->d[RF_STEP_DF];
+    }
+    if (c >= n) return;
+    double* tc = centres_table + (long)c * N * 2;
+    double* td = defocus_table + (long)c * N;
+    for (int k = 0; k < N; ++k) {
+        tc[2 * k] = centres[2 * k];
+        tc[2 * k + 1] = centres[2 * k + 1];
+        td[k] = defocus[k];
+    }
+    if (q0 < 0) return;
+    int axis, k;
+    const double v = refine_poll(q0 + c, N, anchor, st, centres, defocus, axis, k);
+    if (axis == 2)
+        td[k] = v;
+    else
+        tc[2 * k + axis] = v;
+}
+
+// grid (1), one thread: best = loss0 = the seed's worst loss; not finite: best = +inf and EMD_SEARCH_NONFINITE
+__global__ __launch_bounds__(64) void ew_refine_seed_kernel(const double* __restrict__ worst, RefineState* __restrict__ st) {
+    if (threadIdx.x != 0) return;
+    const double l = worst[0];
+    st->d[RF_LOSS0] = l;
+    if (finite_d(l))
+        st->d[RF_BEST] = l;
+    else
+        st->i[RI_STATUS] |= EMD_SEARCH_NONFINITE;
+}
+
+// grid (1), one thread: the round's decision from its Q worst losses
+__global__ __launch_bounds__(64) void ew_refine_decide_kernel(const double* __restrict__ worst, int Q, int N, int anchor,
+                                                              RefineState* __restrict__ st, double* __restrict__ centres,
+                                                              double* __restrict__ defocus, int* __restrict__ choice) {
+    if (threadIdx.x != 0) return;
+    int best = -1;
+    for (int q = 0; q < Q; ++q)
+        if (finite_d(worst[q]) && (best < 0 || worst[q] < worst[best])) best = q;
+    if (best < 0) {
+        st->i[RI_STATUS] |= EMD_SEARCH_NONFINITE;
+        choice[0] = -2;
+    } else if (worst[best] < st->d[RF_BEST]) {
+        int axis, k;
+        const double v = refine_poll(best, N, anchor, st, centres, defocus, axis, k);
+        if (axis == 2)
+            defocus[k] = v;
+        else
+            centres[2 * k + axis] = v;
+        st->d[RF_BEST] = worst[best];
+        st->i[RI_MOVES] += 1;
+        choice[0] = best;
+    } else {
+        st->d[RF_STEP_XY] = 0.5 * st->d[RF_STEP_XY];
+        st->d[RF_STEP_DF] = 0.5 * st->d[RF_STEP_DF];
+        choice[0] = -1;
+    }
+}
+
+// grid (1): the state and its numbers into the caller's arrays
+__global__ __launch_bounds__(64) void ew_refine_finish_kernel(const RefineState* __restrict__ st, const double* __restrict__ centres,
+                                                              const double* __restrict__ defocus, int N, double* __restrict__ result_centres,
+                                                              double* __restrict__ result_defocus, double* __restrict__ result,
+                                                              int* __restrict__ status) {
+    const int t = threadIdx.x;
+    if (t < N) {
+        result_centres[2 * t] = centres[2 * t];
+        result_centres[2 * t + 1] = centres[2 * t + 1];
+        result_defocus[t] = defocus[t];
+    }
+    if (t != 0) return;
+    result[0] = st->d[RF_BEST];
+    result[1] = st->d[RF_LOSS0];
+    status[0] = st->i[RI_STATUS];
+    status[1] = st->i[RI_MOVES];
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 // The entry points' arguments go through emd::check_ranges behind their shape checks.  No range is marked as an input: every overlap
@@ -571,6 +700,7 @@ struct ReconArgs {
     int iterations, fi;
     cplx *E, *stack;       // [C][s][s], [C][N][s][s]
     double *losses, *worst;   // [C][N], [C]; any of the four outputs may be NULL (the composed path needs E, or the layout's spare wave)
+    int stacks;               // 0: images [N][s][s], one stack under every candidate; 1: [C][N][s][s], candidate c has its own (3.30)
 };
 
 // The iterations of the composed reconstruction of one candidate (pad_periods > 0, or the development knob), every one through the
@@ -604,16 +734,19 @@ void launch_fused(const ReconArgs& a, char* ws, const ReconLayout& l, hipStream_
     cplx* Bf = reinterpret_cast<cplx*>(ws + l.Bf);
     cplx* Eh = a.E ? reinterpret_cast<cplx*>(ws + l.Eh) : nullptr;
     // the rows of the images, transformed once into candidate 0's planes: psi_k starts as the image under every candidate, so
-    // iteration 0 reads them with candidate stride 0; the first row pass then fills every candidate's planes, these included
-    launch_pass<OP_FWD>(pass_args(a.images, a.fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), N, st);
+    // iteration 0 reads them with candidate stride 0; the first row pass then fills every candidate's planes, these included.
+    // Candidate stacks: all C N images are transformed, iteration 0 reads with the candidate stride of every other iteration, and
+    // the modulus takes image b mod (C N) = b
+    const int nimg = a.stacks ? C * N : N;
+    launch_pass<OP_FWD>(pass_args(a.images, a.fi ? 2 : 1, ss, S, S, A, ss, 1, S, S, S, S, tw), nimg, st);
     for (int it = 0; it < a.iterations; ++it) {
         const bool last = it == a.iterations - 1;
-        launch_recon_cols(A, it == 0 ? 0 : (long)N * ss, Bf, last ? Eh : nullptr, C, N, S, tw, a.table, a.o, st);
+        launch_recon_cols(A, it == 0 && !a.stacks ? 0 : (long)N * ss, Bf, last ? Eh : nullptr, C, N, S, tw, a.table, a.o, st);
         if (!last) {
             PassArgs m = pass_args(Bf, 0, ss, S, S, A, ss, 1, S, S, S, S, tw);
             m.amp = a.images;
             m.from_intensity = a.fi;
-            m.nimg = N;
+            m.nimg = nimg;
             if (C == 1)   // b mod N == b: the instance without the division, 0.4 us a launch faster (profiles/exitwave_unify.txt)
                 launch_pass<OP_MOD>(m, N, st);
             else
@@ -627,10 +760,12 @@ void launch_fused(const ReconArgs& a, char* ws, const ReconLayout& l, hipStream_
 // The one reconstruction path of emd_exitwave_reconstruct_f64 (C = 1, the defocuses as a table of one row),
 // emd_exitwave_candidates_f64 and emd_exitwave_search_f64.  Fused: every candidate in the same launches.  Composed: the candidates
 // one after the other, with no host work between them.  Then, from b_k of the last iteration, the outputs that are asked for: the
-// stack (1 launch), the losses (3) and the worst loss (1).
+// stack (1 launch), the losses (3) and the worst loss (1).  Candidate stacks: the kernels that take image b mod N get C N images
+// on the fused path, and candidate c's own N images on the composed one.
 void launch_recon(const ReconArgs& a, char* ws, const ReconLayout& l, hipStream_t st) {
     const int C = a.C, N = a.N, s = a.s;
     const long ss = (long)s * s;
+    const int nimg = a.stacks && l.fused ? C * N : N;
     const unsigned tiles = (unsigned)emd::tiles_of((int)ss, 256);
     const cplx* bwave = reinterpret_cast<const cplx*>(ws + (l.fused ? l.A : l.Bf));   // b_k of the last iteration, [step][N][s][s]
     double* part = reinterpret_cast<double*>(ws + l.part);
@@ -639,15 +774,18 @@ void launch_recon(const ReconArgs& a, char* ws, const ReconLayout& l, hipStream_
     const int step = l.fused ? C : 1;   // candidates per pass of this loop
     for (int c = 0; c < C; c += step) {
         const unsigned B = (unsigned)(step * N);
+        ReconArgs ac = a;   // composed, candidate stacks: this candidate's images
+        if (a.stacks && !l.fused) ac.images = a.images + (long)c * N * ss;
+        const float* img = ac.images;
         if (l.fused)
             launch_fused(a, ws, l, st);
         else
-            launch_composed(a, a.table + (size_t)c * N, a.E ? a.E + c * ss : reinterpret_cast<cplx*>(ws + l.Ew), ws, l, st);
+            launch_composed(ac, a.table + (size_t)c * N, a.E ? a.E + c * ss : reinterpret_cast<cplx*>(ws + l.Ew), ws, l, st);
         if (a.stack)
-            hipLaunchKernelGGL(ew_modulus_cand_kernel, dim3(tiles, B), dim3(256), 0, st, bwave, a.images, ss, N, a.fi, a.stack + (long)c * N * ss);
+            hipLaunchKernelGGL(ew_modulus_cand_kernel, dim3(tiles, B), dim3(256), 0, st, bwave, img, ss, nimg, a.fi, a.stack + (long)c * N * ss);
         if (a.losses) {
-            hipLaunchKernelGGL(ew_loss_rows_cand_kernel, dim3((unsigned)s, B), dim3(256), 0, st, bwave, a.images, s, N, part);
-            hipLaunchKernelGGL(ew_loss_resid_cand_kernel, dim3((unsigned)s, B), dim3(256), 0, st, bwave, a.images, s, N, part, resid);
+            hipLaunchKernelGGL(ew_loss_rows_cand_kernel, dim3((unsigned)s, B), dim3(256), 0, st, bwave, img, s, nimg, part);
+            hipLaunchKernelGGL(ew_loss_resid_cand_kernel, dim3((unsigned)s, B), dim3(256), 0, st, bwave, img, s, nimg, part, resid);
             hipLaunchKernelGGL(ew_loss_final_kernel, dim3(B), dim3(256), 0, st, resid, s, a.losses + (size_t)c * N);
         }
     }
@@ -880,6 +1018,157 @@ extern "C" int emd_exitwave_search_f64(const float* images, int N, int s, int pa
         a.E = reinterpret_cast<cplx*>(E);
         a.worst = reinterpret_cast<double*>(ws + l.worst);
         launch_recon(a, ws + l.ws, l.cand, st);
+    }
+    return emd::check_launch(who);
+}
+
+extern "C" size_t emd_exitwave_candidate_stacks_workspace_bytes(int C, int N, int s, int pad_periods) {
+    return emd_exitwave_candidates_workspace_bytes(C, N, s, pad_periods);
+}
+
+extern "C" int emd_exitwave_candidate_stacks_f64(const float* images, int C, int N, int s, int pad_periods, const double* defocus_table,
+                                                 double wavelength, double px, double cs, int iterations, int flags, double* losses,
+                                                 double* worst, double* E, double* stack, void* workspace, size_t workspace_bytes,
+                                                 emd_stream_t stream) {
+    const char* who = "emd_exitwave_candidate_stacks_f64";
+    const int S = padded_side(s, pad_periods);
+    if (cand_refused(who, C, N, s, S, pad_periods, px, iterations)) return EMD_E_INVALID;
+    const ReconLayout l = recon_layout(C, N, s, S, true);
+    const size_t ne = (size_t)C * N * s * s, nt = (size_t)C * N * sizeof(double);
+    const Range rg[] = {{workspace, l.bytes, 16},
+                        {images, ne * sizeof(float), 4},   // a chunk of candidates of a larger array starts at any image
+                        {E, (size_t)C * s * s * sizeof(cplx), 16, true},
+                        {stack, ne * sizeof(cplx), 16, true},
+                        {losses, nt, 8},
+                        {worst, (size_t)C * sizeof(double), 8},
+                        {defocus_table, nt, 8}};
+    const int rc = emd::check_ranges(who, rg, 7, "the outputs and the workspace must be 16-byte aligned, arrays of doubles 8-byte, the images 4-byte",
+                                     &workspace_bytes);
+    if (rc != EMD_OK) return rc;
+    const ReconArgs a{images, C, N, s, S, defocus_table, optics(wavelength, px, cs, S), iterations,
+                      (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0, reinterpret_cast<cplx*>(E), reinterpret_cast<cplx*>(stack), losses, worst, 1};
+    launch_recon(a, static_cast<char*>(workspace), l, static_cast<hipStream_t>(stream));
+    return emd::check_launch(who);
+}
+
+namespace {
+
+constexpr int kMaxS0 = 4096;   // the side of the frames the crops are cut from (register.hip's limit)
+
+// the refinement's state (RefineState, centres [N][2], defocus [N]), the tables of a chunk (centres [C][N][2], defocus [C][N]), its
+// crops [C][N][s][s] float32 and losses [C][N], a worst loss for the seed's and the result's own reconstruction
+struct RefineLayout {
+    ReconLayout cand;
+    size_t state, centres, defocus, ctable, dtable, crops, losses, worst, ws, bytes;
+};
+
+RefineLayout refine_layout(int C, int N, int s, int S) {
+    RefineLayout l{};
+    l.cand = recon_layout(C, N, s, S, true);
+    size_t bytes = 0;
+    l.state = bytes;
+    bytes += emd::round256(sizeof(RefineState));
+    l.centres = bytes;
+    bytes += emd::round256((size_t)N * 2 * sizeof(double));
+    l.defocus = bytes;
+    bytes += emd::round256((size_t)N * sizeof(double));
+    l.ctable = bytes;
+    bytes += emd::round256((size_t)C * N * 2 * sizeof(double));
+    l.dtable = bytes;
+    bytes += emd::round256((size_t)C * N * sizeof(double));
+    l.crops = bytes;
+    bytes += emd::round256((size_t)C * N * s * s * sizeof(float));
+    l.losses = bytes;
+    bytes += emd::round256((size_t)C * N * sizeof(double));
+    l.worst = bytes;
+    bytes += emd::round256(sizeof(double));
+    l.ws = bytes;
+    l.bytes = bytes + l.cand.bytes;
+    return l;
+}
+
+bool refine_ok(int N, int S0, int side, int anchor, int C, int rounds) {
+    return N >= 2 && N <= kMaxN && S0 >= 1 && S0 <= kMaxS0 && side >= 1 && side <= S0 && anchor >= 0 && anchor < N && C >= 1 && C <= kMaxC &&
+           rounds >= 1 && rounds <= kMaxRounds;
+}
+
+}  // namespace
+
+extern "C" size_t emd_exitwave_refine_workspace_bytes(int C, int N, int side, int pad_periods) {
+    const int S = padded_side(side, pad_periods);
+    if (N < 2 || !cand_ok(C, N) || !S) return 0;
+    return refine_layout(C, N, side, S).bytes;
+}
+
+extern "C" int emd_exitwave_refine_f64(const float* images, int N, int S0, int side, int pad_periods, float pad_val, const double* centres0,
+                                       const double* defocus0, const double* steps0, int anchor, int C, int rounds, double wavelength,
+                                       double px, double cs, int iterations, int flags, double* result_centres, double* result_defocus,
+                                       double* result, int* status, double* history_losses, int* history_choice, double* history_steps,
+                                       double* E, void* workspace, size_t workspace_bytes, emd_stream_t stream) {
+    const char* who = "emd_exitwave_refine_f64";
+    if (!refine_ok(N, S0, side, anchor, C, rounds)) {
+        emd::set_error("%s: bad refinement (2..%d images of side 1..%d, 1 <= side <= S0, 0 <= anchor < images, 1..%d candidates a chunk, "
+                       "1..%d rounds; got %d images of side %d, side %d, anchor %d, %d candidates, %d rounds)", who, kMaxN, kMaxS0, kMaxC,
+                       kMaxRounds, N, S0, side, anchor, C, rounds);
+        return EMD_E_INVALID;
+    }
+    const int s = side, S = padded_side(s, pad_periods);
+    if (cand_refused(who, C, N, s, S, pad_periods, px, iterations)) return EMD_E_INVALID;
+    const RefineLayout l = refine_layout(C, N, s, S);
+    const int Q = 6 * (N - 1);
+    const Range rg[] = {{workspace, l.bytes, 16},
+                        {images, (size_t)N * S0 * S0 * sizeof(float), 4},
+                        {E, (size_t)s * s * sizeof(cplx), 16, true},
+                        {result_centres, (size_t)N * 2 * sizeof(double), 8},
+                        {result_defocus, (size_t)N * sizeof(double), 8},
+                        {result, 2 * sizeof(double), 8},
+                        {status, 2 * sizeof(int), 8},
+                        {history_losses, (size_t)rounds * Q * sizeof(double), 8},
+                        {history_choice, (size_t)rounds * sizeof(int), 4},
+                        {history_steps, (size_t)rounds * 2 * sizeof(double), 8},
+                        {centres0, (size_t)N * 2 * sizeof(double), 8},
+                        {defocus0, (size_t)N * sizeof(double), 8},
+                        {steps0, 2 * sizeof(double), 8}};
+    const int rc = emd::check_ranges(who, rg, 13,
+                                     "the workspace and E must be 16-byte aligned, arrays of doubles and status 8-byte, the images and "
+                                     "history_choice 4-byte", &workspace_bytes);
+    if (rc != EMD_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    RefineState* state = reinterpret_cast<RefineState*>(ws + l.state);
+    double* centres = reinterpret_cast<double*>(ws + l.centres);
+    double* defocus = reinterpret_cast<double*>(ws + l.defocus);
+    double* ctable = reinterpret_cast<double*>(ws + l.ctable);
+    double* dtable = reinterpret_cast<double*>(ws + l.dtable);
+    float* crops = reinterpret_cast<float*>(ws + l.crops);
+    double* worst1 = reinterpret_cast<double*>(ws + l.worst);
+    ReconArgs a{crops, 1, N, s, S, dtable, optics(wavelength, px, cs, S), iterations, (flags & EMD_EXITWAVE_FROM_INTENSITY) ? 1 : 0,
+                nullptr, nullptr, reinterpret_cast<double*>(ws + l.losses), worst1, 1};
+    // n candidates from poll q0 on (q0 < 0: the state itself): their tables, their crops, their reconstructions
+    auto evaluate = [&](int q0, int n, double* steps_out) {
+        hipLaunchKernelGGL(ew_refine_table_kernel, dim3(1), dim3(64), 0, st, state, centres, defocus, N, anchor, q0, n, ctable, dtable,
+                           steps_out);
+        emd::launch_crop_candidates(images, N, S0, ctable, n, s, pad_val, crops, st);
+        a.C = n;
+        launch_recon(a, ws + l.ws, l.cand, st);
+    };
+    hipLaunchKernelGGL(ew_refine_init_kernel, dim3(1), dim3(64), 0, st, centres0, defocus0, steps0, N, state, centres, defocus);
+    evaluate(-1, 1, nullptr);
+    hipLaunchKernelGGL(ew_refine_seed_kernel, dim3(1), dim3(64), 0, st, worst1, state);
+    for (int r = 0; r < rounds; ++r) {
+        double* hl = history_losses + (size_t)r * Q;
+        for (int q0 = 0; q0 < Q; q0 += C) {
+            a.worst = hl + q0;
+            evaluate(q0, Q - q0 < C ? Q - q0 : C, q0 == 0 ? history_steps + 2 * (size_t)r : nullptr);
+        }
+        hipLaunchKernelGGL(ew_refine_decide_kernel, dim3(1), dim3(64), 0, st, hl, Q, N, anchor, state, centres, defocus, history_choice + r);
+    }
+    hipLaunchKernelGGL(ew_refine_finish_kernel, dim3(1), dim3(64), 0, st, state, centres, defocus, N, result_centres, result_defocus, result,
+                       status);
+    if (E) {   // the exit wave at the result: one more reconstruction, of one candidate, without its losses
+        a.E = reinterpret_cast<cplx*>(E);
+        a.losses = a.worst = nullptr;
+        evaluate(-1, 1, nullptr);
     }
     return emd::check_launch(who);
 }

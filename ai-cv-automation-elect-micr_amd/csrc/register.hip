@@ -18,6 +18,7 @@
 //                        weighted centroid, (dx, dy, response)
 //   reg_centres_kernel   pos_k = pos_{k-1} + shift_{k-1}; centre_k = S / 2 + pos_k - mean(pos): one thread
 //   reg_crop_kernel      32 x 8 tiles of the output: four taps, every operation rounded on its own, float32 out
+//   reg_crop_cand_kernel the same pixel function over [C][N] planes: image b mod N under the centres of candidate b / N
 //
 // No floating-point atomics, every sum in a fixed order: bitwise reproducible.  Launches only; shifts and centres are read on the device.
 #include <climits>
@@ -284,6 +285,36 @@ __global__ __launch_bounds__(256) void reg_crop_kernel(const float* __restrict__
     out[(n * side + r) * side + c] = (float)v;
 }
 
+// reg_crop_kernel's arithmetic for one output pixel (r, c) of the crop of `img` [S][S] around centre = (x, y), statement by statement,
+// for the candidates' kernel.  reg_crop_kernel keeps its own text: moving it onto this function changed its instructions (not its results'
+// specification), and its digest is kept (profiles/exitwave_refine_isa_digest_compare.txt).
+__device__ __forceinline__ float crop_pixel(const float* __restrict__ img, int S, const double* __restrict__ centre, int side, float pad_val,
+                                            int r, int c) {
+#pragma clang fp contract(off)
+    long ix, iy;
+    double fx, fy;
+    crop_origin(centre[0], side, ix, fx);
+    crop_origin(centre[1], side, iy, fy);
+    const long x = ix + c, y = iy + r;
+    const bool xin0 = x >= 0 && x < S, xin1 = x + 1 >= 0 && x + 1 < S, yin0 = y >= 0 && y < S, yin1 = y + 1 >= 0 && y + 1 < S;
+    const double pad = (double)pad_val;
+    const double p00 = yin0 && xin0 ? (double)img[y * S + x] : pad, p01 = yin0 && xin1 ? (double)img[y * S + x + 1] : pad;
+    const double p10 = yin1 && xin0 ? (double)img[(y + 1) * S + x] : pad, p11 = yin1 && xin1 ? (double)img[(y + 1) * S + x + 1] : pad;
+    const double v = (1.0 - fy) * ((1.0 - fx) * p00 + fx * p01) + fy * ((1.0 - fx) * p10 + fx * p11);
+    return (float)v;
+}
+
+
+// grid (ceil(side / 32), ceil(side / 8), C N), block (32, 8): plane b = c N + n is image n = b mod N under centres_table[c][n]
+__global__ __launch_bounds__(256) void reg_crop_cand_kernel(const float* __restrict__ images, int N, int S,
+                                                            const double* __restrict__ centres_table, int side, float pad_val,
+                                                            float* __restrict__ out) {
+    const int c = blockIdx.x * 32 + threadIdx.x, r = blockIdx.y * 8 + threadIdx.y;
+    const long b = blockIdx.z;
+    if (c >= side || r >= side) return;
+    out[(b * side + r) * side + c] = crop_pixel(images + (b % N) * S * S, S, centres_table + 2 * b, side, pad_val, r, c);
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 using emd::check_ranges;
@@ -422,4 +453,27 @@ extern "C" int emd_crop_stack_f32(const float* images, int N, int S, const doubl
     hipLaunchKernelGGL(reg_crop_kernel, dim3((unsigned)emd::tiles_of(side, 32), (unsigned)emd::tiles_of(side, 8), (unsigned)N), dim3(32, 8), 0,
                        static_cast<hipStream_t>(stream), images, S, centres, side, pad_val, out);
     return emd::check_launch("emd_crop_stack_f32");
+}
+
+// the launch of emd_crop_candidates_f32, for emd_exitwave_refine_f64 (exitwave.hip), which has checked the arguments
+void emd::launch_crop_candidates(const float* images, int N, int S, const double* centres_table, int C, int side, float pad_val, float* out,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL(reg_crop_cand_kernel, dim3((unsigned)emd::tiles_of(side, 32), (unsigned)emd::tiles_of(side, 8), (unsigned)(C * N)),
+                       dim3(32, 8), 0, st, images, N, S, centres_table, side, pad_val, out);
+}
+
+extern "C" int emd_crop_candidates_f32(const float* images, int N, int S0, const double* centres_table, int C, int side, float pad_val,
+                                       float* out, emd_stream_t stream) {
+    if (N < 1 || C < 1 || (long)C * N > kMaxCrops || S0 < 1 || S0 > kMaxS || side < 1 || side > S0) {
+        emd::set_error("emd_crop_candidates_f32: bad shape (candidates x images in 1..%d, images of side 1..%d, 1 <= side <= S0; got %d "
+                       "candidates of %d images of side %d, side %d)", kMaxCrops, kMaxS, C, N, S0, side);
+        return EMD_E_INVALID;
+    }
+    const Range r[] = {{images, (size_t)N * S0 * S0 * sizeof(float), 4, false, true},
+                       {out, (size_t)C * N * side * side * sizeof(float), 4, false, false},
+                       {centres_table, (size_t)C * N * 2 * sizeof(double), 8, false, true}};
+    const int rc = check_ranges("emd_crop_candidates_f32", r, 3, "centres_table must be 8-byte aligned, images and out 4-byte");
+    if (rc != EMD_OK) return rc;
+    emd::launch_crop_candidates(images, N, S0, centres_table, C, side, pad_val, out, static_cast<hipStream_t>(stream));
+    return emd::check_launch("emd_crop_candidates_f32");
 }

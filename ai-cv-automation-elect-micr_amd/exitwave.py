@@ -13,15 +13,19 @@ Deviations from the reference: ``px`` (the pixel size) replaces its ``px_dim = 1
 ``|b_k| = 0`` the modulus constraint gives ``a_k`` (the reference: NaN); with ``from_intensity`` the amplitude is
 ``sqrt(max(image_k, 0))`` and ``psi_k`` starts as that amplitude, not as the image; with ``cs != 0`` the back-propagation multiplies
 by ``H(-df)`` as the reference does, which is not ``conj H(df)`` (the Cs term keeps its sign; at ``cs == 0`` the two are equal bit
-for bit); ``aperture_mask``, ``refine_params``, TIFF reading and the display helpers are not
-here.  ``resize_stack`` (``cv2.resize`` of the crops) is ``emdenoise.resample.resize``.
+for bit); ``aperture_mask``, TIFF reading, a gradient-based refinement of the positions and the display
+helpers are not here; ``refine_params`` is a compass search, since the reference's ``minimize`` call cannot run.  ``resize_stack`` (``cv2.resize`` of the crops) is ``emdenoise.resample.resize``.
 
 Registration (csrc/register.hip) is what the reference's ``EWREC.__init__`` does before it reconstructs:
 ``phase_correlate`` / ``rel_pos_estimate`` (``cv2.phaseCorrelate`` restated in include/emdenoise.h; OpenCV is not run), the cropping
 centres, ``crop_stack`` (a bilinear sub-pixel crop), and ``align`` / ``reconstruct_series`` that chain them on the device.  Deviations:
 ``R = P / |P|`` is 0 where ``|P| = 0`` (OpenCV adds an epsilon); images of zeros give shift (0, 0) and response 0 (cv2: NaN); the
 centres are ``S/2 + pos - mean(pos)`` (the reference's loop does not run and its sign moves the crop against the drift); the crop is
-bilinear (the reference weights the wrong tap and returns the integer crop)."""
+bilinear (the reference weights the wrong tap and returns the integer crop).
+
+Refinement is the constructor's ``param_refinement=True``: ``crop_candidates`` and ``reconstruct_candidate_stacks``
+(candidates that have their own images), ``refine_params`` (the compass search over crop centres and defocuses, decided on the
+device) and ``refine_series`` (align, refine, crop, reconstruct)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -342,13 +346,27 @@ def reconstruct_candidates(images, defocus_table, wavelength, px=1.0, cs=0.0, it
     float64 CUDA table is used where it is (capturable); anything else is uploaded and must be finite.  When the workspace for all C
     exceeds ``CANDIDATES_WORKSPACE_CAP`` bytes the candidates run in chunks, one call after the other on the stream with no
     synchronisation between them; ``candidates_per_launch`` sets the chunk.  The bits are the same for any chunking."""
+    return _candidates("reconstruct_candidates", False, images, defocus_table, wavelength, px, cs, iterations, pad_periods, from_intensity,
+                       per_image, return_waves, return_stack, candidates_per_launch, _composed)
+
+
+def _candidates(name, own_stacks, images, defocus_table, wavelength, px, cs, iterations, pad_periods, from_intensity, per_image,
+                return_waves, return_stack, candidates_per_launch, _composed):
+    """``reconstruct_candidates`` (images [N,s,s]) and ``reconstruct_candidate_stacks`` (``own_stacks``: [C,N,s,s])."""
     import torch
 
-    name = "reconstruct_candidates"
-    N, s = _images(name, images, pad_periods)
+    tshape = tuple(defocus_table.shape) if hasattr(defocus_table, "shape") else np.shape(defocus_table)
+    if own_stacks:
+        shp = tuple(images.shape) if hasattr(images, "shape") else np.shape(images)
+        if len(shp) != 4 or shp[0] < 1:
+            raise ValueError(f"{name}: the stacks are [C,N,s,s], C >= 1 (got a shape of {shp})")
+        N, s = _images(name, images[0], pad_periods)
+        if len(tshape) != 2 or tshape != (shp[0], N):
+            raise ValueError(f"{name}: the defocus table is [C,N] = [{shp[0]},{N}] (got a shape of {tshape})")
+    else:
+        N, s = _images(name, images, pad_periods)
     _recon_kw(name, {"px": px, "iterations": iterations})
     _positive(name, wavelength=wavelength)
-    tshape = tuple(defocus_table.shape) if hasattr(defocus_table, "shape") else np.shape(defocus_table)
     if len(tshape) != 2 or tshape[1] != N or tshape[0] < 1:
         raise ValueError(f"{name}: the defocus table is [C,N] = [C,{N}], C >= 1 (got a shape of {tshape})")
     Ct = int(tshape[0])
@@ -374,7 +392,10 @@ def reconstruct_candidates(images, defocus_table, wavelength, px=1.0, cs=0.0, it
             if int(candidates_per_launch) != candidates_per_launch or not 1 <= candidates_per_launch <= per:
                 raise ValueError(f"{name}: candidates_per_launch must be an integer, 1..{per} (got {candidates_per_launch!r})")
             per = int(candidates_per_launch)
-        x, as_np = _wave(images, device, True)
+        if own_stacks:
+            x, as_np = _real(images, device)
+        else:
+            x, as_np = _wave(images, device, True)
         losses = torch.empty((Ct, N), dtype=torch.float64, device=device)
         worst = torch.empty((Ct,), dtype=torch.float64, device=device)
         E = torch.empty((Ct, s, s), dtype=torch.complex128, device=device) if return_waves else None
@@ -382,15 +403,26 @@ def reconstruct_candidates(images, defocus_table, wavelength, px=1.0, cs=0.0, it
         nbytes = lib.emd_exitwave_candidates_workspace_bytes(per, N, s, int(pad_periods))
         ws = _ws(nbytes, device)
         flags = FROM_INTENSITY if from_intensity else 0
+        entry = "emd_exitwave_candidate_stacks_f64" if own_stacks else "emd_exitwave_candidates_f64"
         for c0 in range(0, Ct, per):
             n = min(per, Ct - c0)
             sub = lambda t: _p(t[c0:c0 + n]) if t is not None else None
-            _lib.check(lib.emd_exitwave_candidates_f64(_p(x), n, N, s, int(pad_periods), sub(table), float(wavelength), float(px), float(cs),
-                                                       int(iterations), flags, sub(losses), sub(worst), sub(E), sub(stack), _p(ws), nbytes,
-                                                       _lib.stream_ptr()), "emd_exitwave_candidates_f64")
+            _lib.check(getattr(lib, entry)(sub(x) if own_stacks else _p(x), n, N, s, int(pad_periods), sub(table), float(wavelength),
+                                           float(px), float(cs), int(iterations), flags, sub(losses), sub(worst), sub(E), sub(stack), _p(ws),
+                                           nbytes, _lib.stream_ptr()), entry)
     outs = [losses if per_image else worst] + [o for o in (E, stack) if o is not None]
     outs = [o.cpu().numpy() if as_np else o for o in outs]
     return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+def reconstruct_candidate_stacks(stacks, defocus_table, wavelength, px=1.0, cs=0.0, iterations=50, pad_periods=0, from_intensity=False,
+                                 per_image=False, return_waves=False, return_stack=False, candidates_per_launch=None, _composed=False):
+    """``reconstruct_candidates`` for candidates that have their own images (``emd_exitwave_candidate_stacks_f64``):
+    ``stacks`` ``[C,N,s,s]`` float32 under ``defocus_table`` ``[C,N]``.  It returns what ``reconstruct_candidates`` returns, chunks under
+    ``CANDIDATES_WORKSPACE_CAP`` in the same way, and every candidate's numbers are bit for bit those of ``reconstruct`` /
+    ``reconstruction_loss`` with its stack and its row alone."""
+    return _candidates("reconstruct_candidate_stacks", True, stacks, defocus_table, wavelength, px, cs, iterations, pad_periods,
+                       from_intensity, per_image, return_waves, return_stack, candidates_per_launch, _composed)
 
 
 def search_increments(search_range, num):
@@ -725,3 +757,192 @@ def reconstruct_series(stack, defocuses, wavelength, side, window=False, **recon
     _padded_side("reconstruct_series", side, reconstruct_kw.get("pad_periods", 0))
     crops, _ = align(stack, side, window)
     return reconstruct(crops, defocuses, wavelength, **reconstruct_kw)
+
+
+# ---- refinement of the crop centres and the defocuses (csrc/exitwave.hip, csrc/register.hip) ------------------------
+
+def _checked_doubles(name, what, v, shape):
+    """On the host, before anything moves: a contiguous float64 CUDA tensor of ``shape`` as it is, anything else as a finite float64
+    array of that shape."""
+    import torch
+
+    if isinstance(v, torch.Tensor) and v.is_cuda:
+        if v.dtype != torch.float64 or tuple(v.shape) != shape or not v.is_contiguous():
+            raise ValueError(f"{name}: device {what} must be a contiguous float64 tensor of shape {list(shape)}")
+        return v
+    a = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v, np.float64)
+    if a.shape != shape or not np.isfinite(a).all():
+        raise ValueError(f"{name}: the {what} are {list(shape)}, finite (got a shape of {a.shape})")
+    return np.ascontiguousarray(a)
+
+
+def _uploaded(name, what, v, device):
+    """A value ``_checked_doubles`` let through, on the device."""
+    import torch
+
+    if isinstance(v, torch.Tensor):
+        return v
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{name}: the {what} are not on the device; pass a float64 CUDA tensor when capturing")
+    return torch.from_numpy(v).to(device)
+
+
+def crop_candidates(stack, centres_table, side, pad_val=0.0):
+    """``crop_stack`` under every one of C sets of centres in one launch (``emd_crop_candidates_f32``): ``stack`` ``[N,S,S]`` float32,
+    ``centres_table`` ``[C,N,2]`` -> float32 ``[C,N,side,side]``; ``out[c]`` is bit for bit ``crop_stack(stack, centres_table[c], side)``.
+    C N <= 65535.  A contiguous float64 CUDA table is used where it is (capturable), anything else is uploaded."""
+    import torch
+
+    name = "crop_candidates"
+    N, S = _stack(name, stack, 1, MAX_CROPS, power_of_two=False)
+    side = _side(name, side, S)
+    tshape = tuple(centres_table.shape if hasattr(centres_table, "shape") else np.shape(centres_table))
+    if len(tshape) != 3 or tshape[1:] != (N, 2) or not 1 <= tshape[0] <= MAX_CROPS // N:
+        raise ValueError(f"{name}: the centres table is [C,N,2] = [C,{N},2], 1 <= C <= {MAX_CROPS // N} (got a shape of {tshape})")
+    if not np.isfinite(pad_val):
+        raise ValueError(f"{name}: pad_val must be finite (got {pad_val!r})")
+    if isinstance(centres_table, torch.Tensor) and centres_table.is_cuda:
+        table = _checked_doubles(name, "centres", centres_table, tshape)
+    else:   # as crop_stack: host centres are uploaded as they are (a non-finite centre puts every tap outside)
+        table = np.ascontiguousarray(centres_table.cpu() if isinstance(centres_table, torch.Tensor) else centres_table, dtype=np.float64)
+    device = _device(stack)
+    table = _uploaded(name, "centres", table, device)
+    x, as_np = _real(stack, device)
+    out = torch.empty((tshape[0], N, side, side), dtype=torch.float32, device=device)
+    _lib.check(_lib.load().emd_crop_candidates_f32(_p(x), N, S, _p(table), int(tshape[0]), side, float(pad_val), _p(out), _lib.stream_ptr()),
+               "emd_crop_candidates_f32")
+    return out.cpu().numpy() if as_np else out
+
+
+class RefineResult(NamedTuple):
+    centres: object            # [N,2] = (x, y) and [N]: the state after the last round
+    defocuses: object
+    loss: object               # its (largest over the images) loss: the smallest finite one met, the seed's included
+    loss0: object              # the seed's
+    history_losses: object     # [rounds, 6 (N - 1)]: every poll of every round
+    history_choice: object     # [rounds] int32: the poll that was taken, -1 the steps were halved, -2 no poll was finite
+    history_steps: object      # [rounds, 2] = (step_xy, step_defocus) the round polled with
+    status: int                # SEARCH_NONFINITE
+    moves: int
+    wave: object               # E at the result with return_exit_wave, else None
+
+
+def refine_polls(N, anchor):
+    """[(axis, k)] of the parameters p = 0..3 (N - 1) - 1 of ``refine_params``: axis 0 = x, 1 = y, 2 = defocus of image k, the images
+    in ascending k without the anchor.  Poll q = 2 p adds the axis' step to that entry, q = 2 p + 1 subtracts it."""
+    free = [k for k in range(N) if k != anchor]
+    return [(axis, k) for axis in range(3) for k in free]
+
+
+def refine_params(stack, centres, defocuses, wavelength, side, anchor=None, step_xy=1.0, step_defocus=None, rounds=8, candidates=None,
+                  pad_val=0.0, return_exit_wave=False, **kw):
+    """``EWREC.refine_params`` (ewrec_class.py:436-478, which does not run): the crop centres ``[N,2]`` and the
+    defocuses ``[N]`` of a series ``stack`` ``[N,S,S]`` float32 (2 <= N <= 64) refined jointly, on the device
+    (``emd_exitwave_refine_f64``), so that the largest per-image ``reconstruction_loss`` of the ``side x side`` crops gets smaller.
+
+    A compass search: every round polls each of the 3 (N - 1) free parameters at plus and minus its step (``step_xy`` pixels for the
+    centres, ``step_defocus`` for the defocuses; default 0.1 max|defocuses|), all 6 (N - 1) polls reconstructed as candidates, ``candidates``
+    (1..64) at a time -- by default as many as fit ``CANDIDATES_WORKSPACE_CAP`` --, with the same bits whatever that number is.  The
+    best poll is taken if it is strictly better than the best so far; otherwise both steps are halved.  Image ``anchor`` (default
+    N // 2) keeps its centre and defocus: it is the gauge.  The loss never increases; the true parameters are NOT what it converges to
+    (DESIGN.md 3.30).
+
+    ``centres``, ``defocuses`` and ``steps`` = (step_xy, step_defocus) given as one float64 CUDA tensor ``[2]`` in ``step_xy`` (then
+    ``step_defocus`` must be None) are used where they are: the call is launches only and can be captured.  Keywords: ``px``, ``cs``,
+    ``iterations``, ``pad_periods``, ``from_intensity``.  A ``RefineResult``: numpy / float / int fields for a numpy stack, device
+    tensors for a CUDA stack (``status`` and ``moves`` are read back unless the stream is capturing)."""
+    import torch
+
+    name = "refine_params"
+    args, composed = _recon_kw(name, kw)
+    N, S0 = _stack(name, stack, 2, MAX_IMAGES, power_of_two=False)
+    side = _side(name, side, S0)
+    _padded_side(name, side, args["pad_periods"])
+    _positive(name, wavelength=wavelength)
+    if anchor is None:
+        anchor = N // 2
+    if int(anchor) != anchor or not 0 <= anchor < N:
+        raise ValueError(f"{name}: anchor must be an integer, 0..{N - 1} (got {anchor!r})")
+    if int(rounds) != rounds or not 1 <= rounds <= MAX_ROUNDS:
+        raise ValueError(f"{name}: 1..{MAX_ROUNDS} rounds (got {rounds!r})")
+    if not np.isfinite(pad_val):
+        raise ValueError(f"{name}: pad_val must be finite (got {pad_val!r})")
+    Q = 6 * (N - 1)
+    if candidates is not None and (int(candidates) != candidates or not 1 <= candidates <= MAX_CANDIDATES):
+        raise ValueError(f"{name}: 1..{MAX_CANDIDATES} candidates (got {candidates!r})")
+    c0 = _checked_doubles(name, "centres", centres, (N, 2))
+    d0 = _checked_doubles(name, "defocuses", defocuses, (N,))
+    if isinstance(step_xy, torch.Tensor) and step_xy.is_cuda:
+        if step_defocus is not None:
+            raise ValueError(f"{name}: device steps are one tensor (step_xy, step_defocus); step_defocus must be None")
+        steps = _checked_doubles(name, "steps", step_xy, (2,))
+    else:
+        if step_defocus is None:
+            if isinstance(d0, torch.Tensor):
+                raise ValueError(f"{name}: with device defocuses give step_defocus (its default reads them)")
+            step_defocus = 0.1 * float(np.abs(d0).max())
+        _positive(name, step_xy=step_xy, step_defocus=step_defocus)
+        steps = np.array([step_xy, step_defocus], np.float64)
+    device = _device(stack)
+    c0, d0, steps = (_uploaded(name, what, v, device) for what, v in (("centres", c0), ("defocuses", d0), ("steps", steps)))
+    x, as_np = _real(stack, device)
+    capturing = torch.cuda.is_current_stream_capturing()
+    lib = _lib.load()
+    pad, R = int(args["pad_periods"]), int(rounds)
+    out_c = torch.empty((N, 2), dtype=torch.float64, device=device)
+    out_d = torch.empty((N,), dtype=torch.float64, device=device)
+    result = torch.empty((2,), dtype=torch.float64, device=device)
+    status = torch.empty((2,), dtype=torch.int32, device=device)
+    hist_loss = torch.empty((R, Q), dtype=torch.float64, device=device)
+    hist_choice = torch.empty((R,), dtype=torch.int32, device=device)
+    hist_steps = torch.empty((R, 2), dtype=torch.float64, device=device)
+    E = torch.empty((side, side), dtype=torch.complex128, device=device) if return_exit_wave else None
+    with _composed_knob(composed):
+        if candidates is None:   # the largest chunk whose workspace fits the cap
+            candidates = min(Q, MAX_CANDIDATES)
+            while candidates > 1 and lib.emd_exitwave_refine_workspace_bytes(candidates, N, side, pad) > CANDIDATES_WORKSPACE_CAP:
+                candidates -= 1
+        Cn = int(candidates)
+        nbytes = lib.emd_exitwave_refine_workspace_bytes(Cn, N, side, pad)
+        ws = _ws(nbytes, device)
+        rc = lib.emd_exitwave_refine_f64(_p(x), N, S0, side, pad, float(pad_val), _p(c0), _p(d0), _p(steps), int(anchor), Cn, R,
+                                         float(wavelength), float(args["px"]), float(args["cs"]), int(args["iterations"]),
+                                         FROM_INTENSITY if args["from_intensity"] else 0, _p(out_c), _p(out_d), _p(result), _p(status),
+                                         _p(hist_loss), _p(hist_choice), _p(hist_steps), _p(E), _p(ws), nbytes, _lib.stream_ptr())
+    _lib.check(rc, "emd_exitwave_refine_f64")
+    if capturing:
+        return RefineResult(out_c, out_d, result[0], result[1], hist_loss, hist_choice, hist_steps, status[0], status[1], E)
+    st = status.cpu().numpy()
+    if as_np:
+        res = result.cpu().numpy()
+        return RefineResult(out_c.cpu().numpy(), out_d.cpu().numpy(), float(res[0]), float(res[1]), hist_loss.cpu().numpy(),
+                            hist_choice.cpu().numpy(), hist_steps.cpu().numpy(), int(st[0]), int(st[1]), None if E is None else E.cpu().numpy())
+    return RefineResult(out_c, out_d, result[0], result[1], hist_loss, hist_choice, hist_steps, int(st[0]), int(st[1]), E)
+
+
+def refine_series(stack, defocuses, wavelength, side, window=False, refine_kw=None, **reconstruct_kw):
+    """``EWREC.__init__`` with ``param_refinement=True``: ``align`` (the centres), ``refine_params`` from them and ``defocuses``, then
+    ``crop_stack`` and ``reconstruct`` at the refined parameters: ``(exit wave [side,side], RefineResult)``.  ``refine_kw``: ``anchor``,
+    ``step_xy``, ``step_defocus``, ``rounds``, ``candidates``, ``pad_val``, and ``iterations`` for the polls' reconstructions (default:
+    ``reconstruct_kw``'s); the optics and ``pad_periods`` of ``reconstruct_kw`` hold for both."""
+    name = "refine_series"
+    N, S = _stack(name, stack, 2, MAX_PAIRS)
+    side = _side(name, side, S)
+    _padded_side(name, side, reconstruct_kw.get("pad_periods", 0))
+    _recon_kw(name, {k: v for k, v in reconstruct_kw.items() if k not in ("return_stack", "return_losses")})
+    rkw = dict(refine_kw or {})
+    unknown = sorted(set(rkw) - {"anchor", "step_xy", "step_defocus", "rounds", "candidates", "pad_val", "iterations"})
+    if unknown:
+        raise TypeError(f"{name}: unexpected refine_kw key(s) {unknown}")
+    shared = {k: v for k, v in reconstruct_kw.items() if k in ("px", "cs", "iterations", "pad_periods", "from_intensity", "_composed")}
+    shared.update({k: rkw.pop(k) for k in ("iterations",) if k in rkw})
+    x, as_np = _real(stack, _device(stack))
+    _, centres = align(x, side, window, rkw.get("pad_val", 0.0))
+    ref = refine_params(x, centres, defocuses, wavelength, side, **rkw, **shared)
+    crops = _crop(x, ref.centres, side, rkw.get("pad_val", 0.0))
+    out = reconstruct(crops, ref.defocuses, wavelength, **reconstruct_kw)
+    if not as_np:
+        return out, ref
+    to_np = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else v
+    ref = RefineResult(*(to_np(v) if i not in (2, 3) else float(v) for i, v in enumerate(ref)))
+    return (tuple(to_np(o) for o in out) if isinstance(out, tuple) else to_np(out)), ref

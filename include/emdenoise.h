@@ -1312,6 +1312,57 @@ int emd_exitwave_search_f64(const float* images, int N, int s, int pad_periods, 
                             double* history_increments, double* history_losses, int* status, double* E, void* workspace,
                             size_t workspace_bytes, emd_stream_t stream);
 
+/* Candidate stacks and the refinement of crop centres and defocuses: ewrec_class.py:436-478, `refine_params` and
+ * `reconstruction_loss_arbitrary_params`, which do not run as written; the formulas below are the specification.
+ *
+ * crop_candidates: images [N][S0][S0] float32, centres_table [C][N][2] (DEVICE doubles), out [C][N][side][side], C N <= 65535: one
+ *     launch with the candidate as a grid dimension; out[c] is bit for bit emd_crop_stack_f32 under centres_table[c].
+ *
+ * candidate_stacks: emd_exitwave_candidates_f64 with images [C][N][s][s]: candidate c has its own N images.  losses[c], worst[c],
+ *     E[c] and stack[c] are bit for bit what emd_exitwave_reconstruct_f64 gives for images[c] and defocus_table[c] alone; the same
+ *     kernels, launch counts and workspace as emd_exitwave_candidates_f64.  The images are 4-byte aligned (a chunk of the candidates
+ *     of a larger array starts at any image); everything else as there.
+ *
+ * refine: a compass (pattern) search that minimises the largest per-image loss over the crop centres and the defocuses, jointly.
+ *     images [N][S0][S0] float32, 2 <= N <= 64, 1 <= S0 <= 4096; the crops are side x side (emd_crop_stack_f32's arithmetic, pad_val
+ *     outside the frame), side (1 + pad_periods) a power of two in 8..4096; the optics, iterations, flags and pad_periods are
+ *     emd_exitwave_reconstruct_f64's.  centres0 [N][2] = (x, y), defocus0 [N], steps0 [2] = (step_xy, step_df) are DEVICE doubles;
+ *     every decision is made on the device, nothing is read back: capturable, and a replay reads new images, seed and steps.  Every
+ *     operation below is one rounded double operation.
+ *   State: centres [N][2], defocus [N], steps, best.  `anchor` (0 <= anchor < N) is the gauge: that image's three parameters are
+ *     never polled (a common shift picks another region; a common defocus offset leaves the loss unchanged at pad_periods = 0).
+ *   loss(centres, defocus) = the worst loss (emd_exitwave_candidates_f64's) of the reconstruction of the crops around `centres`.
+ *   Before round 0: loss0 = loss(seed); best = loss0, or +inf with EMD_SEARCH_NONFINITE if loss0 is not finite.
+ *   Polls: the free images j = 0..N-2 are the k != anchor in ascending k; parameter p = axis (N - 1) + j, axis 0 = x, 1 = y,
+ *     2 = defocus; candidate q = 2 p is the state with that one entry + step, q = 2 p + 1 with that entry - step (step_xy for axes
+ *     0 and 1, step_df for axis 2); Q = 6 (N - 1).
+ *   A round: the Q candidates in ceil(Q / C) chunks of at most C (1 <= C <= 64; a candidate's bits do not depend on C), each chunk a
+ *     table kernel, one candidate crop and one candidate-stacks reconstruction; history_losses[r][q] = its worst loss;
+ *     history_steps[r] = the steps the round polled with.  i = the first index of the smallest FINITE loss.  loss_i < best strictly:
+ *     the state becomes candidate i, best = loss_i, moves += 1, history_choice[r] = i.  Otherwise both steps are multiplied by 0.5
+ *     and history_choice[r] = -1.  No finite candidate: nothing changes, history_choice[r] = -2, EMD_SEARCH_NONFINITE is set.
+ *   result_centres [N][2], result_defocus [N]; result [2] = (best, loss0); status [2] (ints) = (status bits, moves);
+ *     history_losses [rounds][Q], history_choice [rounds] (ints), history_steps [rounds][2]; E [s][s] (may be NULL): the exit wave at
+ *     the result, by one more reconstruction.  1 <= rounds <= 1024.
+ *   Launches, with I iterations, R rounds, K = ceil(Q / C) and pad_periods == 0:  2 I + 11 + R (K (2 I + 8) + 1), + 2 I + 4 with E
+ *     (init; the seed's table, crop and 2 I + 6 of a reconstruction with its losses; seed; per chunk the same 2 I + 8; one decision
+ *     a round; finish; for E a table, a crop and 2 I + 2).  With pad_periods > 0 a reconstruction of n candidates is n (8 I + 2) + 2
+ *     launches (one candidate without losses: 8 I) in place of 2 I + 6 (2 I + 2).
+ *   The workspace is 16-byte aligned, as is E; arrays of doubles and status 8-byte; the images and history_choice 4-byte.  Outputs and
+ *     the workspace may overlap neither one another nor the inputs. */
+int emd_crop_candidates_f32(const float* images, int N, int S0, const double* centres_table, int C, int side, float pad_val, float* out,
+                            emd_stream_t stream);
+size_t emd_exitwave_candidate_stacks_workspace_bytes(int C, int N, int s, int pad_periods);
+int emd_exitwave_candidate_stacks_f64(const float* images, int C, int N, int s, int pad_periods, const double* defocus_table,
+                                      double wavelength, double px, double cs, int iterations, int flags, double* losses, double* worst,
+                                      double* E, double* stack, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+size_t emd_exitwave_refine_workspace_bytes(int C, int N, int side, int pad_periods);
+int emd_exitwave_refine_f64(const float* images, int N, int S0, int side, int pad_periods, float pad_val, const double* centres0,
+                            const double* defocus0, const double* steps0, int anchor, int C, int rounds, double wavelength, double px,
+                            double cs, int iterations, int flags, double* result_centres, double* result_defocus, double* result,
+                            int* status, double* history_losses, int* history_choice, double* history_steps, double* E, void* workspace,
+                            size_t workspace_bytes, emd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-D FFT of any side (csrc/fft_any.hip): numpy.fft.fft2 / ifft2 / rfft2 and Fresnel propagation of [B][H][W]
  * with H and W independent, in double; complex arrays are interleaved (re, im) doubles.  The functions above keep their limit (a
