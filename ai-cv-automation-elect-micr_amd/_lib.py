@@ -609,6 +609,17 @@ SIGNATURES = {
     # step rates beta1 beta2 epsilon losses pred g_amp g_phase g_params workspace ws_bytes stream
     "emd_psiart_step_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_int] +
                             [C.c_void_p] * 8 + [C.c_double] * 3 + [C.c_void_p] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- the same with per-image shifts
+    "emd_psiart_shift_workspace_bytes": (C.c_size_t, [C.c_int] * 2),
+    # images N S amp phase params shifts ramp weights wavelength sampling offset_scale flags losses pred g_amp g_phase g_params g_shifts
+    # workspace ws_bytes stream
+    "emd_psiart_shift_loss_grad_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double] * 3 + [C.c_int] +
+                                       [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    # images N S amp phase params shifts ramp weights wavelength sampling offset_scale flags m_amp v_amp m_phase v_phase m_params
+    # v_params m_shifts v_shifts step rates shift_rates beta1 beta2 epsilon losses pred g_amp g_phase g_params g_shifts workspace
+    # ws_bytes stream
+    "emd_psiart_shift_step_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double] * 3 + [C.c_int] +
+                                  [C.c_void_p] * 11 + [C.c_double] * 3 + [C.c_void_p] * 6 + [C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 # development hooks (include/emdenoise_dev.h): not part of the drop-in boundary, bound for tools/ and bench.py's A/B legs

@@ -22,6 +22,13 @@
 // sum in a fixed order: bitwise reproducible.  Launches only; parameters, ramp, weights, rates and the step counter are read on the
 // device.
 //
+// Per-image sub-pixel shifts (the emd_psiart_shift_* entry points): the SHIFT instances of the two column kernels add
+// 2 (i' d0_k + j' d1_k) / S to the argument of sincospi (i', j' the signed indices), which multiplies C_k by the linear phase of a
+// circular shift of image k by (d0_k, d1_k) pixels.  dL/dd0_k = sum Im z_k 2 pi i' / S and dL/dd1_k = sum Im z_k 2 pi j' / S are sums
+// per image: pa_bwd_cols_kernel reduces them over the workgroup inside its loop over k, into partial_shift[line][k][2], and the SHIFT
+// instance of pa_scalars_kernel sums the lines and applies Adam with one rate per image.  The instances without SHIFT are what the
+// entry points without shifts launch, unchanged.
+//
 // An all-zero wave under EMD_PSIART_NORMALISE: mean|b_k| = 0, so c_k = mean(r_k) / 0 is inf or NaN, and loss_k, L and the predictions
 // are NaN.  Nothing of it reaches the parameters: G_b is 0 where |b_k| = 0, that is everywhere, so every gradient is exactly 0 and a
 // step's Adam update sees g = 0 and stays finite.  It is not refused: the wave is on the device.
@@ -125,6 +132,20 @@ __device__ __forceinline__ double offset_of(const double* __restrict__ par, doub
 __device__ __forceinline__ cplx ctf_of(double tbase, double q, double T, double a20k) {
     double s, c;
     sincospi(tbase + a20k * q, &s, &c);
+    return make_double2(c * T, -s * T);
+}
+
+// 2 (i' d0 + j' d1) / S with jd1 = j' d1 and two_inv = 2 / S: every operation rounds on its own, so that the forward and the reverse
+// kernel form the same bits, and all of it is +-0 when both shifts are 0
+__device__ __forceinline__ double shift_term(int i, int S, double d0, double jd1, double two_inv) {
+    const double ip = (double)(i < (S >> 1) ? i : i - S);
+    return __dmul_rn(__fma_rn(ip, d0, jd1), two_inv);
+}
+
+// ctf_of with the shift's term added to t once tbase + a20_k q is formed: with sh = +-0 the bits of ctf_of
+__device__ __forceinline__ cplx ctf_shifted(double tbase, double q, double T, double a20k, double sh) {
+    double s, c;
+    sincospi(__dadd_rn(tbase + a20k * q, sh), &s, &c);
     return make_double2(c * T, -s * T);
 }
 
@@ -266,10 +287,12 @@ __global__ __launch_bounds__(256) void pa_rows_kernel(RowArgs a) {
 
 // grid (S), S * 16 bytes of LDS; NU = max(S / 256, 1) elements of the line per thread.  W: [j][i] (the rows' transforms, transposed);
 // PH: [j][i] = psi^; CT: [j][i] = (chi_base / pi, T); G: [N][i][j] (C_k psi^, inverse-transformed along the first axis only).
-template <int NU>
+// SHIFT: shifts [N][2] in pixels, read per image.
+template <int NU, bool SHIFT>
 __global__ __launch_bounds__(256) void pa_fwd_cols_kernel(const cplx* __restrict__ W, cplx* __restrict__ PH, double2* __restrict__ CT,
                                                           cplx* __restrict__ G, int N, Geom g, const cplx* __restrict__ tw,
-                                                          const double* __restrict__ par, const double* __restrict__ ramp, double scale) {
+                                                          const double* __restrict__ par, const double* __restrict__ ramp, double scale,
+                                                          const double* __restrict__ shifts) {
     extern __shared__ __align__(16) unsigned char smem[];
     cplx* line = reinterpret_cast<cplx*>(smem);
     const int tid = threadIdx.x, j = blockIdx.x, S = g.S;
@@ -300,11 +323,18 @@ __global__ __launch_bounds__(256) void pa_fwd_cols_kernel(const cplx* __restrict
     const double a20 = par[kA20], off = offset_of(par, scale);
     for (int k = 0; k < N; ++k) {
         const double a20k = a20 * ramp[k] + off;
+        double d0 = 0.0, jd1 = 0.0;
+        if (SHIFT) {
+            d0 = shifts[2 * k];
+            jd1 = __dmul_rn((double)(j < (S >> 1) ? j : j - S), shifts[2 * k + 1]);
+        }
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int i = tid + 256 * u;
             if (i < S) {
-                const cplx v = cmul(ph[u], ctf_of(tb[u], q[u], T[u], a20k));
+                const cplx C = SHIFT ? ctf_shifted(tb[u], q[u], T[u], a20k, shift_term(i, S, d0, jd1, 2.0 * inv))
+                                     : ctf_of(tb[u], q[u], T[u], a20k);
+                const cplx v = cmul(ph[u], C);
                 line[swz(i)] = make_double2(v.x, -v.y);
             }
         }
@@ -374,14 +404,18 @@ __global__ __launch_bounds__(256) void pa_loss_final_kernel(const double* __rest
 
 // grid (S), S * 16 bytes of LDS.  Tt: [N][j][i] (the rows' transforms of G_b, transposed); PH, CT as pa_fwd_cols_kernel wrote them;
 // U: [i][j] (sum_k conj(C_k) F_k, inverse-transformed along the first axis only); partial: [j][27].  HOLD: psi^ stays in registers
-// (NU <= 4); otherwise it is read again for every image.
-template <int NU, bool HOLD>
+// (NU <= 4); otherwise it is read again for every image.  SHIFT: C_k carries the shift's phase, and for every image the workgroup's
+// sums of Im z_k i' and of Im z_k go through wave_sum_lane0 and four LDS slots, so that no register lives across the loop for them;
+// partial_shift: [j][N][2] = (2 pi / S) (sum Im z_k i', j' sum Im z_k).
+template <int NU, bool HOLD, bool SHIFT>
 __global__ __launch_bounds__(256) void pa_bwd_cols_kernel(const cplx* __restrict__ Tt, const cplx* __restrict__ PH,
                                                           const double2* __restrict__ CT, cplx* __restrict__ U, double* __restrict__ partial,
                                                           int N, Geom g, const cplx* __restrict__ tw, const double* __restrict__ par,
-                                                          const double* __restrict__ ramp, double scale) {
+                                                          const double* __restrict__ ramp, double scale,
+                                                          const double* __restrict__ shifts, double* __restrict__ partial_shift) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ double red[4][kNP];
+    __shared__ double sred[SHIFT ? 4 : 1][SHIFT ? kMaxN : 1][2];
     cplx* line = reinterpret_cast<cplx*>(smem);
     const int tid = threadIdx.x, j = blockIdx.x, S = g.S;
     const double inv = 1.0 / (double)S, invn = inv * inv;
@@ -414,11 +448,18 @@ __global__ __launch_bounds__(256) void pa_bwd_cols_kernel(const cplx* __restrict
         }
         fft_line(line, S, tw);
         const double rk = ramp[k], a20k = a20 * rk + off;
+        double d0 = 0.0, jd1 = 0.0, sz_i = 0.0, sz = 0.0;
+        if (SHIFT) {
+            d0 = shifts[2 * k];
+            jd1 = __dmul_rn((double)(j < (S >> 1) ? j : j - S), shifts[2 * k + 1]);
+        }
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int i = tid + 256 * u;
             if (i < S) {
-                const cplx F = line[swz(i)], C = ctf_of(tb[u], q[u], T[u], a20k);
+                const cplx F = line[swz(i)];
+                const cplx C = SHIFT ? ctf_shifted(tb[u], q[u], T[u], a20k, shift_term(i, S, d0, jd1, 2.0 * inv))
+                                     : ctf_of(tb[u], q[u], T[u], a20k);
                 const cplx p = HOLD ? ph[u] : PH[base + i];
                 acc[u] = cadd(acc[u], cmul(F, make_double2(C.x, -C.y)));
                 const cplx y = cmul(C, p);                                          // z = conj(F / n) C psi^
@@ -426,6 +467,18 @@ __global__ __launch_bounds__(256) void pa_bwd_cols_kernel(const cplx* __restrict
                 s_im[u] += zi;
                 s_ramp[u] += rk * zi;
                 s_re[u] += zr;
+                if (SHIFT) {
+                    sz_i += zi * (double)(i < (S >> 1) ? i : i - S);
+                    sz += zi;
+                }
+            }
+        }
+        if (SHIFT) {
+            sz_i = wave_sum_lane0(sz_i);
+            sz = wave_sum_lane0(sz);
+            if ((tid & 63) == 0) {
+                sred[tid >> 6][k][0] = sz_i;
+                sred[tid >> 6][k][1] = sz;
             }
         }
     }
@@ -468,12 +521,29 @@ __global__ __launch_bounds__(256) void pa_bwd_cols_kernel(const cplx* __restrict
     }
     __syncthreads();
     if (tid < kNP) partial[(long)j * kNP + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    if (SHIFT && tid < 2 * N) {
+        const int k = tid >> 1, c = tid & 1;
+        const double s = ((sred[0][k][c] + sred[1][k][c]) + sred[2][k][c]) + sred[3][k][c];
+        partial_shift[((long)j * N + k) * 2 + c] = (2.0 * kPi * inv) * (c ? (double)(j < (S >> 1) ? j : j - S) * s : s);
+    }
 }
 
+struct ShiftArgs {
+    const double* partial;   // [S][N][2]
+    double *x, *m, *v;       // [N][2]: the shifts and their moments (a step), or NULL
+    const double* rates;     // [N], one per image for both axes (a step)
+    double* g;               // [N][2] or NULL
+    int N;
+};
+
 // one workgroup: g[p] = sum over the lines of partial[.][p] in ascending order; d off / d u = sech^2(u / scale); Adam on the scalars
-// and the step counter
-__global__ __launch_bounds__(64) void pa_scalars_kernel(const double* __restrict__ partial, int S, double* __restrict__ par, double scale,
-                                                        double* __restrict__ g_params, AdamArgs ad) {
+// and the step counter.  SHIFT (256 threads; 64 without): the threads 64 .. 64 + 2 N sum partial_shift over the lines in the same
+// order and apply Adam to the shifts with the same step and correction.  They start at the second wave on purpose: both sums are
+// chains of S dependent loads, and in one wave the two branches would run one after the other (measured: the step 14-28 % slower).
+template <bool SHIFT>
+__global__ __launch_bounds__(SHIFT ? 256 : 64) void pa_scalars_kernel(const double* __restrict__ partial, int S, double* __restrict__ par,
+                                                                      double scale, double* __restrict__ g_params, AdamArgs ad,
+                                                                      ShiftArgs sa) {
     const int p = threadIdx.x;
     const int t = ad.update ? ad.step[0] + 1 : 0;
     if (p < kNP) {
@@ -489,6 +559,16 @@ __global__ __launch_bounds__(64) void pa_scalars_kernel(const double* __restrict
             if (lr_t != 0.0) adam_update(par, ad.m_par, ad.v_par, p, g, lr_t, ad.beta1, ad.beta2, ad.eps);
         }
     }
+    if (SHIFT && p >= 64 && p < 64 + 2 * sa.N) {
+        const int e = p - 64;
+        double g = 0.0;
+        for (int l = 0; l < S; ++l) g += sa.partial[(long)l * 2 * sa.N + e];
+        if (sa.g) sa.g[e] = g;
+        if (ad.update) {
+            const double lr_t = sa.rates[e >> 1] * adam_correction(t, ad.beta1, ad.beta2);
+            if (lr_t != 0.0) adam_update(sa.x, sa.m, sa.v, e, g, lr_t, ad.beta1, ad.beta2, ad.eps);
+        }
+    }
     __syncthreads();   // every thread has read the counter
     if (ad.update && p == 0) ad.step[0] = t;
 }
@@ -496,10 +576,11 @@ __global__ __launch_bounds__(64) void pa_scalars_kernel(const double* __restrict
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 struct Layout {
-    size_t tw, W, PH, CT, G, Bw, part, part2, scal, partial, bytes;
+    size_t tw, W, PH, CT, G, Bw, part, part2, scal, partial, partial_shift, bytes;
 };
 
-Layout layout(int N, int S) {
+// shift: the layout without it, then partial_shift
+Layout layout(int N, int S, bool shift = false) {
     Layout l{};
     const size_t plane = emd::round256((size_t)S * S * sizeof(cplx)), stack = emd::round256((size_t)N * S * S * sizeof(cplx));
     size_t bytes = 0;
@@ -523,6 +604,8 @@ Layout layout(int N, int S) {
     bytes += emd::round256((size_t)N * 4 * sizeof(double));
     l.partial = bytes;
     bytes += emd::round256((size_t)S * kNP * sizeof(double));
+    l.partial_shift = bytes;
+    if (shift) bytes += emd::round256((size_t)S * N * 2 * sizeof(double));
     l.bytes = bytes;
     return l;
 }
@@ -540,11 +623,15 @@ struct Call {
     double wavelength, sampling, scale;
     double *losses, *pred, *g_amp, *g_phase, *g_params;
     AdamArgs adam;
+    bool shift;              // the SHIFT instances; the fields below are theirs
+    double* shifts;          // [N][2], read only without an update
+    double *m_shifts, *v_shifts, *g_shifts;
+    const double* shift_rates;
 };
 
 void run(const Call& c, void* workspace, hipStream_t st) {
     const int N = c.N, S = c.S;
-    const Layout l = layout(N, S);
+    const Layout l = layout(N, S, c.shift);
     char* ws = static_cast<char*>(workspace);
     cplx* tw = reinterpret_cast<cplx*>(ws + l.tw);
     cplx* W = reinterpret_cast<cplx*>(ws + l.W);
@@ -556,6 +643,7 @@ void run(const Call& c, void* workspace, hipStream_t st) {
     double* part2 = reinterpret_cast<double*>(ws + l.part2);
     double* scal = reinterpret_cast<double*>(ws + l.scal);
     double* partial = reinterpret_cast<double*>(ws + l.partial);
+    double* partial_shift = reinterpret_cast<double*>(ws + l.partial_shift);
     const Geom g = geom(S, c.wavelength, c.sampling);
     const size_t lds = (size_t)S * sizeof(cplx);
     hipLaunchKernelGGL(pa_twiddle_kernel, dim3((unsigned)emd::tiles_of(S, 256)), dim3(256), 0, st, tw, S);
@@ -571,7 +659,13 @@ void run(const Call& c, void* workspace, hipStream_t st) {
     r.part = part;
     r.dst = W;
     launch_rows<R_PSI>(r, 1, st);
-#define PA_FWD(NU) hipLaunchKernelGGL(pa_fwd_cols_kernel<NU>, dim3((unsigned)S), dim3(256), lds, st, W, PH, CT, G, N, g, tw, c.par, c.ramp, c.scale)
+#define PA_FWD(NU)                                                                                                                    \
+    if (c.shift)                                                                                                                      \
+        hipLaunchKernelGGL((pa_fwd_cols_kernel<NU, true>), dim3((unsigned)S), dim3(256), lds, st, W, PH, CT, G, N, g, tw, c.par, c.ramp, \
+                           c.scale, c.shifts);                                                                                        \
+    else                                                                                                                              \
+        hipLaunchKernelGGL((pa_fwd_cols_kernel<NU, false>), dim3((unsigned)S), dim3(256), lds, st, W, PH, CT, G, N, g, tw, c.par, c.ramp, \
+                           c.scale, nullptr)
     switch (S / 256) {
         case 0:
         case 1: PA_FWD(1); break;
@@ -585,12 +679,17 @@ void run(const Call& c, void* workspace, hipStream_t st) {
     launch_rows<R_MOD>(r, N, st);
     hipLaunchKernelGGL(pa_loss_kernel, dim3((unsigned)S, (unsigned)N), dim3(256), 0, st, Bw, c.images, S, c.flags, part, part2, c.pred);
     hipLaunchKernelGGL(pa_loss_final_kernel, dim3(1), dim3(256), 0, st, part, part2, N, S, c.flags, c.weights, scal, c.losses);
-    if (!c.adam.update && !c.g_amp && !c.g_phase && !c.g_params) return;
+    if (!c.adam.update && !c.g_amp && !c.g_phase && !c.g_params && !c.g_shifts) return;
     r.src = Bw;
     r.dst = G;
     launch_rows<R_GB>(r, N, st);
-#define PA_BWD(NU, HOLD) \
-    hipLaunchKernelGGL((pa_bwd_cols_kernel<NU, HOLD>), dim3((unsigned)S), dim3(256), lds, st, G, PH, CT, W, partial, N, g, tw, c.par, c.ramp, c.scale)
+#define PA_BWD(NU, HOLD)                                                                                                              \
+    if (c.shift)                                                                                                                      \
+        hipLaunchKernelGGL((pa_bwd_cols_kernel<NU, HOLD, true>), dim3((unsigned)S), dim3(256), lds, st, G, PH, CT, W, partial, N, g, tw, \
+                           c.par, c.ramp, c.scale, c.shifts, partial_shift);                                                          \
+    else                                                                                                                              \
+        hipLaunchKernelGGL((pa_bwd_cols_kernel<NU, HOLD, false>), dim3((unsigned)S), dim3(256), lds, st, G, PH, CT, W, partial, N, g, tw, \
+                           c.par, c.ramp, c.scale, nullptr, nullptr)
     switch (S / 256) {
         case 0:
         case 1: PA_BWD(1, true); break;
@@ -606,8 +705,13 @@ void run(const Call& c, void* workspace, hipStream_t st) {
         r.adam = c.adam;
         launch_rows<R_GRAD>(r, 1, st);
     }
-    if (c.adam.update || c.g_params)
-        hipLaunchKernelGGL(pa_scalars_kernel, dim3(1), dim3(64), 0, st, partial, S, c.par, c.scale, c.g_params, c.adam);
+    if (!c.adam.update && !c.g_params && !c.g_shifts) return;
+    if (c.shift) {
+        const ShiftArgs sa{partial_shift, c.shifts, c.m_shifts, c.v_shifts, c.shift_rates, c.g_shifts, N};
+        hipLaunchKernelGGL(pa_scalars_kernel<true>, dim3(1), dim3(256), 0, st, partial, S, c.par, c.scale, c.g_params, c.adam, sa);
+    } else {
+        hipLaunchKernelGGL(pa_scalars_kernel<false>, dim3(1), dim3(64), 0, st, partial, S, c.par, c.scale, c.g_params, c.adam, ShiftArgs{});
+    }
 }
 
 bool shape_ok(const char* who, int N, int S, double wavelength, double sampling, double scale, int flags) {
@@ -751,6 +855,132 @@ extern "C" int emd_psiart_step_f64(const float* images, int N, int S, double* am
     c.g_phase = g_phase;
     c.g_params = g_params;
     c.adam = AdamArgs{m_amp, v_amp, m_phase, v_phase, m_params, v_params, step, rates, beta1, beta2, epsilon, 1};
+    run(c, workspace, static_cast<hipStream_t>(stream));
+    return emd::check_launch(who);
+}
+
+// ---- with per-image shifts: the same checks, the SHIFT instances -------------------------------------------------------------------
+
+extern "C" size_t emd_psiart_shift_workspace_bytes(int N, int S) {
+    if (N < 1 || N > kMaxN || !size_ok(S)) return 0;
+    return layout(N, S, true).bytes;
+}
+
+extern "C" int emd_psiart_shift_loss_grad_f64(const float* images, int N, int S, const double* amp, const double* phase,
+                                              const double* params, const double* shifts, const double* ramp, const double* weights,
+                                              double wavelength, double sampling, double offset_scale, int flags, double* losses,
+                                              double* pred, double* g_amp, double* g_phase, double* g_params, double* g_shifts,
+                                              void* workspace, size_t workspace_bytes, emd_stream_t stream) {
+    const char* who = "emd_psiart_shift_loss_grad_f64";
+    if (!shape_ok(who, N, S, wavelength, sampling, offset_scale, flags)) return EMD_E_INVALID;
+    const size_t field = (size_t)S * S * sizeof(double), pairs = (size_t)N * 2 * sizeof(double);
+    const emd::Range rg[] = {{workspace, layout(N, S, true).bytes, 16, false, false},
+                             {images, (size_t)N * S * S * sizeof(float), 4, false, true},
+                             {amp, field, 8, false, true},
+                             {phase, field, 8, false, true},
+                             {params, kNP * sizeof(double), 8, false, true},
+                             {shifts, pairs, 8, false, true},
+                             {ramp, (size_t)N * sizeof(double), 8, false, true},
+                             {weights, (size_t)N * sizeof(double), 8, false, true},
+                             {losses, (size_t)(N + 1) * sizeof(double), 8, false, false},
+                             {pred, (size_t)N * field, 8, true, false},
+                             {g_amp, field, 8, true, false},
+                             {g_phase, field, 8, true, false},
+                             {g_params, kNP * sizeof(double), 8, true, false},
+                             {g_shifts, pairs, 8, true, false}};
+    const int rc = emd::check_ranges(who, rg, 14, kAligned, &workspace_bytes);
+    if (rc != EMD_OK) return rc;
+    Call c{};
+    c.images = images;
+    c.N = N;
+    c.S = S;
+    c.flags = flags;
+    c.amp = const_cast<double*>(amp);      // read only without an update
+    c.phase = const_cast<double*>(phase);
+    c.par = const_cast<double*>(params);
+    c.ramp = ramp;
+    c.weights = weights;
+    c.wavelength = wavelength;
+    c.sampling = sampling;
+    c.scale = offset_scale;
+    c.losses = losses;
+    c.pred = pred;
+    c.g_amp = g_amp;
+    c.g_phase = g_phase;
+    c.g_params = g_params;
+    c.shift = true;
+    c.shifts = const_cast<double*>(shifts);
+    c.g_shifts = g_shifts;
+    run(c, workspace, static_cast<hipStream_t>(stream));
+    return emd::check_launch(who);
+}
+
+extern "C" int emd_psiart_shift_step_f64(const float* images, int N, int S, double* amp, double* phase, double* params, double* shifts,
+                                         const double* ramp, const double* weights, double wavelength, double sampling,
+                                         double offset_scale, int flags, double* m_amp, double* v_amp, double* m_phase, double* v_phase,
+                                         double* m_params, double* v_params, double* m_shifts, double* v_shifts, int* step,
+                                         const double* rates, const double* shift_rates, double beta1, double beta2, double epsilon,
+                                         double* losses, double* pred, double* g_amp, double* g_phase, double* g_params, double* g_shifts,
+                                         void* workspace, size_t workspace_bytes, emd_stream_t stream) {
+    const char* who = "emd_psiart_shift_step_f64";
+    if (!shape_ok(who, N, S, wavelength, sampling, offset_scale, flags)) return EMD_E_INVALID;
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && epsilon > 0.0)) {
+        emd::set_error("%s: 0 <= beta1, beta2 < 1 and epsilon > 0 (got %g, %g, %g)", who, beta1, beta2, epsilon);
+        return EMD_E_INVALID;
+    }
+    const size_t field = (size_t)S * S * sizeof(double), vec = kNP * sizeof(double), pairs = (size_t)N * 2 * sizeof(double);
+    const emd::Range rg[] = {{workspace, layout(N, S, true).bytes, 16, false, false},
+                             {images, (size_t)N * S * S * sizeof(float), 4, false, true},
+                             {ramp, (size_t)N * sizeof(double), 8, false, true},
+                             {weights, (size_t)N * sizeof(double), 8, false, true},
+                             {rates, (kNP + 2) * sizeof(double), 8, false, true},
+                             {shift_rates, (size_t)N * sizeof(double), 8, false, true},
+                             {amp, field, 8, false, false},
+                             {phase, field, 8, false, false},
+                             {params, vec, 8, false, false},
+                             {shifts, pairs, 8, false, false},
+                             {m_amp, field, 8, false, false},
+                             {v_amp, field, 8, false, false},
+                             {m_phase, field, 8, false, false},
+                             {v_phase, field, 8, false, false},
+                             {m_params, vec, 8, false, false},
+                             {v_params, vec, 8, false, false},
+                             {m_shifts, pairs, 8, false, false},
+                             {v_shifts, pairs, 8, false, false},
+                             {step, sizeof(int), 4, false, false},
+                             {losses, (size_t)(N + 1) * sizeof(double), 8, false, false},
+                             {pred, (size_t)N * field, 8, true, false},
+                             {g_amp, field, 8, true, false},
+                             {g_phase, field, 8, true, false},
+                             {g_params, vec, 8, true, false},
+                             {g_shifts, pairs, 8, true, false}};
+    const int rc = emd::check_ranges(who, rg, 25, kAligned, &workspace_bytes);
+    if (rc != EMD_OK) return rc;
+    Call c{};
+    c.images = images;
+    c.N = N;
+    c.S = S;
+    c.flags = flags;
+    c.amp = amp;
+    c.phase = phase;
+    c.par = params;
+    c.ramp = ramp;
+    c.weights = weights;
+    c.wavelength = wavelength;
+    c.sampling = sampling;
+    c.scale = offset_scale;
+    c.losses = losses;
+    c.pred = pred;
+    c.g_amp = g_amp;
+    c.g_phase = g_phase;
+    c.g_params = g_params;
+    c.adam = AdamArgs{m_amp, v_amp, m_phase, v_phase, m_params, v_params, step, rates, beta1, beta2, epsilon, 1};
+    c.shift = true;
+    c.shifts = shifts;
+    c.m_shifts = m_shifts;
+    c.v_shifts = v_shifts;
+    c.g_shifts = g_shifts;
+    c.shift_rates = shift_rates;
     run(c, workspace, static_cast<hipStream_t>(stream));
     return emd::check_launch(who);
 }

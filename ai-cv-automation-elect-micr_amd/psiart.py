@@ -13,9 +13,16 @@ is ``set_weights`` once with a device tensor, then overwriting it between replay
 
 Deviations from the reference: the normalisation is ``mean(r_k) / mean|b_k|`` (the reference: a complex mean against the mean of the
 intensity); the loss is on ``|b_k|`` (the reference subtracts a complex tensor from a real one); the ramp and the weights are
-arguments; a rate per parameter replaces ``var_to_train``.  Not here: the spatial-coherence and aperture envelopes, the per-image
-affine transforms and ``central_crop`` (align first with ``emdenoise.affine.align``), TIFF I/O, the ``learning_rate.txt`` polling,
-checkpoints, padding."""
+arguments; a rate per parameter replaces ``var_to_train``.  Not here: the spatial-coherence and aperture envelopes, the rotation,
+scale and shear of the per-image affine transforms and ``central_crop`` (align first with ``emdenoise.affine.align``), TIFF I/O, the
+``learning_rate.txt`` polling, checkpoints, padding.
+
+Per-image shifts, the translation part of the per-image transforms of psi-art.py:229-266: ``shifts`` ``[N,2]`` in
+pixels, along axis 0 then axis 1, move prediction k by ``(d0_k, d1_k)`` as a linear phase on its transfer function; whole pixels
+``(a, b)`` are ``numpy.roll(p_k, (a, b), (0, 1))``.  The shift is circular: what leaves on one side enters on the other, so a residual
+of up to a pixel after ``crop_stack`` wraps one border line into the loss.  ``PsiArtFit(shifts=True)`` trains them with Adam beside
+everything else, one rate per image; the middle image's rate is 0 by default, because a translation of every image at once is a
+translation of the wave and one image has to fix that gauge."""
 from __future__ import annotations
 
 import numpy as np
@@ -174,6 +181,18 @@ def _images(name, images):
     return N, S
 
 
+def _shift_pairs(name, v, N, device):
+    """``shifts`` -> float64 CUDA tensor [N,2].  A contiguous float64 CUDA tensor of that shape is used where it is; anything else is
+    checked on the host and uploaded (not while capturing)."""
+    import torch
+
+    shp = tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+    if shp != (N, 2):
+        raise ValueError(f"{name}: shifts are [N,2] = [{N},2], in pixels (got a shape of {shp})")
+    return _vector(name, "shifts", v.reshape(-1) if isinstance(v, torch.Tensor) else np.asarray(v, np.float64).reshape(-1), 2 * N,
+                   device).view(N, 2)
+
+
 def _to_dev(a, dtype, device):
     import torch
 
@@ -203,7 +222,8 @@ def ctf(S, wavelength, sampling, params, ramp=(0.0,), offset_scale=1.0):
     return out.cpu().numpy() if as_np else out
 
 
-def _loss_grad(name, images, amplitude, phase, params, ramp, weights, wavelength, sampling, offset_scale, flags, want_pred, want_grad):
+def _loss_grad(name, images, amplitude, phase, params, ramp, weights, wavelength, sampling, offset_scale, flags, want_pred, want_grad,
+               shifts=None):
     import torch
 
     N, S = _images(name, images)
@@ -215,6 +235,9 @@ def _loss_grad(name, images, amplitude, phase, params, ramp, weights, wavelength
     params = _host_vector(name, "params", params, NPARAM)
     ramp = _host_vector(name, "ramp", defocus_ramp(N) if ramp is None else ramp, N)
     weights = _host_vector(name, "weights", np.full(N, 1.0 / N) if weights is None else weights, N)
+    if shifts is not None and not _is_dev(shifts):   # checked on the host before anything moves
+        if np.shape(shifts) != (N, 2) or not np.isfinite(np.asarray(shifts, np.float64)).all():
+            raise ValueError(f"{name}: shifts are [N,2] = [{N},2] finite numbers, in pixels (got a shape of {np.shape(shifts)})")
     as_np = not _is_dev(images) and not _is_dev(amplitude)
     device = _device(images, amplitude, phase)
     A, P = _to_dev(amplitude, torch.float64, device), _to_dev(phase, torch.float64, device)
@@ -224,21 +247,34 @@ def _loss_grad(name, images, amplitude, phase, params, ramp, weights, wavelength
     out = {"losses": f64(N + 1), "predictions": f64(N, S, S) if want_pred else None, "g_amplitude": f64(S, S) if want_grad else None,
            "g_phase": f64(S, S) if want_grad else None, "g_params": f64(NPARAM) if want_grad else None}
     lib = _lib.load()
-    nbytes = lib.emd_psiart_workspace_bytes(N, S)
-    ws = _ws(nbytes, device)
-    _lib.check(lib.emd_psiart_loss_grad_f64(_p(x), N, S, _p(A), _p(P), _p(p), _p(r), _p(w), float(wavelength), float(sampling),
-                                            float(offset_scale), flags, _p(out["losses"]), _p(out["predictions"]), _p(out["g_amplitude"]),
-                                            _p(out["g_phase"]), _p(out["g_params"]), _p(ws), nbytes, _lib.stream_ptr()),
-               "emd_psiart_loss_grad_f64")
+    if shifts is None:
+        nbytes = lib.emd_psiart_workspace_bytes(N, S)
+        ws = _ws(nbytes, device)
+        _lib.check(lib.emd_psiart_loss_grad_f64(_p(x), N, S, _p(A), _p(P), _p(p), _p(r), _p(w), float(wavelength), float(sampling),
+                                                float(offset_scale), flags, _p(out["losses"]), _p(out["predictions"]),
+                                                _p(out["g_amplitude"]), _p(out["g_phase"]), _p(out["g_params"]), _p(ws), nbytes,
+                                                _lib.stream_ptr()),
+                   "emd_psiart_loss_grad_f64")
+    else:
+        d = _shift_pairs(name, shifts, N, device)
+        out["g_shifts"] = f64(N, 2) if want_grad else None
+        nbytes = lib.emd_psiart_shift_workspace_bytes(N, S)
+        ws = _ws(nbytes, device)
+        _lib.check(lib.emd_psiart_shift_loss_grad_f64(_p(x), N, S, _p(A), _p(P), _p(p), _p(d), _p(r), _p(w), float(wavelength),
+                                                      float(sampling), float(offset_scale), flags, _p(out["losses"]),
+                                                      _p(out["predictions"]), _p(out["g_amplitude"]), _p(out["g_phase"]),
+                                                      _p(out["g_params"]), _p(out["g_shifts"]), _p(ws), nbytes, _lib.stream_ptr()),
+                   "emd_psiart_shift_loss_grad_f64")
     out = {k: v for k, v in out.items() if v is not None}
     out["loss"] = out["losses"][N]
     out["losses"] = out["losses"][:N]
     return {k: v.cpu().numpy() for k, v in out.items()} if as_np else out
 
 
-def forward(amplitude, phase, params, ramp, wavelength, sampling, offset_scale=1.0, images=None, from_intensity=True):
+def forward(amplitude, phase, params, ramp, wavelength, sampling, offset_scale=1.0, images=None, from_intensity=True, shifts=None):
     """The model's images ``p_k = c_k |ifft2(C_k fft2(A exp(i P)))|``, float64 ``[len(ramp),S,S]``.  Without ``images`` ``c_k = 1``;
-    with them ``c_k = mean(r_k) / mean|b_k|`` (``r_k`` the root of image k; ``from_intensity=False``: ``|image_k|``)."""
+    with them ``c_k = mean(r_k) / mean|b_k|`` (``r_k`` the root of image k; ``from_intensity=False``: ``|image_k|``).  ``shifts``
+    ``[len(ramp),2]`` (numpy or a float64 CUDA tensor): image k moved circularly by ``(d0_k, d1_k)`` pixels."""
     import torch
 
     shp = tuple(amplitude.shape) if hasattr(amplitude, "shape") else np.shape(amplitude)
@@ -252,19 +288,21 @@ def forward(amplitude, phase, params, ramp, wavelength, sampling, offset_scale=1
         _side("forward", shp[0])
         images = torch.zeros((n, shp[0], shp[0]), dtype=torch.float32, device=_device(amplitude, phase)) if _is_dev(amplitude) else \
             np.zeros((n, shp[0], shp[0]), np.float32)
-    return _loss_grad("forward", images, amplitude, phase, params, ramp, None, wavelength, sampling, offset_scale, flags, True, False)[
-        "predictions"]
+    return _loss_grad("forward", images, amplitude, phase, params, ramp, None, wavelength, sampling, offset_scale, flags, True, False,
+                      shifts)["predictions"]
 
 
 def loss_and_gradients(images, amplitude, phase, params, wavelength, sampling, ramp=None, weights=None, offset_scale=1.0, normalise=True,
-                       from_intensity=True, gradients=True, predictions=False):
+                       from_intensity=True, gradients=True, predictions=False, shifts=None):
     """The loss of the model against ``images`` and its gradients: a dict with ``losses`` ``[N]`` (``mean((p_k - r_k)^2)``), ``loss``
     (``sum_k w_k loss_k``) and, with ``gradients``, ``g_amplitude`` and ``g_phase`` ``[S,S]`` and ``g_params`` ``[27]`` (the order of
     ``PARAM_NAMES``; the last is the gradient by the raw offset u); with ``predictions`` also ``predictions`` ``[N,S,S]``.  ``ramp``
-    defaults to ``defocus_ramp(N)``, ``weights`` to ``1 / N``.  Without ``gradients`` the reverse launches are not made."""
+    defaults to ``defocus_ramp(N)``, ``weights`` to ``1 / N``.  Without ``gradients`` the reverse launches are not made.  With
+    ``shifts`` ``[N,2]`` (pixels along axis 0, then axis 1; numpy or a float64 CUDA tensor) image k of the model is moved circularly by
+    ``(d0_k, d1_k)`` and the gradients gain ``g_shifts`` ``[N,2]``."""
     flags = (NORMALISE if normalise else 0) | (0 if from_intensity else AMPLITUDES)
     return _loss_grad("loss_and_gradients", images, amplitude, phase, params, ramp, weights, wavelength, sampling, offset_scale, flags,
-                      predictions, gradients)
+                      predictions, gradients, shifts)
 
 
 class PsiArtFit:
@@ -277,11 +315,16 @@ class PsiArtFit:
     "amplitude", "phase", the symbols, "focal_spread", "defocus_offset"), 29 numbers in that order, or a float64 CUDA tensor of 29
     entries that is used where it is.  A rate of 0 means "not trained".
 
+    ``shifts=True`` (from 0) or an ``[N,2]`` array (pixels along axis 0, then axis 1) also trains a circular sub-pixel shift of every
+    image, at ``shift_rate`` (default ``learning_rate``); ``set_shift_rates`` takes one rate per image.  The ``middle`` image's rate
+    starts at 0: moving every image by the same amount is the same as moving the wave, so one image is the gauge and stays where it
+    is.  With ``shifts=None`` nothing of this exists and the calls are the ones without shifts.
+
     ``step(n)`` makes n steps, each ten launches on the current stream and nothing else: it can be captured."""
 
     def __init__(self, images, wavelength, sampling, symbols=("a20", "a40"), estimates=(50., 0.), middle=None, ramp=None, normalise=True,
                  from_intensity=True, learning_rate=1e-3, rates=None, beta1=0.99, beta2=0.999, epsilon=0.1, offset_scale=1.0,
-                 focal_spread=None):
+                 focal_spread=None, shifts=None, shift_rate=None):
         import torch
 
         N, S = _images("PsiArtFit", images)
@@ -310,6 +353,15 @@ class PsiArtFit:
             rates = self._rates_host(default if rates is None else rates)
         if ramp is not None and not _is_dev(ramp) and (np.shape(ramp) != (N,) or not np.isfinite(np.asarray(ramp, np.float64)).all()):
             raise ValueError(f"PsiArtFit: ramp must be {N} finite numbers")
+        if shifts is None and shift_rate is not None:
+            raise ValueError("PsiArtFit: shift_rate without shifts (pass shifts=True to train them from 0)")
+        if shifts is not None:
+            shift_rate = learning_rate if shift_rate is None else shift_rate
+            if not (np.isfinite(shift_rate) and shift_rate >= 0):
+                raise ValueError(f"PsiArtFit: shift_rate must be finite and not negative (got {shift_rate!r})")
+            d0 = np.zeros((N, 2), np.float64) if shifts is True else shifts
+            if not _is_dev(d0) and (np.shape(d0) != (N, 2) or not np.isfinite(np.asarray(d0, np.float64)).all()):
+                raise ValueError(f"PsiArtFit: shifts are True or [N,2] = [{N},2] finite numbers, in pixels")
         self._as_np = not _is_dev(images)
         self.device = device = _device(images)
         self._rates = self._rate_tensor(rates)
@@ -323,7 +375,14 @@ class PsiArtFit:
         self._moments = [torch.zeros_like(t) for t in (self._amp, self._amp, self._phase, self._phase, self._params, self._params)]
         self._step = torch.zeros(1, dtype=torch.int32, device=device)
         self._losses = torch.zeros(N + 1, dtype=torch.float64, device=device)
-        self._nbytes = _lib.load().emd_psiart_workspace_bytes(N, S)
+        self._shifts = None
+        if shifts is not None:
+            self._shifts = _shift_pairs("PsiArtFit", d0, N, device).clone()
+            self._shift_moments = [torch.zeros_like(self._shifts), torch.zeros_like(self._shifts)]
+            r0 = np.full(N, float(shift_rate))
+            r0[self.middle] = 0.0                     # the gauge: a common translation belongs to the wave
+            self._shift_rates = torch.from_numpy(r0).to(device)
+        self._nbytes = (_lib.load().emd_psiart_workspace_bytes if shifts is None else _lib.load().emd_psiart_shift_workspace_bytes)(N, S)
         self._ws = _ws(self._nbytes, device)
 
     @staticmethod
@@ -376,12 +435,40 @@ class PsiArtFit:
             self._weights.copy_(torch.from_numpy(h.copy()))
         return self
 
+    def set_shift_rates(self, v):
+        """One rate per image for its shift (both axes).  A float64 CUDA tensor of N entries is adopted where it is; anything else is
+        copied into the tensor in use, so that a captured ``step`` sees it on replay.  A rate of 0 freezes that image's shift."""
+        import torch
+
+        if self._shifts is None:
+            raise ValueError("PsiArtFit.set_shift_rates: this fit has no shifts (construct it with shifts=True or an [N,2] array)")
+        if _is_dev(v):
+            self._shift_rates = _vector("PsiArtFit", "shift rates", v, self.N, self.device)
+        else:
+            h = np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v, np.float64).reshape(-1)
+            if h.shape != (self.N,) or not np.isfinite(h).all() or (h < 0).any():
+                raise ValueError(f"PsiArtFit: the shift rates are {self.N} finite numbers >= 0")
+            self._shift_rates.copy_(torch.from_numpy(h.copy()))
+        return self
+
     def step(self, n=1):
         """n Adam steps.  ``losses`` and ``loss`` afterwards are those of the last step, before its update."""
         if int(n) != n or n < 0:
             raise ValueError(f"PsiArtFit.step: n must be a non-negative integer (got {n!r})")
         lib = _lib.load()
         m = self._moments
+        if self._shifts is not None:
+            sm = self._shift_moments
+            for _ in range(int(n)):
+                _lib.check(lib.emd_psiart_shift_step_f64(_p(self.images), self.N, self.S, _p(self._amp), _p(self._phase), _p(self._params),
+                                                         _p(self._shifts), _p(self._ramp), _p(self._weights), self.wavelength,
+                                                         self.sampling, self.offset_scale, self.flags, _p(m[0]), _p(m[1]), _p(m[2]),
+                                                         _p(m[3]), _p(m[4]), _p(m[5]), _p(sm[0]), _p(sm[1]), _p(self._step),
+                                                         _p(self._rates), _p(self._shift_rates), self.beta1, self.beta2, self.epsilon,
+                                                         _p(self._losses), _p(None), _p(None), _p(None), _p(None), _p(None), _p(self._ws),
+                                                         self._nbytes, _lib.stream_ptr()),
+                           "emd_psiart_shift_step_f64")
+            return self
         for _ in range(int(n)):
             _lib.check(lib.emd_psiart_step_f64(_p(self.images), self.N, self.S, _p(self._amp), _p(self._phase), _p(self._params),
                                                _p(self._ramp), _p(self._weights), self.wavelength, self.sampling, self.offset_scale,
@@ -420,6 +507,11 @@ class PsiArtFit:
     def params(self):
         """The 27 scalars in the order of ``PARAM_NAMES`` (the last is the raw offset u)."""
         return self._out(self._params)
+
+    @property
+    def shifts(self):
+        """The shifts ``[N,2]`` in pixels (axis 0, then axis 1), or None for a fit without them."""
+        return None if self._shifts is None else self._out(self._shifts)
 
     @property
     def steps(self):

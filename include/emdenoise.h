@@ -1586,7 +1586,8 @@ int emd_affine_limits_i32(const double* C, int N, int H, int W, int* limits, emd
  *     of 0 leaves the parameter and its moments bitwise unchanged (a field with rate 0 is not written at all).
  * Deviations from the reference: the normalisation uses mean|b_k| against the mean of the root image (the reference: a complex mean
  *     against the mean of the intensity); the loss is on |b_k|; ramp (3 |k - middle| there) and the weights (its bootstrapping window)
- *     are arguments.  Not here: the spatial-coherence and aperture envelopes, the per-image affine transforms, padding.
+ *     are arguments.  Not here: the spatial-coherence and aperture envelopes, the per-image affine transforms (their translation
+ *     part: the emd_psiart_shift_* entry points below), padding.
  * No floating-point atomics, fixed summation orders: bitwise reproducible.  The workspace is the caller's and 16-byte aligned, arrays
  * of doubles 8-byte, the images and the step counter 4-byte; outputs and the workspace overlap nothing.  Launches only: capturable. */
 #define EMD_PSIART_NPARAM 27
@@ -1604,6 +1605,33 @@ int emd_psiart_step_f64(const float* images, int N, int S, double* amp, double* 
                         double* v_amp, double* m_phase, double* v_phase, double* m_params, double* v_params, int* step, const double* rates,
                         double beta1, double beta2, double epsilon, double* losses, double* pred, double* g_amp, double* g_phase,
                         double* g_params, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+
+/* The same fit with a trainable sub-pixel shift of every image: the translation part of the per-image transforms of
+ * psi-art.py:229-266.  shifts [N][2] doubles, in pixels, along the first axis (the row index) then the second.  With the signed indices
+ * i' = (i < S/2 ? i : i - S), j' likewise (numpy.fft.fftfreq(S) times S):
+ *     t_k = (tbase + a20_k theta^2 / lam) + 2 (i' d0_k + j' d1_k) / S;   C_k = (cospi(t_k) - i sinpi(t_k)) T,
+ * that is C_k times exp(-2 pi i (i' d0_k + j' d1_k) / S): prediction k is moved by (d0_k, d1_k) pixels, and a whole-pixel shift
+ * (a, b) is numpy.roll(p_k, (a, b), (0, 1)).  The shift is CIRCULAR: what leaves on one side enters on the other, so a residual of
+ * up to one pixel after cropping wraps one border line of the image into the loss.  Modulus, c_k, loss and weights are as above.
+ * With all shifts 0 the argument of cospi / sinpi, and so every output, has the bits of the entry points without shifts.
+ *     dL/dd0_k = sum_{i,j} Im z_k (2 pi i' / S);   dL/dd1_k = sum_{i,j} Im z_k (2 pi j' / S),  z_k formed with the shifted C_k: sums
+ *     per image, in a fixed order (lanes, the four waves, the lines ascending).  g_shifts [N][2] may be NULL.
+ * Step: Adam on the shifts with the same t and correction; shift_rates [N], one rate per image for both of its axes; a rate of 0 leaves
+ *     that image's shift and its moments bitwise unchanged.  A translation of all images at once is a translation of the wave: keep one
+ *     image (the middle one) at rate 0 as the gauge.  m_shifts, v_shifts [N][2].
+ * emd_psiart_shift_workspace_bytes: the layout of emd_psiart_workspace_bytes, then partial_shift (S N 2 doubles).  The same refusals
+ * as above, before any launch; ten launches a step; capturable, shifts and rates are read on the device. */
+size_t emd_psiart_shift_workspace_bytes(int N, int S);
+int emd_psiart_shift_loss_grad_f64(const float* images, int N, int S, const double* amp, const double* phase, const double* params,
+                                   const double* shifts, const double* ramp, const double* weights, double wavelength, double sampling,
+                                   double offset_scale, int flags, double* losses, double* pred, double* g_amp, double* g_phase,
+                                   double* g_params, double* g_shifts, void* workspace, size_t workspace_bytes, emd_stream_t stream);
+int emd_psiart_shift_step_f64(const float* images, int N, int S, double* amp, double* phase, double* params, double* shifts,
+                              const double* ramp, const double* weights, double wavelength, double sampling, double offset_scale, int flags,
+                              double* m_amp, double* v_amp, double* m_phase, double* v_phase, double* m_params, double* v_params,
+                              double* m_shifts, double* v_shifts, int* step, const double* rates, const double* shift_rates, double beta1,
+                              double beta2, double epsilon, double* losses, double* pred, double* g_amp, double* g_phase, double* g_params,
+                              double* g_shifts, void* workspace, size_t workspace_bytes, emd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * cv2.resize for one-channel float32 (csrc/resample.hip, csrc/resize_taps.hpp): the reference's
